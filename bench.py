@@ -13,6 +13,12 @@ analysis for the permutation it uses.
 
 One JSON line on stdout (rank 0).
 
+A plain run does only what the headline needs: set-up, warm-up, the `--steps` timed steps and the line, whose `value`,
+`ms_per_step`, `ms_factor` / `ms_solve`, `config` and `ranks` it fills; every other measurement and check of the line is null.
+`--full` adds them all (the two-call split, the residual, `roofline`, `cpu_baseline` and the `klu`, `extra`, `ipm` and `one_shot`
+legs below).  `--dump-outputs DIR` writes what the last timed step computed (the solution x and the diagonal of the factor) as
+float64 .npy files: the inputs are fixed by the arguments, so two builds can be compared output for output.
+
 Ranks.  `python bench.py --gpus N` with no torchrun environment starts the N ranks itself: the parent process -- before it
 imports torch or touches HIP -- starts N children with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set, lets
 rank 0's line through and exits non-zero when any child does.  Under `python -m torch.distributed.run ... bench.py --gpus N`
@@ -21,7 +27,7 @@ the environment is already there and is used as it is.  N > 1 shards ONE system 
 panel broadcasts over RCCL) -> "scaling": "strong"; `--dist replicas` (every rank its own system, no data-path collective,
 "weak") stays available.  `--workload lap3d --grid 200` is BASELINE configs[4].
 
-The line carries `roofline` (dominant kernel family, timed live with HIP events on the stream it runs on), `cpu_baseline` (host
+With --full the line carries `roofline` (dominant kernel family, timed live with HIP events on the stream it runs on), `cpu_baseline` (host
 supernodal restatement on the host cores that go with one GPU and on 32 threads, SciPy SuperLU and the simplicial oracle
 beside it), `ipm` (IPM iterations/s with its own roofline and CPU baseline), `extra` (the north-star systems measured in the
 same run: 21-point stencil 1000^2 and the 7-point Laplacian 100^3, each with its own roofline and CPU baseline), `one_shot`
@@ -52,8 +58,13 @@ FP64_MFMA_PEAK_TF = 78.6     # MI355X FP64 matrix = vector peak; 2
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1, help="ranks = GPUs; without a torchrun environment this process starts them itself")
-    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--steps", type=int, default=40, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: two-call split, residual, roofline, CPU baselines, "
+                    "klu / extra / ipm / one_shot legs (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all; a fixed, seeded "
+                         "sample of an array that would not fit)")
     ap.add_argument("--grid", type=int, default=0, help="grid side (default: 1000 for the 5-pt Laplacian of config 2, 100 for --workload lap3d)")
     ap.add_argument("--workload", default="lap2d", choices=["lap2d", "lap3d", "stencil21"],
                     help="lap2d = BASELINE configs[1] (5-pt Laplacian, the headline); lap3d = 7-pt Laplacian on a cube (configs[4] is --grid 200); "
@@ -78,7 +89,26 @@ def parse():
                     help="N > 1 ranks: 'subtree' (default) = ONE system -- the N = 1 workload -- sharded over the ranks (kvxopt_amd.dist.DistFactor: "
                          "subtrees by proportional mapping, block-cyclic top fronts with panel broadcasts; strong scaling); "
                          "'replicas' = every rank factors its own system (weak scaling, no data-path collective)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(d, arrays, limit=DUMP_BYTES):
+    """--dump-outputs: every array as d/<name>.npy in float64.  The arrays share `limit` bytes equally; one larger than its share
+    is replaced by a sample of its flattened entries at sorted positions drawn by default_rng(0) -- the same positions for the same
+    size, so that two runs with the same arguments write comparable files."""
+    os.makedirs(d, exist_ok=True)
+    cap = max(1, limit // (8 * max(len(arrays), 1)))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > cap:
+            a = a.reshape(-1, order="F")[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def spawn_ranks(args):
@@ -525,10 +555,12 @@ class Plumbing:
         return ("HIP runtime of the PyTorch wheel %s" % self.torch.version.hip) if self.torch is not None else "system HIP runtime (/opt/rocm), torch not imported"
 
 
-def measure_system(args, pl, dist, rank, world, dev, wl, nrhs, steps, warmup, mode, family="auto", cpu="full", pmc_key=None):
-    """Factor + solve of one system, timed as the contract says (barrier + synchronize on both sides, MAX over the ranks),
-    with the roofline of the dominant kernel family (HIP events on the factor's own streams) and the CPU baselines beside it.
+def measure_system(args, pl, dist, rank, world, dev, wl, nrhs, steps, warmup, mode, family="auto", cpu="full", pmc_key=None, dump=False):
+    """Factor + solve of one system, timed as the contract says (barrier + synchronize on both sides, MAX over the ranks);
+    with --full (and, short of the roofline and the CPU baselines, with --quick) also the two-call split, the residual, the
+    roofline of the dominant kernel family (HIP events on the factor's own streams) and the CPU baselines beside it.
     mode: 'single' (this rank alone), 'replicas' (every rank its own copy), 'subtree' (ONE system over the ranks).
+    dump: res["_outputs"] = what the last timed step computed, fetched before anything else runs on the factor.
     Returns the result dict on every rank (CPU legs on rank 0 only)."""
     from kvxopt_amd import workloads
     from kvxopt_amd.chol import Factor
@@ -589,9 +621,16 @@ def measure_system(args, pl, dist, rank, world, dev, wl, nrhs, steps, warmup, mo
     if collective:
         dt = dist.max(dt)
     ms_factor, ms_solve = F.timing()
+    outputs = None
+    if dump:
+        xo = pl.to_host(x_d, n * nrhs)
+        outputs = {"x": xo if nrhs == 1 else xo.reshape(n, nrhs, order="F")}
+        if DF is None:                                       # (a sharded factor has no whole diagonal on one rank)
+            outputs["factor_diag"] = F.diag()
+    more = args.full or args.quick
     ms_sep = None
     heavy = info["flops"] > 2e13                             # (the 200^3 cube: seconds per step -- no split, one reading of one family)
-    if DF is None and not args.separate_calls and not heavy:
+    if more and DF is None and not args.separate_calls and not heavy:
         # the one-enqueue step cannot tell its two parts apart: a few steps as two calls (factorize, then solve) for the split
         acc = [0.0, 0.0]
         for it in range(8):                                  # (three to capture and warm the two graphs of this form, five measured)
@@ -606,9 +645,11 @@ def measure_system(args, pl, dist, rank, world, dev, wl, nrhs, steps, warmup, mo
     coll = (DF.collectives, DF.bytes_moved) if DF is not None else (0, 0)   # (counted up to here: warm-up + timed steps)
 
     # residual of the last solve (parity bar: <= 1e-10 relative)
-    x = pl.to_host(x_d, n * nrhs)
-    r = workloads.sym_matvec(n, colptr, rowind, values, x.reshape(n, nrhs, order="F")) - b_host.reshape(n, nrhs, order="F")
-    relres = float(np.linalg.norm(r) / np.linalg.norm(b_host))
+    x, relres = None, None
+    if more:
+        x = pl.to_host(x_d, n * nrhs)
+        r = workloads.sym_matvec(n, colptr, rowind, values, x.reshape(n, nrhs, order="F")) - b_host.reshape(n, nrhs, order="F")
+        relres = float(np.linalg.norm(r) / np.linalg.norm(b_host))
     nsys = world if mode == "replicas" else 1
     res = {"workload": wname, "n": int(n), "nrhs": nrhs, "value": work * steps * nsys / dt / 1e9, "unit": "GF/s", "ms_per_step": dt / steps * 1e3,
            "ms_factor": ms_factor, "ms_solve": ms_solve, "as_two_calls": ms_sep, "rel_residual": relres, "steps": steps, "warmup": warmup,
@@ -617,12 +658,12 @@ def measure_system(args, pl, dist, rank, world, dev, wl, nrhs, steps, warmup, mo
                          "ms_factor is the whole call and ms_solve 0 -- the two parts are not separable (see as_two_calls)"),
            "nnz_lower": int(len(values)), "lnz": int(info["lnz"]), "flops_sum_cj2": info["flops"], "nsuper": int(info["nsuper"]),
            "nlevels": int(info["nlevels"]), "max_front": int(info["max_front"]), "lsize": int(info["lsize"]), "analyze_s": round(t_analyze, 3),
-           "dev_bytes_rank0": int(F.info()["dev_bytes"]), "_work": work, "_dt": dt, "_x": x, "_F": F, "_DF": DF}
+           "dev_bytes_rank0": int(F.info()["dev_bytes"]), "_work": work, "_dt": dt, "_x": x, "_F": F, "_DF": DF, "_outputs": outputs}
     if DF is not None:
         res["sharding"] = {"shared_fronts_rank0": DF.nshared, "block_cyclic_rank0": DF.ncyclic, "block_columns": DF.ob,
                            "collectives_per_step_rank0": coll[0] // max(steps_run, 1), "mb_moved_per_step_rank0": coll[1] / max(steps_run, 1) / 1e6,
                            "panel_doubles_rank0": DF.lsize_local, "panel_doubles_total": DF.lsize_total}
-    if args.quick:
+    if args.quick or not args.full:
         return res
 
     # --- roofline leg: dominant kernel family timed live with HIP events on the factor's stream (hipGraph replay is off for
@@ -841,7 +882,10 @@ def main():
     wl = build_workload(args.workload, g)
     headline_cfg2 = args.workload == "lap2d" and g == 1000 and args.nrhs == 1
     res = measure_system(args, pl, dist, rank, world, dev, wl, args.nrhs, args.steps, args.warmup, mode,
-                         pmc_key=("config2" if headline_cfg2 and mode == "single" else None))
+                         pmc_key=("config2" if headline_cfg2 and mode == "single" else None), dump=bool(args.dump_outputs) and rank == 0)
+    if res["_outputs"] is not None:
+        dump_outputs(args.dump_outputs, res["_outputs"])
+        res["_outputs"] = None
     if args.quick:
         if rank == 0:
             print(json.dumps(dict(public(res), opts=args.chol_opts, n_gpus=world)))
@@ -862,14 +906,14 @@ def main():
     # --- BASELINE configs[2] (kvxopt.klu), rank 0 only.  Before the `extra` systems: klu.linsolve is a 1 ms call bound by host
     # latency, and right after the 170 GB factor of the 200^3 system the same call measured 1.04 ms against 0.91 here
     klu = None
-    if rank == 0 and world == 1 and not args.no_klu and headline_cfg2:
+    if args.full and rank == 0 and world == 1 and not args.no_klu and headline_cfg2:
         try:
             klu = klu_leg(args)
         except Exception as e:
             klu = {"error": repr(e)}
 
-    extra = []
-    if not args.no_extra and headline_cfg2:
+    extra = [] if args.full else None
+    if args.full and not args.no_extra and headline_cfg2:
         systems = [("stencil21", 1000, 5, 2), ("lap3d", 100, 3, 1)]
         if world == 1 and not args.no_config5:
             # BASELINE configs[4] on ONE GPU: the N = 1 anchor of the 8-GPU configuration (n = 8e6; no CPU run: the restated CPU path
@@ -895,7 +939,7 @@ def main():
     # (inequality form), rank 0 only, a few hundred ms; never part of `value`
     ipm = None
     one_shot = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_ipm:
             try:
                 ipm = ipm_leg(args, pl)
@@ -931,8 +975,8 @@ def main():
                        "analyze_s": res["analyze_s"], "parallelism": par},
             "ms_factor": res["ms_factor"], "ms_solve": res["ms_solve"], "as_two_calls": res.get("as_two_calls"), "step_form": res["step_form"],
             "rel_residual": res["rel_residual"],
-            "roofline": res["roofline"], "cpu_baseline": cpu, "ranks": ranks, "sharding": res.get("sharding"),
-            "extra": extra, "ipm": ipm, "klu": klu, "one_shot": one_shot,
+            "roofline": res.get("roofline"), "cpu_baseline": cpu, "ranks": ranks, "sharding": res.get("sharding"),
+            "extra": extra, "ipm": ipm, "klu": klu, "one_shot": one_shot, "full": args.full,
         }
         print(json.dumps(out))
         sys.stdout.flush()

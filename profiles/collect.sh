@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the judged profile artefacts on the GPU box (run through gpurun from the repo root):
 #   bash profiles/collect.sh r04
-# 1. bench.py JSON line (the whole default run), 2. rocprofv3 --kernel-trace --stats of the same command without its CPU legs,
+# 1. bench.py JSON line (the whole --full run), 2. rocprofv3 --kernel-trace --stats of the same command without its CPU legs,
 # 3./4. two separate --pmc passes (FETCH_SIZE, WRITE_SIZE: the TCC block cannot hold both, MI355X_MICROARCH.md) of the headline
 # system and of the 21-point system, 5. the same two counters on a kernel of known byte count in the library's own access pattern
 # (profiles/calibrate_fetch.py).  Summaries land in gpurun_out/<tag>_*; profiles/summarize.py turns them into the small files
@@ -13,9 +13,9 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $ROOT
 LEAN="--no-cpu-baseline --no-ipm --no-klu --no-extra --no-one-shot"
-timeout -k 10 900 python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout -k 10 900 python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 tail -c 400 $OUT/${TAG}_bench.json; echo
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o s --output-format csv -- python3 bench.py --steps 10 --warmup 2 $LEAN > $OUT/${TAG}_stats.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o s --output-format csv -- python3 bench.py --steps 10 --warmup 2 --full $LEAN > $OUT/${TAG}_stats.log 2>&1
 echo "stats done"
 for W in lap2d stencil21; do
   timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE -d $OUT/${TAG}_pmc_fetch_$W -o p --output-format csv -- python3 bench.py --steps 2 --warmup 1 --quick --workload $W > $OUT/${TAG}_pmc_fetch_$W.log 2>&1

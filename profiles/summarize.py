@@ -50,7 +50,7 @@ if st:
     rows = list(csv.DictReader(open(st[0])))
     nfac = sum(int(r["Calls"]) for r in rows if clean(r["Name"]).startswith(("k_clear_factor", "k_init_factor")))
     with open(os.path.join(prof, tag + "_kernel_stats.csv"), "w") as f:
-        f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-ipm --no-klu --no-extra --no-one-shot\n")
+        f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-ipm --no-klu --no-extra --no-one-shot\n")
         f.write("# %d numeric factorisations in the process: 12 one-enqueue steps (factor + solve, forward sweep beside the top of the tree), 8 steps as two calls, "
                 "24 in the per-family timing loop (graphs off)\n" % nfac)
         f.write("kernel,calls,total_us,avg_us,pct\n")

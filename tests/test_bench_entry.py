@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,7 +57,7 @@ def test_parent_of_the_ranks_does_not_import_torch():
 def test_two_rank_bench_line_shards_one_system():
     """`bench.py --gpus 2` on the one GPU of the box (gloo instead of RCCL -- RCCL refuses two ranks on one device): the line says
     n_gpus 2, strong scaling, names the backend and the per-rank device bytes, and the sharded result meets the residual bar."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--grid", "300", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--grid", "300", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--full"],
                        env=_clean_env(KVX_DIST_BACKEND="gloo"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -71,9 +72,9 @@ def test_two_rank_bench_line_shards_one_system():
 
 @pytest.mark.gpu
 def test_one_gpu_line_carries_extra_one_shot_and_baselines():
-    """The default N = 1 line at a reduced grid: roofline, cpu_baseline with the cores used / available, ranks; the `extra`
-    and `one_shot` legs are tied to the full-size headline and are exercised by the driver's own bench run."""
-    r = subprocess.run([sys.executable, BENCH, "--grid", "200", "--steps", "3", "--warmup", "1", "--no-ipm", "--no-splu"],
+    """The --full N = 1 line at a reduced grid: roofline, cpu_baseline with the cores used / available, ranks; the `extra`
+    and `one_shot` legs are tied to the full-size headline and are exercised by a full-size `bench.py --full` run."""
+    r = subprocess.run([sys.executable, BENCH, "--grid", "200", "--steps", "3", "--warmup", "1", "--no-ipm", "--no-splu", "--full"],
                        env=_clean_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -81,3 +82,43 @@ def test_one_gpu_line_carries_extra_one_shot_and_baselines():
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] <= cb["cores_available"] and cb["by_threads"]
     assert d["roofline"]["bound"] in ("hbm", "mfma") and "timing_mode" in d["roofline"]
+
+
+def test_dump_outputs_stays_within_64_mb_and_samples_the_same_entries(tmp_path):
+    """--dump-outputs writes float64 files of at most 64 MB in all; an array larger than its share becomes a sample at positions
+    that depend on its size only, so two runs with the same arguments write the same files."""
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "import numpy as np, bench\n"
+            "for d in sys.argv[1:]:\n"
+            "    bench.dump_outputs(d, {'x': np.arange(10 ** 7, dtype=np.float32), 'factor_diag': np.ones((5, 3))})\n" % ROOT)
+    r = subprocess.run([sys.executable, "-c", code, str(tmp_path / "a"), str(tmp_path / "b")], env=_clean_env(), capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 * 10 ** 6
+    x = np.load(tmp_path / "a" / "x.npy")
+    assert x.dtype == np.float64 and 0 < x.size < 10 ** 7
+    assert np.all(np.diff(x) > 0) and x[0] >= 0 and x[-1] < 10 ** 7 and np.array_equal(x, np.round(x))     # entries of the array, in order
+    assert np.array_equal(x, np.load(tmp_path / "b" / "x.npy"))
+    fd = np.load(tmp_path / "a" / "factor_diag.npy")
+    assert fd.dtype == np.float64 and fd.shape == (5, 3) and np.all(fd == 1.0)
+
+
+@pytest.mark.gpu
+def test_plain_line_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times its steps and prints the line with every leg beside the headline null; --dump-outputs holds
+    the solution and the factor's diagonal of the last timed step, and that solution solves the benchmark's system."""
+    r = subprocess.run([sys.executable, BENCH, "--grid", "200", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       env=_clean_env(), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "sparse Cholesky factor+solve GF/s" and d["unit"] == "GF/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+    assert all(d[k] is None for k in ("as_two_calls", "rel_residual", "roofline", "cpu_baseline", "extra", "ipm", "klu", "one_shot"))
+    from kvxopt_amd import workloads
+    n, cp, ri, vx = workloads.laplacian_2d(200)
+    x, diag = np.load(tmp_path / "x.npy"), np.load(tmp_path / "factor_diag.npy")
+    assert x.dtype == np.float64 and x.shape == (n,) and diag.shape == (n,) and np.all(diag > 0)
+    b = np.random.default_rng(2).standard_normal(n)
+    assert np.linalg.norm(workloads.sym_matvec(n, cp, ri, vx, x) - b) / np.linalg.norm(b) < 1e-10
