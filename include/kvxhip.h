@@ -171,6 +171,19 @@ int kvx_chol_last_fused_path(kvx_chol *F);
  * prof_read returns the summed kernel time and launch count since the last select. */
 int kvx_chol_prof_select(kvx_chol *F, int family);
 int kvx_chol_prof_read(kvx_chol *F, double *total_ms, int64_t *launches);
+/* Diagnostics of the trailing update of the big fronts' pivot chain (no device needed).
+ * kvx_dbg_tile_cover: the workgroup numbering of ONE launch over the fronts (orders hm, pivot counts hk, in list order) with the
+ * panel columns [kb, kb + klen) and col_lim (uonly = 1: a deferred "far" update from column col_lim on), walked on the host
+ * through the decode and the tile guard the kernels run.  counts[(f * tmax + ti) * tmax + tj] (count * tmax * tmax entries) =
+ * workgroups that take tile (ti, tj) of front f; info (70 entries): ncls, workgroups, tiles accepted by the guard, strays
+ * (accepted outside the counts array), first[17] (info + 4), T[16] (+ 21), TC[16] (+ 37), wg[17] (+ 53).  0 = done, 1 = bad args.
+ * kvx_dbg_syrk_counts: trailing-update launches enqueued by this process, per kernel / schedule (out may be NULL; reset = 1
+ * zeroes them); returns the number of counters.  Order: k_syrk_trailing<64> by classes, <64> grid, <128> by classes, <128> grid,
+ * k_syrk_lds (chain), k_syrk_lds far, far launches walking their tiles (KVX_FAR_WGS), k_syrk_trailing128 one panel, two-level
+ * outer update, far updates on a stream of their own.  A graph replay enqueues nothing and is not counted. */
+int kvx_dbg_tile_cover(int uonly, const int32_t *hm, const int32_t *hk, int count, int kb, int klen, int col_lim, int tmax,
+                       int32_t *counts, int64_t *info);
+int kvx_dbg_syrk_counts(int64_t *out, int reset);
 /* ---- sharded mode: ONE system factored and solved by nranks processes, one GPU each ----------------------------
  * (the reference is single-process: the calls this stands in for are cholmod_l_factorize / cholmod_l_solve,
  * src/C/cholmod.c:362-364, 483.)  Every rank analyses the same matrix (the analysis is deterministic) and computes the

@@ -684,6 +684,7 @@ int enqueue_factor_body(kvx_chol *F, int lfrom, int lto, bool prologue, bool epi
                                 HIPCHK(hipEventRecord(F->ev_u[(size_t)(2 * b)], st));
                                 HIPCHK(hipStreamWaitEvent(su, F->ev_u[(size_t)(2 * b)], 0));
                                 forked = true;
+                                syrk_count(SYRK_FAR_SIDE);
                             }
                             {
                                 ProfScope ps(F, FAM_SYRK, su);

@@ -226,6 +226,22 @@ void launch_syrk_outer(hipStream_t st, const DevSym &ds, const int32_t *list, in
 void launch_syrk_pair(hipStream_t st, const DevSym &ds, const int32_t *list, int count, int max_m, int jb,
                       double *Lx, double *Uout, double *Linv, int *status, int col_lim = 0x7fffffff);
 
+// Host-side count of the trailing-update launches enqueued, by kernel / schedule (process-wide; kvx_dbg_syrk_counts reads them).
+// A graph replay enqueues nothing and counts nothing.
+enum SyrkVariant {
+    SYRK_T64_CLS,        // k_syrk_trailing<64>, numbered over size classes
+    SYRK_T64_GRID,       // k_syrk_trailing<64>, (tiles) x (tiles or tile columns) x (fronts) grid (KVX_SYRK_DIRECT=1)
+    SYRK_T128_CLS,       // k_syrk_trailing<128> (two panels), size classes
+    SYRK_T128_GRID,      // k_syrk_trailing<128>, grid (KVX_SYRK_DIRECT=1)
+    SYRK_LDS,            // k_syrk_lds<false>: chain step with LDS-staged tiles
+    SYRK_LDS_FAR,        // k_syrk_lds<true>: deferred ("far") update
+    SYRK_LDS_FAR_STRIDE, // ... of those, launches of fewer workgroups than tiles (KVX_FAR_WGS: grid-stride loop)
+    SYRK_T128_PANEL,     // k_syrk_trailing128 with one panel (KVX_SYRK_DIRECT=1, KVX_SYRK128_TILES)
+    SYRK_OUTER,          // k_syrk_trailing128 as the outer update of the two-level blocking
+    SYRK_FAR_SIDE,       // far updates enqueued on a stream of their own (KVX_U_STREAM)
+    SYRK_NVAR
+};
+void syrk_count(SyrkVariant v);
 // sharded mode: rank-ob_len update with the panel [ob, ob + ob_len) of the columns in [c_from, c_to) that rank own_r owns
 void launch_syrk_outer_dist(hipStream_t st, const DevSym &ds, const int32_t *list, int max_m, int ob, int ob_len,
                             int own_ob, int own_g, int own_r, int c_from, int c_to, double *Lx, double *Uout);

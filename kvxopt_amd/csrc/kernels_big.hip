@@ -16,8 +16,10 @@
 //
 // Reference role: cholmod_l_factorize / cholmod_l_solve (src/C/cholmod.c:362, 483).
 #include "device.hpp"
+#include "tile_classes.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cstdint>
 #include <cstdlib>
@@ -520,45 +522,6 @@ void launch_trsm_blk(hipStream_t st, const DevSym &ds, const int32_t *list, int 
     hipLaunchKernelGGL(k_trsm_blk, grid, dim3(256), 0, st, ds, list, jb, Lx, Linv);
 }
 
-// Numbering of the workgroups of a trailing-update launch over size classes of fronts (TileClasses, device.hpp; the host side
-// is make_tile_classes below): workgroup id -> front index in the launch's list and tile (ti, tj).  false: nothing to do.
-__device__ __forceinline__ void tri_inv(unsigned L, int &ti, int &tj)
-{
-    unsigned si = (unsigned)((__builtin_sqrtf(8.0f * (float)L + 1.0f) - 1.0f) * 0.5f);
-    while ((si + 1) * (si + 2) / 2 <= L) si++;
-    while (si * (si + 1) / 2 > L) si--;
-    ti = (int)si;
-    tj = (int)(L - si * (si + 1) / 2);
-}
-__device__ __forceinline__ bool cls_decode(const TileClasses &tc, const unsigned wgid, int &fi, int &ti, int &tj)
-{
-    int c = 0;
-    while (c + 1 < tc.ncls && wgid >= tc.wg[c + 1]) c++;                   // (uniform)
-    const unsigned local = wgid - tc.wg[c];
-    const int T = tc.T[c], TC = tc.TC[c];
-    if (TC > 0) {                                      // a few tile columns of T tile rows (column-limited launches)
-        const unsigned tpf = (unsigned)T * (unsigned)TC;
-        const unsigned t = local % tpf;
-        fi = tc.first[c] + (int)(local / tpf);
-        ti = (int)(t % (unsigned)T);
-        tj = (int)(t / (unsigned)T);
-    } else {
-        const unsigned tri = (unsigned)T * (unsigned)(T + 1) / 2;
-        if (T >= 16) {
-            const unsigned chunk = (tri + 7) / 8, tpf = 8 * chunk;
-            const unsigned t = local % tpf;
-            fi = tc.first[c] + (int)(local / tpf);
-            const unsigned L = (t & 7u) * chunk + (t >> 3);
-            if (L >= tri) return false;
-            tri_inv(L, ti, tj);
-        } else {
-            fi = tc.first[c] + (int)(local / tri);
-            tri_inv(local % tri, ti, tj);
-        }
-    }
-    return tj <= ti && fi < tc.first[tc.ncls];         // (ids in the padding in front of an XCD-numbered class)
-}
-
 // ------------------------------------------------------------------------------------------
 // Trailing update C -= X X' on 64x64 tiles (FP64 MFMA).  The trailing matrix spans the rest of
 // the panel (columns < k, ld = m, in Lx) and the update matrix (columns >= k, ld = u).
@@ -590,13 +553,9 @@ __global__ __launch_bounds__(256) void k_syrk_trailing(DevSym ds, const int32_t 
     KVX_STAMP(q0);
     const FrontDesc fd = ds.fd[list[fi]];
     const int k = fd.k, m = fd.m, u = m - k;
-    if (jb >= k) return;
-    const int nbk = min(KW, k - jb);
-    const int t0 = jb + nbk;
-    const int r0 = t0 + KVX_TILE * ti, c0 = t0 + KVX_TILE * tj;
-    if (r0 >= m) return;
-    const int cend = col_lim == INT_MAX ? m : min(col_lim, k);
-    if (c0 >= cend) return;
+    SyrkTile g;
+    if (!syrk_tile_guard(false, m, k, jb, KW, col_lim, ti, tj, g)) return;
+    const int nbk = g.nbk, t0 = g.t0, r0 = g.r0, c0 = g.c0, cend = g.cend;
     double *P = Lx + fd.px;
     double *U = Uo + fd.ux;
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63, lr = l & 15, lk = l >> 4;
@@ -736,22 +695,6 @@ struct SyrkLdsOnly {
     struct { double S[1]; } po;      // (never used)
 };
 
-// Numbering of the workgroups of one launch (TileClasses, device.hpp).  A launch updates every big front of a level that is still
-// in the chain; their trailing matrices differ by an order of magnitude, and a (tiles of the largest front) x (fronts) grid is
-// mostly workgroups that find nothing to do -- the dispatcher starts one per ~2.6 ns, and the bottom levels of the 21-point
-// system launched 870 000 of them per step for 30 000 tiles of work (2.3 ms, measured).  The host therefore hands the kernel
-// the fronts sorted by size and cut into classes of similar tile counts; a class is a (tiles of ITS largest front) x (its
-// fronts) block of consecutive workgroup ids.
-// tile t of a front -> (ti, tj).  Triangular classes of 16 or more tile rows: the 8 XCDs (workgroup ids go round-robin over them,
-// each has its own L2) take contiguous eighths of the row-major tile order, so that the workgroups resident on one XCD work on
-// neighbouring tiles of a few tile rows and share their operand strips.
-static inline unsigned cls_tiles_per_front(int T, int TC)
-{
-    if (TC > 0) return (unsigned)T * (unsigned)TC;
-    const unsigned tri = (unsigned)T * (unsigned)(T + 1) / 2;
-    return T >= 16 ? ((tri + 7) / 8) * 8 : tri;
-}
-
 template <bool UONLY, class Lds>
 __device__ __forceinline__ void syrk_lds_tile(Lds &lds, const unsigned wgid, const DevSym &ds, const int32_t *__restrict__ list, int kb, int klen,
                                               double *__restrict__ Lx, double *__restrict__ Uo,
@@ -761,13 +704,9 @@ __device__ __forceinline__ void syrk_lds_tile(Lds &lds, const unsigned wgid, con
     if (!cls_decode(tc, wgid, fi, ti, tj)) return;
     const FrontDesc fd = ds.fd[list[fi]];
     const int k = fd.k, m = fd.m, u = m - k;
-    if (kb >= k) return;
-    const int nbk = min(klen, k - kb);
-    const int t0 = UONLY ? min(col_lim, k) : kb + nbk;
-    const int r0 = t0 + KVX_TILE * ti, c0 = t0 + KVX_TILE * tj;
-    if (r0 >= m) return;
-    const int cend = (UONLY || col_lim == INT_MAX) ? m : min(col_lim, k);
-    if (c0 >= cend) return;
+    SyrkTile g;
+    if (!syrk_tile_guard(UONLY, m, k, kb, klen, col_lim, ti, tj, g)) return;
+    const int nbk = g.nbk, t0 = g.t0, r0 = g.r0, c0 = g.c0, cend = g.cend;
     double *P = Lx + fd.px;
     double *U = Uo + fd.ux;
     const int tid = threadIdx.x;
@@ -879,51 +818,6 @@ __global__ __launch_bounds__(256, 2) void k_syrk_lds(DevSym ds, const int32_t *_
     }
 }
 
-// Size classes of a launch.  hm / hk: order and pivot columns of the fronts in list order (host copies; the list is sorted by the
-// order of the update region, largest first, so classes are runs of the list).  A class ends where the tile count of the next
-// front falls below ~0.7 of the class's largest, or rises above it.
-static TileClasses make_tile_classes(bool uonly, const int32_t *hm, const int32_t *hk, int count, int kb, int klen, int col_lim)
-{
-    TileClasses tc;
-    int c = -1;
-    for (int i = 0; i < count; i++) {
-        const int m = hm[i], k = hk[i];
-        int R = 0, C = 0;
-        if (kb < k) {
-            const int t0 = uonly ? std::min(col_lim, k) : kb + std::min(klen, k - kb);
-            const int cend = (uonly || col_lim == INT_MAX) ? m : std::min(col_lim, k);
-            R = std::max(m - t0, 0);
-            C = std::max(cend - t0, 0);
-        }
-        const int T = (R + KVX_TILE - 1) / KVX_TILE, TCf = (C + KVX_TILE - 1) / KVX_TILE;
-        if (c == KVX_MAXCLS - 1) {                     // out of classes: the last one takes the rest, whatever its sizes
-            tc.T[c] = std::max(tc.T[c], T);
-            tc.TC[c] = std::max(tc.TC[c], TCf);
-            continue;
-        }
-        if (c >= 0 && T <= tc.T[c] && T * 10 >= tc.T[c] * 7) {
-            tc.TC[c] = std::max(tc.TC[c], TCf);
-            continue;
-        }
-        c++;
-        tc.first[c] = i;
-        tc.T[c] = T;
-        tc.TC[c] = TCf;
-    }
-    tc.ncls = c + 1;
-    tc.wg[0] = 0;
-    tc.first[tc.ncls] = count;
-    for (int q = 0; q < tc.ncls; q++) {
-        const int T = tc.T[q];
-        if (tc.TC[q] * 2 >= T) tc.TC[q] = 0;           // rectangular numbering only where it saves at least half of the workgroups
-        unsigned w0 = tc.wg[q];
-        if (tc.TC[q] == 0 && T >= 16) w0 = (w0 + 7u) & ~7u;                   // XCD numbering: the class starts on XCD 0
-        tc.wg[q] = w0;
-        tc.wg[q + 1] = w0 + (T > 0 ? cls_tiles_per_front(T, tc.TC[q]) : 0u) * (unsigned)(tc.first[q + 1] - tc.first[q]);
-    }
-    return tc;
-}
-
 static void launch_syrk_lds_cls(hipStream_t st, bool uonly, const DevSym &ds, const int32_t *list, const TileClasses &tc, int kb, int klen,
                                 double *Lx, double *Uout, double *Linv, int *status, int col_lim)
 {
@@ -932,10 +826,14 @@ static void launch_syrk_lds_cls(hipStream_t st, bool uonly, const DevSym &ds, co
     if (gx == 0) return;
     // KVX_FAR_WGS > 0: a far launch as that many resident workgroups walking the tiles (measured: no gain, see k_syrk_lds)
     static const unsigned far_wgs = [] { const char *e = getenv("KVX_FAR_WGS"); return e ? (unsigned)atoi(e) : 0u; }();
-    if (uonly)
+    if (uonly) {
+        syrk_count(SYRK_LDS_FAR);
+        if (far_wgs && far_wgs < gx) syrk_count(SYRK_LDS_FAR_STRIDE);
         hipLaunchKernelGGL(k_syrk_lds<true>, dim3(far_wgs ? std::min(gx, far_wgs) : gx), dim3(256), 0, st, ds, list, kb, klen, Lx, Uout, Linv, status, col_lim, tc);
-    else
+    } else {
+        syrk_count(SYRK_LDS);
         hipLaunchKernelGGL(k_syrk_lds<false>, dim3(gx), dim3(256), 0, st, ds, list, kb, klen, Lx, Uout, Linv, status, col_lim, tc);
+    }
 }
 
 // without size information: one class, every front gets the tiles of an update region of order `rows`
@@ -968,12 +866,60 @@ void launch_syrk_step(hipStream_t st, const DevSym &ds, const int32_t *list, con
     const unsigned gx = tc.ncls > 0 ? tc.wg[tc.ncls] : 0u;
     if (gx == 0) return;
     if (gx < lds_tiles && klen <= 2 * NB) {
-        if (klen <= NB) hipLaunchKernelGGL(k_syrk_trailing<64>, dim3(gx), dim3(256), 0, st, ds, list, kb, Lx, Uout, Linv, status, col_lim, tc);
-        else hipLaunchKernelGGL(k_syrk_trailing<128>, dim3(gx), dim3(256), 0, st, ds, list, kb, Lx, Uout, Linv, status, col_lim, tc);
+        if (klen <= NB) {
+            syrk_count(SYRK_T64_CLS);
+            hipLaunchKernelGGL(k_syrk_trailing<64>, dim3(gx), dim3(256), 0, st, ds, list, kb, Lx, Uout, Linv, status, col_lim, tc);
+        } else {
+            syrk_count(SYRK_T128_CLS);
+            hipLaunchKernelGGL(k_syrk_trailing<128>, dim3(gx), dim3(256), 0, st, ds, list, kb, Lx, Uout, Linv, status, col_lim, tc);
+        }
         return;
     }
     launch_syrk_lds_cls(st, false, ds, list, tc, kb, klen, Lx, Uout, Linv, status, col_lim);
 }
+static std::atomic<unsigned long long> g_syrk_counts[SYRK_NVAR];
+void syrk_count(SyrkVariant v) { g_syrk_counts[v].fetch_add(1, std::memory_order_relaxed); }
+
+}  // namespace kvx
+
+extern "C" int kvx_dbg_syrk_counts(int64_t *out, int reset)
+{
+    for (int v = 0; v < kvx::SYRK_NVAR; v++) {
+        const unsigned long long c = reset ? kvx::g_syrk_counts[v].exchange(0) : kvx::g_syrk_counts[v].load();
+        if (out) out[v] = (int64_t)c;
+    }
+    return kvx::SYRK_NVAR;
+}
+
+extern "C" int kvx_dbg_tile_cover(int uonly, const int32_t *hm, const int32_t *hk, int count, int kb, int klen, int col_lim, int tmax,
+                                  int32_t *counts, int64_t *info)
+{
+    using namespace kvx;
+    if (count < 0 || count > (1 << 20) || tmax <= 0 || (count > 0 && (!hm || !hk)) || !counts || !info) return 1;
+    std::fill(counts, counts + (size_t)count * tmax * tmax, 0);
+    std::fill(info, info + 70, (int64_t)0);
+    if (count == 0) return 0;
+    const TileClasses tc = make_tile_classes(uonly != 0, hm, hk, count, kb, klen, col_lim);
+    const unsigned total = tc.wg[tc.ncls];
+    int64_t accepted = 0, stray = 0;
+    for (unsigned wgid = 0; wgid < total; wgid++) {
+        int fi, ti, tj;
+        if (!cls_decode(tc, wgid, fi, ti, tj)) continue;
+        if (fi < 0 || fi >= count) { stray++; continue; }
+        SyrkTile g;
+        if (!syrk_tile_guard(uonly != 0, hm[fi], hk[fi], kb, klen, col_lim, ti, tj, g)) continue;
+        accepted++;
+        if (ti < 0 || tj < 0 || ti >= tmax || tj >= tmax) { stray++; continue; }
+        counts[((size_t)fi * tmax + ti) * tmax + tj]++;
+    }
+    info[0] = tc.ncls; info[1] = total; info[2] = accepted; info[3] = stray;
+    for (int q = 0; q <= tc.ncls; q++) { info[4 + q] = tc.first[q]; info[53 + q] = tc.wg[q]; }
+    for (int q = 0; q < tc.ncls; q++) { info[21 + q] = tc.T[q]; info[37 + q] = tc.TC[q]; }
+    return 0;
+}
+
+namespace kvx {
+
 // deferred ("far") update with the panel block [kb, kb + klen): everything from column t0 on -- later pivot columns and the
 // update matrix; t0 >= k: the update matrix alone -- for the fronts of the list
 void launch_syrk_far(hipStream_t st, const DevSym &ds, const int32_t *list, const int32_t *hm, const int32_t *hk, int count, int kb, int klen,
@@ -1198,8 +1144,10 @@ void launch_syrk_trailing(hipStream_t st, const DevSym &ds, const int32_t *list,
     const char *e = getenv("KVX_SYRK128_TILES");
     const int64_t big_limit = e ? atoll(e) : INT64_MAX;
     if (T * (T + 1) / 2 * count >= big_limit) {
+        syrk_count(SYRK_T128_PANEL);
         hipLaunchKernelGGL(k_syrk_trailing128<false>, syrk128_grid(rows, count), dim3(512), 0, st, ds, list, jb, NB, Lx, Uout, Linv, status, ColOwner{1, 1, 0, 0, INT_MAX, 0});
     } else {                                          // latency regime: more, smaller workgroups
+        syrk_count(SYRK_T64_GRID);
         hipLaunchKernelGGL(k_syrk_trailing<64>, dim3((unsigned)T, (unsigned)T, (unsigned)count), dim3(256), 0, st, ds, list, jb, Lx, Uout, Linv, status, col_lim, no_classes());
     }
 }
@@ -1214,6 +1162,7 @@ void launch_syrk_pair(hipStream_t st, const DevSym &ds, const int32_t *list, int
     if (rows <= 0) return;
     if (!syrk_direct()) { launch_syrk_lds(st, false, ds, list, count, rows, jb, 2 * NB, Lx, Uout, Linv, status, col_lim); return; }
     const unsigned T = (unsigned)((rows + KVX_TILE - 1) / KVX_TILE);
+    syrk_count(SYRK_T128_GRID);
     hipLaunchKernelGGL(k_syrk_trailing<128>, dim3(T, T, (unsigned)count), dim3(256), 0, st, ds, list, jb, Lx, Uout, Linv, status, col_lim, no_classes());
 }
 
@@ -1231,6 +1180,7 @@ void launch_syrk_inner(hipStream_t st, const DevSym &ds, const int32_t *list, in
     if (!syrk_direct()) { launch_syrk_lds(st, false, ds, list, count, rows, jb, NB, Lx, Uout, Linv, status, ob_end); return; }
     const unsigned T = (unsigned)((rows + KVX_TILE - 1) / KVX_TILE);
     const unsigned TC = (unsigned)std::min<int>((int)T, (ob_end - jb - NB + KVX_TILE - 1) / KVX_TILE);
+    syrk_count(SYRK_T64_GRID);
     hipLaunchKernelGGL(k_syrk_trailing<64>, dim3(T, TC, (unsigned)count), dim3(256), 0, st, ds, list, jb, Lx, Uout, Linv, status, ob_end, no_classes());
 }
 
@@ -1240,6 +1190,7 @@ void launch_syrk_outer(hipStream_t st, const DevSym &ds, const int32_t *list, in
     if (count <= 0) return;
     int rows = max_m - ob - 1;                        // (an over-estimate of the trailing order: empty tiles exit at once)
     if (rows <= 0) return;
+    syrk_count(SYRK_OUTER);
     hipLaunchKernelGGL(k_syrk_trailing128<false>, syrk128_grid(rows, count), dim3(512), 0, st, ds, list, ob, ob_len, Lx, Uout, Linv, status, ColOwner{1, 1, 0, 0, INT_MAX, 0});
 }
 

@@ -195,25 +195,33 @@ def test_not_posdef_column_in_big_fronts(g, where):
     assert np.linalg.norm(workloads.sym_matvec(n, cp, ri, vx, x) - 1) < 1e-9 * np.sqrt(n)
 
 
-def test_syrk128_variant_parity(monkeypatch):
-    """The opt-in 128 x 128 LDS-staged trailing update (KVX_SYRK128_TILES) gives the same factor and
-    solutions as the oracle, including the diagonal blocks it factors in its (0, 0) workgroup."""
-    import scipy.sparse as sp
-    monkeypatch.setenv("KVX_SYRK128_TILES", "1")
-    monkeypatch.setenv("KVX_NO_GRAPH", "1")
-    M = sp.random(2500, 2500, 0.02, random_state=4, format="csc")
-    S = (M @ M.T + sp.eye(2500) * 5.0).tocsc()
-    L = sp.tril(S).tocsc(); L.sort_indices()
-    parity(2500, L.indptr, L.indices, L.data, seed=4)
-    parity(*workloads.laplacian_2d(150), seed=150)
-    # the two-level blocking of very large fronts, forced on here (per panel only the rest of an outer block of 1024 -- or
-    # KVX_OUTER_BLOCK -- columns, then one rank-1024 update of the trailing matrix)
-    monkeypatch.delenv("KVX_SYRK128_TILES")
-    monkeypatch.setenv("KVX_TWO_LEVEL_M", "0")
-    parity(2500, L.indptr, L.indices, L.data, seed=5)
-    parity(*workloads.laplacian_2d(150), seed=151)
-    monkeypatch.setenv("KVX_OUTER_BLOCK", "256")
-    parity(2500, L.indptr, L.indices, L.data, seed=6)
+def test_syrk128_variant_parity(tmp_path):
+    """The opt-in 128 x 128 LDS-staged trailing update (KVX_SYRK_DIRECT=1 with KVX_SYRK128_TILES: the single-panel launches take
+    it) and the two-level blocking of very large fronts (KVX_DEFER_U=0 with KVX_TWO_LEVEL_M=0: per panel only the rest of an outer
+    block of 1024 -- or KVX_OUTER_BLOCK -- columns, then one rank-1024 update of the trailing matrix by the 128-tile kernel) give
+    the same factor and solutions as the oracle, including the diagonal blocks they factor in their (0, 0) workgroup.  Each
+    setting in a process of its own (the knobs are read once per process, syrk_schedule_child.py); the launch counters prove
+    that the kernel ran."""
+    import syrk_schedule_child as child
+    cache = str(tmp_path)
+    names = ["rand2500", "lap150"]
+    for m in names:
+        child.prepare(m, cache)
+    r = child.run_setting({"KVX_SYRK_DIRECT": 1, "KVX_SYRK128_TILES": 1}, names, cache)
+    for m in names:
+        c = r[m]["counts"]
+        assert c["t128_panel"] > 0 and c["t64_cls"] == 0 and c["lds"] == 0 and c["outer"] == 0, (m, c)
+    outer = []
+    for ob in (None, 256):
+        setting = {"KVX_DEFER_U": 0, "KVX_TWO_LEVEL_M": 0}
+        if ob:
+            setting["KVX_OUTER_BLOCK"] = ob
+        r = child.run_setting(setting, names, cache)
+        for m in names:
+            c = r[m]["counts"]
+            assert c["outer"] > 0 and c["lds_far"] == 0, (m, ob, c)
+        outer.append(child.total(r, "outer"))
+    assert outer[1] > outer[0]                                   # 256-column outer blocks: more outer updates
 
 
 def test_async_factor_then_solve_without_host_round_trip():
