@@ -437,6 +437,28 @@ int kvx_nts_tri_dev(int64_t ns, const int64_t *off2_dev, const int64_t *off1_dev
 int kvx_nts_pack_dev(int64_t ns, const int64_t *off2_dev, const int64_t *off1_dev, const int64_t *offp_dev, double *full_dev,
                      double *packed_dev, int dir);
 
+/* ---- general cones: the KKT system of misc.kkt_chol (misc.py:1213-1349) for 'l' rows, 'q' cones and 's' blocks ----------
+ * S = Gs' Gs with Gs = pack2(W^-T G) (misc.py:1267-1277: scale(Gs, W, 'T', 'I'), pack2, syrk), n x n, on a fixed pattern: the
+ * union of the cliques of columns that touch each 'l' row, 'q' cone and 's' block (lower triangles of the 's' block rows of G
+ * only: the strict upper triangle is ignored as scale and sgemv ignore it, misc.py:801-833).  G: N x n CCS, N = ml + sum q_k +
+ * sum m_k^2, rows in the reference's order ('l', then the 'q' cones, then the 's' blocks stored by columns).  Host only. */
+typedef struct kvx_cone kvx_cone;
+int kvx_cone_plan(int64_t ml, int64_t nq, const int64_t *q, int64_t ns, const int64_t *s, int64_t n, const int64_t *Gp,
+                  const int64_t *Gi, kvx_cone **out);
+/* lower CCS pattern of S (Sp: n + 1, Si: snz; either may be NULL to query snz) */
+int kvx_cone_pattern(kvx_cone *C, int64_t *snz, int64_t *Sp, int64_t *Si);
+/* Sx_dev[snz] := S for the scaling W: di (ml, the 'l' block of W['di']), v (the 'q' vectors W['v'] back to back), beta (nq),
+ * rti (the 's' blocks W['rti'] back to back, m_k^2 each).  'l' rows: di^2 g g'; 'q' cones: (G'G + 4|v|^2 p p' - 2 (p q' + q p'))
+ * / beta^2 with p = G' J v, q = G' v; 's' blocks: the Gram matrix of pack2(rti' G(:, j) rti) over the clique columns j (FP64
+ * MFMA).  Every entry is summed in a fixed order (no floating-point atomics).  Null stream, enqueue only. */
+int kvx_cone_assemble_dev(kvx_cone *C, const double *Gx_dev, const double *di_dev, const double *v_dev, const double *beta_dev,
+                          const double *rti_dev, double *Sx_dev);
+void kvx_cone_free(kvx_cone *C);
+/* helpers of the general-cone driver (coneprog.py:1273-1280, 1379-1431): y[idx[i]] := x[i] (an 's' diagonal placed into its
+ * block), and x_k(i, j) *= sqrt(w_j) for every 's' block (w in the off1 layout of the kvx_nts_* entries) */
+int kvx_vec_scatter_dev(int64_t n, const double *x_dev, const int64_t *idx_dev, double *y_dev);
+int kvx_nts_colscale_dev(int64_t ns, const int64_t *off2_dev, const int64_t *off1_dev, double *x_dev, const double *w_dev);
+
 /* ---- dense helpers of the equality-constrained KKT solve with a general S (misc.py:1476-1487, 1545): K = A S^-1 A' formed
  * as a dense p x p matrix from X = S^-1 A' (kvx_chol_solve_dev with nrhs = p) when p is moderate ------------------------- */
 /* Y(j, c) = sum_i A(i, j) X(i, c) for the CCS matrix A with n columns and every column c < ncols of the dense X */

@@ -199,6 +199,12 @@ _SIGS = {
                                       i64p, ctypes.POINTER(i64p), ctypes.POINTER(i64p), ctypes.POINTER(f64p),
                                       i64p, i64p, f64p, i64p, ctypes.POINTER(i64p)]),
     "kvx_lu_det": (ctypes.c_int, [vp, f64p]),
+    "kvx_cone_plan": (ctypes.c_int, [i64, i64, i64p, i64, i64p, i64, i64p, i64p, ctypes.POINTER(vp)]),
+    "kvx_cone_pattern": (ctypes.c_int, [vp, i64p, i64p, i64p]),
+    "kvx_cone_assemble_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+    "kvx_cone_free": (None, [vp]),
+    "kvx_vec_scatter_dev": (ctypes.c_int, [i64, vp, vp, vp]),
+    "kvx_nts_colscale_dev": (ctypes.c_int, [i64, vp, vp, vp, vp]),
     "kvx_spmm_t_dev": (ctypes.c_int, [i64, i64, vp, vp, vp, vp, i64, vp, i64]),
     "kvx_dense_from_ccs_dev": (ctypes.c_int, [i64, i64, vp, vp, vp, vp, i64]),
     "kvx_pack_lower_dev": (ctypes.c_int, [i64, vp, i64, vp]),

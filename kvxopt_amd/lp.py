@@ -512,6 +512,22 @@ class KKTDiagEqDev:
             z.xmy(1.0, di, self.t, -1.0)
 
 
+def dense_schur(Sfac, AT, X, Kd, Kx, kdiag, n, p, cols):
+    """K = A S^-1 A' as a dense p x p matrix in HBM from the factor of S (misc.py:1476-1487 written with S^-1): X = S^-1 A' in
+    column blocks of `cols` (AT: the CCS of A', n x p), K = A X, its lower triangle packed into Kx, -diag(K) into kdiag.  Returns
+    max diag(K) (one host round trip); the solves with S are only enqueued, a failed factorisation of S surfaces in its status."""
+    for c0 in range(0, p, cols):                                       # column blocks of X = S^-1 A' and of K = A X
+        nb = min(cols, p - c0)
+        raise_for(lib().kvx_dense_from_ccs_dev(n, nb, AT.cp.ptr + 8 * c0, AT.ri.ptr, AT.vx.ptr, X.ptr, n))
+        Sfac.solve_dev(X.ptr, 0, nb, n, sync=False)
+        raise_for(lib().kvx_spmm_t_dev(p, nb, AT.cp.ptr, AT.ri.ptr, AT.vx.ptr, X.ptr, n, Kd.ptr + 8 * c0 * p, p))
+    raise_for(lib().kvx_pack_lower_dev(p, Kd.ptr, p, Kx.ptr))
+    # scale to max diag K = 1 (one host round trip; it also surfaces a failed factorisation of S)
+    raise_for(lib().kvx_vec_copy_strided_dev(p, Kd.ptr, p + 1, kdiag.ptr))
+    kdiag.scal(-1.0)
+    return kdiag.max_step()
+
+
 class KKTGenEqDev:
     """Device-resident `misc.kkt_chol2` with equality constraints and a GENERAL sparse G (S not diagonal), for a moderate
     number p of equality rows.  The reference forms Asct = L^-1 P A' by sparse triangular solves, K = Asct' Asct by a sparse
@@ -581,17 +597,7 @@ class KKTGenEqDev:
     def factor(self, di, sync=True):
         n, p = self.n, self.p
         self.S.factor(di, sync=False)                                  # S = G' W^-1 W^-T G: assembly + numeric refactorisation
-        for c0 in range(0, p, self.cols):                              # column blocks of X = S^-1 A' and of K = A X
-            nb = min(self.cols, p - c0)
-            raise_for(lib().kvx_dense_from_ccs_dev(n, nb, self.AT.cp.ptr + 8 * c0, self.AT.ri.ptr, self.AT.vx.ptr, self.X.ptr, n))
-            self.S.fac.solve_dev(self.X.ptr, 0, nb, n, sync=False)     # (a failed S surfaces in check())
-            raise_for(lib().kvx_spmm_t_dev(p, nb, self.AT.cp.ptr, self.AT.ri.ptr, self.AT.vx.ptr, self.X.ptr, n,
-                                           self.Kd.ptr + 8 * c0 * p, p))
-        raise_for(lib().kvx_pack_lower_dev(p, self.Kd.ptr, p, self.Kx.ptr))
-        # scale to max diag K = 1 (one host round trip; it also surfaces a failed factorisation of S)
-        raise_for(lib().kvx_vec_copy_strided_dev(p, self.Kd.ptr, p + 1, self.kdiag.ptr))
-        self.kdiag.scal(-1.0)
-        kmax = self.kdiag.max_step()
+        kmax = dense_schur(self.S.fac, self.AT, self.X, self.Kd, self.Kx, self.kdiag, n, p, self.cols)
         self.S.check()
         if not (kmax > 0.0) or not np.isfinite(kmax):
             raise ArithmeticError(0)

@@ -650,3 +650,51 @@ def kkt_chol2(G, dims, A, mnl=0):
         return state["dev"].solve
 
     return factor
+
+
+def kkt_chol(G, dims, A, mnl=0):
+    """KKT solver factory of the reference for general cones (misc.py:1213-1349): returns factor(W, H=None, Df=None), which
+    returns solve(x, y, z) overwriting (bx, by, bz) with (ux, uy, W uz) of
+
+        [ 0   A'  G'   ] [ux]   [bx]
+        [ A   0   0    ] [uy] = [by],
+        [ G   0  -W'W  ] [uz]   [bz]
+
+    with S = Gs' Gs, Gs = pack2(W^-T G), assembled on the fixed pattern of the cliques of the 'l' rows, 'q' cones and 's' blocks
+    (kvx_cone_assemble_dev) and factored by the sparse Cholesky on one analysis; p > 0 is eliminated with K = A S^-1 A' (the
+    reference uses a QR factorisation of A' there: the same solution, other roundings).  Host vectors in and out, arithmetic on
+    the device.  The nonlinear block (mnl > 0), H and Df are not part of this path."""
+    from . import cone, lp
+    if mnl:
+        raise NotImplementedError("misc.kkt_chol on the GPU: the nonlinear block (mnl > 0) is not supported")
+    dims = {"l": dims["l"], "q": list(dims.get("q") or []), "s": list(dims.get("s") or [])}
+    D = cone.Dims(dims)
+    _, n, Gp, Gi, Gx = cone._ccs(G)
+    p, _, Ap, Ai, Ax = cone._ccs(A)
+    state = {"kkt": None, "W": None}
+
+    def factor(W, H=None, Df=None):
+        if H is not None or Df is not None:
+            raise NotImplementedError("misc.kkt_chol on the GPU: H and Df (coneqp / cvxprog) are not supported")
+        _lib.require_device()
+        if state["kkt"] is None:
+            state["kkt"] = cone.KKTConeDev(D, n, Gp, Gi, Gx, p, Ap, Ai, Ax)
+            state["W"] = cone.WDev(D)
+            state["x"], state["y"], state["z"] = lp.DVec(n), lp.DVec(p), lp.DVec(D.N)
+        state["W"].set_host(W)
+        state["kkt"].factor(state["W"])
+
+        def solve(x, y, z):
+            xb, yb, zb = _buf(x)[0], _buf(y)[0], _buf(z)[0]
+            X, Y, Z = state["x"], state["y"], state["z"]
+            X.set(xb[:n]); Z.set(zb[:D.N])
+            if p:
+                Y.set(yb[:p])
+            state["kkt"].solve(X, Y, Z)
+            xb[:n] = X.get()
+            zb[:D.N] = Z.get()
+            if p:
+                yb[:p] = Y.get()
+        return solve
+
+    return factor

@@ -1,6 +1,10 @@
-"""`kvxopt.solvers` names for the device-resident interior-point drivers of kvxopt_amd.lp (orthant cone only):
+"""`kvxopt.solvers` names for the device-resident interior-point drivers of kvxopt_amd.lp (orthant cone) and kvxopt_amd.cone
+(second-order and semidefinite cones):
 
-    conelp(c, G, h, dims=None, A=None, b=None, primalstart=None, dualstart=None)     coneprog.py:420
+    conelp(c, G, h, dims=None, A=None, b=None, primalstart=None, dualstart=None)     coneprog.py:420  (-> cone.conelp when dims
+                                                                                     has 'q' or 's' blocks, coneprog.py:459, 504)
+    socp(c, Gl, hl, Gq, hq, A=None, b=None, primalstart=None, dualstart=None)        coneprog.py:3044
+    sdp(c, Gl, hl, Gs, hs, A=None, b=None, primalstart=None, dualstart=None)         coneprog.py:3597
     coneqp(P, q, G, h, dims=None, A=None, b=None, initvals=None)                     coneprog.py:1440
     lp(c, G, h, A=None, b=None, primalstart=None, dualstart=None)                    coneprog.py:2551 (-> conelp)
     qp(P, q, G, h, A=None, b=None, initvals=None)                                    coneprog.py:4120 (-> coneqp)
@@ -12,6 +16,10 @@ take the reference's plug-in, a function `W -> g(x, y, z)` (coneprog.py:323-344,
 and solve, lp.KKTUserHost); the named solvers ('ldl', 'ldl2', 'qr', 'chol', 'chol2') and `solver=` (external codes) are not part of
 this path and raise.
 """
+import numpy as np
+
+from . import base as _base
+from . import cone as _cone
 from . import lp as _lp
 
 options = {}
@@ -38,6 +46,11 @@ def _kkt(kw):
 
 def conelp(c, G, h, dims=None, A=None, b=None, primalstart=None, dualstart=None, **kw):
     k = _kkt(kw)
+    if dims is not None and (dims.get("q") or dims.get("s")):
+        # the reference's own test for the general-cone path (coneprog.py:459, 504): misc.kkt_chol on the GPU
+        if k is not None:
+            raise NotImplementedError("conelp with 'q' / 's' cones runs misc.kkt_chol on the GPU; kktsolver is not selectable")
+        return _cone.conelp(c, G, h, dims, A=A, b=b, options=_opts(kw), primalstart=primalstart, dualstart=dualstart)
     return _lp.conelp(c, G, h, dims=dims, A=A, b=b, options=_opts(kw), primalstart=primalstart, dualstart=dualstart, kktsolver=k)
 
 
@@ -57,3 +70,114 @@ def lp(c, G, h, A=None, b=None, primalstart=None, dualstart=None, **kw):
 def qp(P, q, G, h, A=None, b=None, initvals=None, **kw):
     """solvers.qp (coneprog.py:4120-4330): coneqp on the orthant."""
     return coneqp(P, q, G, h, None, A, b, initvals, **kw)
+
+
+def _stack(blocks, n):
+    """[B_0; B_1; ...] (dense or sparse, each with n columns) as one CCS spmatrix."""
+    rows, cols, vals, off = [], [], [], 0
+    for B in blocks:
+        m, nb, cp, ri, v = _cone._ccs(B)
+        if nb != n:
+            raise TypeError("the constraint matrices must have %d columns" % n)
+        rows.append(np.asarray(ri, dtype=np.int64) + off)
+        cols.append(np.repeat(np.arange(n, dtype=np.int64), np.diff(np.asarray(cp, dtype=np.int64))))
+        vals.append(np.asarray(v, dtype=np.float64))
+        off += m
+    r = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+    c = np.concatenate(cols) if cols else np.zeros(0, np.int64)
+    order = np.lexsort((r, c))
+    cp = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(c, minlength=n), out=cp[1:])
+    return _base.spmatrix.from_ccs(off, n, cp, r[order], (np.concatenate(vals) if vals else np.zeros(0))[order])
+
+
+def _flat(v):
+    return np.asarray(_base._dense_buffer(v)[0], dtype=np.float64).reshape(-1) if not isinstance(v, np.ndarray) else \
+        np.asarray(v, dtype=np.float64).reshape(-1, order="F")
+
+
+def _nrows(B):
+    return _cone._ccs(B)[0]
+
+
+def _common(sol, keys):
+    out = {k: sol[k] for k in ("status", "x", "y", "gap", "relative gap", "primal objective", "dual objective",
+                                "primal infeasibility", "dual infeasibility", "primal slack", "dual slack",
+                                "residual as primal infeasibility certificate", "residual as dual infeasibility certificate",
+                                "iterations")}
+    out.update(keys)
+    return out
+
+
+def socp(c, Gl=None, hl=None, Gq=None, hq=None, A=None, b=None, kktsolver=None, solver=None, primalstart=None, dualstart=None, **kw):
+    """solvers.socp (coneprog.py:3044-3596): minimize c'x s.t. Gl x <= hl, ||.||-cone constraints Gq[k] x + sq[k] = hq[k],
+    A x = b; conelp with dims = {'l': rows of Gl, 'q': [rows of Gq[k]], 's': []}.  Returns x, y, sl, sq, zl, zq and the
+    reference's status keys (numpy arrays)."""
+    if solver is not None:
+        raise NotImplementedError("kvxopt_amd.solvers runs misc.kkt_chol on the GPU; 'solver' is not selectable")
+    n = _flat(c).size
+    Gq, hq = list(Gq or []), list(hq or [])
+    if len(Gq) != len(hq):
+        raise TypeError("'Gq' and 'hq' must have the same length")
+    ml = _nrows(Gl) if Gl is not None else 0
+    qd = [_nrows(G) for G in Gq]
+    G = _stack(([Gl] if Gl is not None else []) + Gq, n)
+    h = np.concatenate([_flat(hl)] + [_flat(x) for x in hq]) if Gl is not None else \
+        np.concatenate([_flat(x) for x in hq] or [np.zeros(0)])
+    dims = {"l": ml, "q": qd, "s": []}
+    ps = ds = None
+    if primalstart is not None:
+        ps = {"x": primalstart["x"], "s": np.concatenate([_flat(primalstart["sl"])] * (ml > 0) + [_flat(v) for v in primalstart["sq"]])}
+    if dualstart is not None:
+        ds = {"z": np.concatenate([_flat(dualstart["zl"])] * (ml > 0) + [_flat(v) for v in dualstart["zq"]])}
+        if "y" in dualstart:
+            ds["y"] = dualstart["y"]
+    sol = conelp(c, G, h, dims, A=A, b=b, primalstart=ps, dualstart=ds, kktsolver=kktsolver, **kw)
+    off = np.concatenate([[ml], ml + np.cumsum(qd)]).astype(int)
+
+    def split(v):
+        if v is None:
+            return None, None
+        return v[:ml].copy(), [v[off[k]:off[k + 1]].copy() for k in range(len(qd))]
+    sl, sq = split(sol["s"])
+    zl, zq = split(sol["z"])
+    return _common(sol, {"sl": sl, "sq": sq, "zl": zl, "zq": zq})
+
+
+def sdp(c, Gl=None, hl=None, Gs=None, hs=None, A=None, b=None, kktsolver=None, solver=None, primalstart=None, dualstart=None, **kw):
+    """solvers.sdp (coneprog.py:3597-4186): minimize c'x s.t. Gl x <= hl, sum_j x_j mat(Gs[k][:, j]) <= hs[k] (semidefinite),
+    A x = b; conelp with dims = {'l': rows of Gl, 'q': [], 's': [orders of hs[k]]}.  The 's' blocks of the result (ss, zs)
+    are full symmetric m_k x m_k matrices, as the reference returns them."""
+    if solver is not None:
+        raise NotImplementedError("kvxopt_amd.solvers runs misc.kkt_chol on the GPU; 'solver' is not selectable")
+    n = _flat(c).size
+    Gs, hs = list(Gs or []), list(hs or [])
+    if len(Gs) != len(hs):
+        raise TypeError("'Gs' and 'hs' must have the same length")
+    ml = _nrows(Gl) if Gl is not None else 0
+    sd = []
+    for k, H in enumerate(hs):
+        m = int(round(np.sqrt(_flat(H).size)))
+        if m * m != _flat(H).size or _nrows(Gs[k]) != m * m:
+            raise TypeError("'Gs[%d]' must have %d rows and 'hs[%d]' must be square" % (k, m * m, k))
+        sd.append(m)
+    G = _stack(([Gl] if Gl is not None else []) + Gs, n)
+    h = np.concatenate(([_flat(hl)] if Gl is not None else []) + [_flat(H) for H in hs] or [np.zeros(0)])
+    dims = {"l": ml, "q": [], "s": sd}
+    ps = ds = None
+    if primalstart is not None:
+        ps = {"x": primalstart["x"], "s": np.concatenate([_flat(primalstart["sl"])] * (ml > 0) + [_flat(v) for v in primalstart["ss"]])}
+    if dualstart is not None:
+        ds = {"z": np.concatenate([_flat(dualstart["zl"])] * (ml > 0) + [_flat(v) for v in dualstart["zs"]])}
+        if "y" in dualstart:
+            ds["y"] = dualstart["y"]
+    sol = conelp(c, G, h, dims, A=A, b=b, primalstart=ps, dualstart=ds, kktsolver=kktsolver, **kw)
+    off = np.concatenate([[ml], ml + np.cumsum([m * m for m in sd])]).astype(int)
+
+    def split(v):
+        if v is None:
+            return None, None
+        return v[:ml].copy(), [v[off[k]:off[k + 1]].reshape((m, m), order="F").copy() for k, m in enumerate(sd)]
+    sl, ss = split(sol["s"])
+    zl, zs = split(sol["z"])
+    return _common(sol, {"sl": sl, "ss": ss, "zl": zl, "zs": zs})

@@ -199,3 +199,52 @@ def convdiff_2d(g, seed=0):
     np.add.at(colptr, J + 1, 1)
     np.cumsum(colptr, out=colptr)
     return n, colptr, I.astype(np.int64), V
+
+
+def socp_sum_of_norms(nx, ncones, order=4, nnz_row=3, seed=31):
+    """Sparse SOCP (robust least squares as a sum of norms with a box): variables (x, t), x in R^nx, t in R^ncones,
+
+        minimize sum_k t_k  s.t.  || A_k x - b_k ||_2 <= t_k  (cones of `order`),  -1 <= x <= 1,
+
+    A_k: (order - 1) x nx with `nnz_row` random entries per row, in a window of 16 columns around k nx / ncones (a banded
+    coupling: the factor of S stays sparse).  Returns (c, G as (N, n, colptr, rowind, values), h, dims):
+    the 'l' rows x <= 1, -x <= 1 first, then cone k as the rows s = (t_k, A_k x - b_k) = h - G (x, t)."""
+    rng = np.random.default_rng(seed)
+    n = nx + ncones
+    rows, cols, vals = [np.arange(nx), nx + np.arange(nx)], [np.arange(nx), np.arange(nx)], [np.ones(nx), -np.ones(nx)]
+    ml = 2 * nx
+    h = [np.ones(ml)]
+    for k in range(ncones):
+        r0 = ml + k * order
+        rows.append(np.array([r0])); cols.append(np.array([nx + k])); vals.append(np.array([-1.0]))
+        rr = np.repeat(np.arange(1, order), nnz_row) + r0
+        cc = (k * nx // ncones + rng.integers(0, 16, size=rr.size)) % nx
+        rows.append(rr); cols.append(cc); vals.append(-rng.standard_normal(rr.size))
+        h.append(np.concatenate([[0.0], -rng.standard_normal(order - 1)]))
+    N = ml + ncones * order
+    r, c, v = np.concatenate(rows).astype(np.int64), np.concatenate(cols).astype(np.int64), np.concatenate(vals)
+    key = c * N + r
+    uniq, start = np.unique(key, return_index=True)
+    order_ = np.argsort(key, kind="stable")
+    v = np.add.reduceat(v[order_], np.searchsorted(key[order_], uniq))
+    ri, ci = (uniq % N).astype(np.int64), (uniq // N).astype(np.int64)
+    cp = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(ci, minlength=n), out=cp[1:])
+    cvec = np.concatenate([np.zeros(nx), np.ones(ncones)])
+    return cvec, (N, n, cp, ri, v), np.concatenate(h), {"l": ml, "q": [order] * ncones, "s": []}
+
+
+def sdp_box(n, blocks, density=0.3, seed=32):
+    """SDP with a few blocks and an 'l' box: minimize c'x s.t. sum_j x_j F_kj <= m_k I (block k, order m_k), -1 <= x <= 1.
+    F_kj symmetric with about `density` of its entries nonzero; G stores the whole of every F_kj (column j of block k's rows
+    = vec(F_kj)).  x = 0 is strictly feasible and the box bounds the problem.  Returns (c, G dense (N x n), h, dims)."""
+    rng = np.random.default_rng(seed)
+    ml = 2 * n
+    G = [np.vstack([np.eye(n), -np.eye(n)])]
+    h = [np.ones(ml)]
+    for m in blocks:
+        F = rng.standard_normal((m, m, n)) * (rng.random((m, m, n)) < density)
+        F = F + F.transpose(1, 0, 2)
+        G.append(F.reshape(m * m, n, order="F"))
+        h.append((m * np.eye(m)).reshape(-1, order="F"))
+    return rng.standard_normal(n), np.vstack(G), np.concatenate(h), {"l": ml, "q": [], "s": list(blocks)}
