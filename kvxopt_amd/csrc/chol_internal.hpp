@@ -1,4 +1,5 @@
-// Internal (library-private) view of the Cholesky factor object shared by api.cpp and dist_api.cpp.
+// Internal (library-private) view of the Cholesky factor object shared by api.cpp, chol_setup.cpp, chol_factor.cpp, chol_solve.cpp
+// and dist_api.cpp.
 #pragma once
 #include "../../include/kvxhip.h"
 #include "abi_guard.hpp"
@@ -80,6 +81,38 @@ struct LazyExec {
     }
 };
 
+// Every environment knob of the Cholesky host path (the launchers' own -- KVX_FAR_WGS, KVX_SYRK_LDS_TILES, KVX_SYRK128_TILES,
+// KVX_FWD_NARROW_WGS, KVX_WAVE_OCC -- live in the .hip files).  read_chol_knobs() fills the table ONCE PER FACTOR, at device set-up
+// (ensure_device): a process may change a knob between two factors, never under a factor that exists.  DESIGN.md has the table.
+struct CholKnobs {
+    // ---- the handle's analysis and device tables
+    int sub_maxf = 0;               // KVX_SUB_MAXF: fronts per leaf subtree, 1..KVX_SUB_MAXF (0: by the order of the system, analyze_subtrees)
+    bool factor_subtrees = false;   // KVX_FACTOR_SUBTREES=1: the leaf subtrees are factored by one wavefront each before the level loop (measured slower, build_subtrees)
+    int u_block = 384;              // KVX_U_BLOCK: pivot columns per pass of the deferred update, a multiple of 64
+    bool init_two_passes = false;   // KVX_INIT_TWO_PASSES (any value): zero L and scatter A in two launches (no grouped scatter map)
+    bool use_subtrees = true;       // KVX_NO_SUBTREES=1: no leaf subtrees in the solves
+    bool use_graph = true;          // KVX_NO_GRAPH=1: every call enqueues its launches itself
+    int wide_from = -1;             // KVX_WIDE_FROM: right-hand sides from which the rhs-major path is used (0 = never; -1 = by size, see solve_dev)
+    int side_spread = 1;            // KVX_SIDE_SPREAD=0: the small-front launches of a level on one stream
+    int two_level_m = 6144;         // KVX_TWO_LEVEL_M: levels whose largest front is at least this order use the two-level blocked update (with KVX_DEFER_U=0)
+    int outer_block = 1024;         // KVX_OUTER_BLOCK: columns per outer block of the two-level update, a multiple of 64: config 5 runs at 33.3 / 37.5 / 38.6 / 37.4 TF/s with 256 / 512 / 1024 / 2048
+    // ---- the schedule of the factorisation and of the sweeps (every test that sets one of these starts a process of its own)
+    int64_t asm_potrf_wgs = 1024;   // KVX_ASM_POTRF_WGS: largest extend-add launch (workgroups) that also factors the first diagonal block; 0 = never
+    int64_t pair_tiles = 3000;      // KVX_PAIR_TILES: tile count of a launch from which on two panels share one pass (chain_pairs)
+    int defer_u = 1;                // KVX_DEFER_U=0: the round-3 schedules -- no blocked chain, two-level outer blocks from two_level_m on
+    bool syrk_direct = false;       // KVX_SYRK_DIRECT=1: the round-3 trailing-update kernels; process-wide, the launchers read the same syrk_direct() (device.hpp)
+    double blocked_gf = 0.5;        // KVX_BLOCKED_GF: Gflop per panel step from which on a level's chain is blocked (choose_chain)
+    int u_stream = 1;               // KVX_U_STREAM=0: the far updates of the blocked chain on the chain's own stream
+    bool pipe_own_stream = false;   // KVX_PIPE_OWN_STREAM=1: the pipelined forward sweep on side[2] instead of side[0] (pipe_level_hook)
+    bool solve_nofork = false;      // KVX_SOLVE_NOFORK (non-zero): the sweeps keep every kernel class of a level on one stream
+};
+CholKnobs read_chol_knobs();
+// ---- per call, debugging: read where they are used, every time (KVX_SPSOLVE_DENSE is toggled on one factor by its test)
+//   chol_factor.cpp  KVX_DBG_MEMSET_NODES, KVX_DBG_GRAPH_SYNC, KVX_DBG_GRAPH_DOT          api.cpp  KVX_SPSOLVE_DENSE, KVX_FREE_TIMING
+//   chol_solve.cpp   KVX_DBG_NO_SOLVE_GRAPH, KVX_FUSED_EAGER, KVX_SUBTREES_PLAIN, KVX_PIPE_FRONTS (first fused call of a factor), KVX_DBG_T (once)
+// "1" = no factor graphs at all, "<n>" = none for factors of order n (enqueue_factor); any value = no graph of the one-enqueue form
+inline const char *dbg_no_factor_graph() { return getenv("KVX_DBG_NO_FACTOR_GRAPH"); }
+
 struct LevelPlan {
     // fronts of the level grouped by kernel class (symbolic.hpp front_class), big first
     int64_t off[KVX_NCLS];   // offset into d_lists of class c
@@ -88,9 +121,7 @@ struct LevelPlan {
     int maxk[KVX_NCLS];
     int big_maxk = 0;          // largest pivot count among the big fronts (solves)
     int chain_maxk = 0;        // ... among those factored by the batched multi-workgroup chain (all of them)
-    int big_maxu = 0;          // largest update matrix (m - k) among the big fronts
     double big_flops = 0.0;    // flops of the big fronts of the level
-    int64_t big_u_len = 0;   // doubles of the parity buffer used by the big fronts (head)
     // solve groups: [big], [LDS classes: 256 threads], [wave classes: 64 threads]
     int64_t soff[3];
     int scnt[3];
@@ -100,6 +131,7 @@ struct LevelPlan {
 struct kvx_chol {
     Symbolic S;
     kvx_chol_opts opts;
+    CholKnobs K;              // the environment knobs as they stood at this factor's device set-up
     bool dev_ready = false;
     bool numeric = false;
     bool pending = false;     // a factorisation was enqueued and its status not yet read
@@ -108,8 +140,8 @@ struct kvx_chol {
     bool diag_valid = false;
     int64_t minor = 0;
     hipStream_t stream = nullptr;
-    hipStream_t side[4] = {nullptr, nullptr, nullptr, nullptr};   // [3]: trailing updates beside the pivot chain   // independent kernel classes of one level run concurrently
-    hipEvent_t ev_fork = nullptr, ev_fork2 = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipStream_t side[3] = {nullptr, nullptr, nullptr};   // independent kernel classes of one level run concurrently; [2]: far updates beside the pivot chain
+    hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_out = nullptr;                // orders the caller's (null-stream) work after an asynchronous solve
     hipEvent_t ev_in = nullptr;                 // orders the factor's stream after the caller's (null-stream) work
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -157,7 +189,7 @@ struct kvx_chol {
     std::vector<int32_t> flists_host;              // host copy of d_flists
     // Per (level, panel step) the big fronts still in the chain, largest trailing matrix first, and per (level, block of
     // u_block pivot columns) those whose update matrix the block updates, largest update matrix first: the LDS-staged
-    // trailing update numbers its workgroups over size classes of these lists (api.cpp build_chain_lists, device.hpp TileClasses)
+    // trailing update numbers its workgroups over size classes of these lists (chol_setup.cpp build_chain_lists, device.hpp TileClasses)
     struct ChainList { int64_t off; int cnt; };
     std::vector<std::vector<ChainList>> chain_steps, u_steps;     // [level][jb / 64], [level][kb / u_block]
     std::vector<int32_t> chain_host, chain_m, chain_k;            // the lists concatenated; order and pivot count of every entry
@@ -165,22 +197,18 @@ struct kvx_chol {
     std::vector<hipEvent_t> ev_u;                  // per block of a level's chain: its panels are solved (the deferred updates' stream waits)
     hipEvent_t ev_ujoin = nullptr;
     int last_fused_path = 0;                       // kvx_chol_last_fused_path
-    int u_block = 384;                             // pivot columns per pass of the deferred update (KVX_U_BLOCK)
     int32_t *d_flists = nullptr;
     std::vector<int64_t> linv_off_host;        // per front: offset of its inverted diagonal blocks in d_Linv (-1: not a big front)
     uint8_t *d_keep = nullptr;                 // per permuted column: 1 = this rank reports the entry of x
     std::vector<int32_t> lists_host;           // level lists in use (filtered in sharded mode)
     std::vector<int64_t> lptr_host;
-    int outer_block = 1024;    // columns per outer block of the two-level update (KVX_OUTER_BLOCK; a multiple of 64): config 5 runs at 33.3 / 37.5 / 38.6 / 37.4 TF/s with 256 / 512 / 1024 / 2048
-    int two_level_m = 6144;    // levels whose largest front is at least this order use the two-level blocked update (KVX_TWO_LEVEL_M)
     // leaf subtrees walked by one wavefront each in the solves (build_subtrees)
     SubDesc *d_subs = nullptr;
     SubDesc *d_subs_f = nullptr;               // the same subtrees grouped by LDS image size (32 / 48 / 64 rows) for the factorisation
     int nsubf[3] = {0, 0, 0};
-    bool factor_subtrees = false;              // opt-in KVX_FACTOR_SUBTREES=1: the subtrees are factored by one wavefront each before the level loop (measured slower)
+    bool factor_subtrees = false;              // K.factor_subtrees on a factor that has subtrees and is not sharded: they are factored by one wavefront each before the level loop
     int32_t *d_cd_woff = nullptr, *d_depth = nullptr, *d_lists_sw = nullptr;
     int nsub = 0, nsub32 = 0, nsub48 = 0;      // subtrees; the first nsub32 hold only fronts of order <= 32, the next nsub48 - nsub32 of order <= 48
-    bool use_subtrees = true;
     std::vector<SubDesc> subs_host;
     std::vector<int32_t> cd_woff_host;
     std::vector<uint8_t> in_sub;
@@ -191,13 +219,10 @@ struct kvx_chol {
     // many right-hand sides (kernels_wide.hip): per front row, the children's update rows that land on it (built at the first such solve)
     int32_t *d_inv_ptr = nullptr, *d_inv_src = nullptr, *d_iperm = nullptr;   // d_iperm: position of every caller row in the permuted order
     int wide_state = 0;                        // 0 = not built yet, 1 = ready, -1 = not available for this factor (sharded mode, index range)
-    int wide_from = -1;                        // right-hand sides from which the rhs-major path is used (KVX_WIDE_FROM; 0 = never; -1 = by size, see solve_dev)
     bool solve_merged = false;                 // sw lists hold every small front outside the subtrees (one launch per level)
-    int side_spread = 1;      // spread the small-front launches of a level over the streams (KVX_SIDE_SPREAD=0: one stream)
     std::vector<LevelPlan> plan;
     // hipGraph replay of the (static) launch sequences: captured on the second call, replayed after.
     // Disabled while a kernel family is being event-timed and by KVX_NO_GRAPH=1.
-    bool use_graph = true;
     int factor_calls = 0;
     LazyExec g_factor;
     struct SolveGraph { int kind; int nrhs; int calls; LazyExec exec; };
@@ -254,16 +279,22 @@ inline void prof_collect(kvx_chol *F)
 }
 
 
-// api.cpp
+// chol_setup.cpp
 void build_plan_from(const Symbolic &S, const std::vector<int32_t> &lists, const std::vector<int64_t> &lptr, std::vector<LevelPlan> &plan);
 void build_plan(kvx_chol *F);
 int build_subtrees(kvx_chol *F);
 int build_chain_lists(kvx_chol *F);
 int ensure_device(kvx_chol *F);
 int ensure_solve_ws(kvx_chol *F, int64_t nrhs);
+int ensure_wide(kvx_chol *F);
+void destroy_graphs(kvx_chol *F);
+// chol_factor.cpp
 int wait_for_caller(kvx_chol *F);
 int enqueue_factor_body(kvx_chol *F, int lfrom = -1, int lto = 0, bool prologue = true, bool epilogue = true);
+int enqueue_factor(kvx_chol *F);
 int finish_factor(kvx_chol *F, int64_t *minor);
+void dump_graph_dot(hipGraph_t graph);           // KVX_DBG_GRAPH_DOT
+// chol_solve.cpp
 // the streams and events a triangular sweep forks its kernel classes over (default: the factor's own main / side[0] / side[1])
 struct SweepStreams { hipStream_t main, lds, wave; hipEvent_t fork, join0, join1; };
 // wait_levels: the sweep follows a factorisation in flight -- each level waits for that level's completion event (ev_lvl)
@@ -272,8 +303,43 @@ struct SweepStreams { hipStream_t main, lds, wave; hipEvent_t fork, join0, join1
 void enqueue_fwd(kvx_chol *F, double *X, int64_t ldx, int nrhs, int lfrom = -1, int lto = 0, const SweepStreams *ss = nullptr, bool wait_levels = false,
                  bool sub_tail = false);
 void enqueue_bwd(kvx_chol *F, double *X, int64_t ldx, int nrhs, int lfrom = 0, int lto = -1);
-void destroy_graphs(kvx_chol *F);
+int solve_dev(kvx_chol *F, int sys, double *B, int64_t nrhs, int64_t ldB, bool async = false);
+int factor_solve_dev(kvx_chol *F, const double *values_dev, double *B, int64_t nrhs, int64_t ldB, bool async = false);
+int spsolve_forward_reach(kvx_chol *F, int sys, int64_t ncol, const int64_t *Bp, const int64_t *Bi, const double *Bx,
+                          std::vector<int64_t> &xp, std::vector<int64_t> &xi, std::vector<double> &xx);
 // dist_api.cpp
 void dist_release(kvx_chol *F);
+
+// Capture `body` (which enqueues on F->stream and, through events, on the side streams) into an
+// executable graph.  Leaves `out` without an executable (and the stream usable) if capture is not possible.
+template <class Body>
+void capture_graph(kvx_chol *F, Body body, LazyExec &out)
+{
+    out.tried = true;
+    hipGraph_t graph = nullptr;
+    if (hipStreamBeginCapture(F->stream, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); return; }
+    int rc = body();
+    hipError_t e = hipStreamEndCapture(F->stream, &graph);
+    if (rc != KVX_OK || e != hipSuccess || !graph) { (void)hipGetLastError(); if (graph) (void)hipGraphDestroy(graph); return; }
+    dump_graph_dot(graph);
+    out.start(graph);                              // instantiation on a thread of its own; the graph is destroyed there
+}
+
+// One call of a launch sequence that may replay from a graph.  slot: the graph slot of this sequence (its LazyExec `exec` and its
+// call counter `calls`; null: no graph for this call).  Counts the call, captures on the second one (if may_capture), replays when
+// the executable is ready and runs the body itself otherwise -- as the call that takes the capture does: a capture runs nothing.
+template <class Slot, class Body>
+int capture_or_replay(kvx_chol *F, Slot *slot, bool may_capture, Body body)
+{
+    hipGraphExec_t exec = nullptr;
+    if (slot) {
+        slot->calls++;
+        if (!slot->exec.tried && slot->calls >= 2 && may_capture) capture_graph(F, body, slot->exec);
+        exec = slot->exec.ready();
+    }
+    if (!exec) return body();
+    HIPCHK(hipGraphLaunch(exec, F->stream));
+    return KVX_OK;
+}
 
 }  // namespace kvx

@@ -226,6 +226,9 @@ void launch_syrk_outer(hipStream_t st, const DevSym &ds, const int32_t *list, in
 void launch_syrk_pair(hipStream_t st, const DevSym &ds, const int32_t *list, int count, int max_m, int jb,
                       double *Lx, double *Uout, double *Linv, int *status, int col_lim = 0x7fffffff);
 
+// KVX_SYRK_DIRECT=1 (read once per process, chol_setup.cpp): the round-3 kernels (every wave loads its operands from global memory)
+// instead of the LDS-staged tiles -- the launchers of kernels_big.hip and the host schedule (CholKnobs) take the same value
+bool syrk_direct();
 // Host-side count of the trailing-update launches enqueued, by kernel / schedule (process-wide; kvx_dbg_syrk_counts reads them).
 // A graph replay enqueues nothing and counts nothing.
 enum SyrkVariant {

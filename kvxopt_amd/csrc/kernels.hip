@@ -84,7 +84,7 @@ void launch_copy_d(hipStream_t st, double *dst, const double *src, int64_t n)
 // Zero the factor AND scatter the caller's values in ONE pass over L.  A's entries land in nearly every cache line of the small
 // fronts' panels (three entries per column of 20-60 rows on the 5-point system), so the scatter behind the zeroing was a second
 // full read-modify-write pass over L -- 64 us behind the 63 us of the zeroing on config 2.  Here a workgroup owns a chunk of
-// KVX_INIT_CHUNK doubles of L (16 KB; 4 / 8 / 16 / 32 / 64 KB measured: 101 / 105 / 87-95 / 91 / 84 us): zeros in LDS, the chunk's entries on top (the scatter map grouped by chunk on the host, api.cpp),
+// KVX_INIT_CHUNK doubles of L (16 KB; 4 / 8 / 16 / 32 / 64 KB measured: 101 / 105 / 87-95 / 91 / 84 us): zeros in LDS, the chunk's entries on top (the scatter map grouped by chunk at device set-up, chol_setup.cpp),
 // one coalesced store of the chunk.  The gather from the caller's value array (24 MB, cached) is the cheap side.
 #ifndef KVX_INIT_SHIFT_V
 #define KVX_INIT_SHIFT_V 11

@@ -854,7 +854,7 @@ static void launch_syrk_lds(hipStream_t st, bool uonly, const DevSym &ds, const 
 }
 
 // the launches of the single-GPU chain: `list` = the big fronts still in the chain at panel step kb, largest update region
-// first (api.cpp build_chain_lists), hm / hk their orders and pivot counts.  Launches of few tiles with one or two panels go
+// first (chol_setup.cpp build_chain_lists), hm / hk their orders and pivot counts.  Launches of few tiles with one or two panels go
 // to the direct kernel (every wave requests all operands of a tile up front: one memory round trip on the chain's critical
 // path where the LDS-staged kernel has one per 16 panel columns); KVX_SYRK_LDS_TILES = tile count from which on the staged one.
 void launch_syrk_step(hipStream_t st, const DevSym &ds, const int32_t *list, const int32_t *hm, const int32_t *hk, int count, int kb, int klen,
@@ -1120,13 +1120,6 @@ static dim3 syrk128_grid(int rows, int count)
 }
 
 static TileClasses no_classes() { TileClasses tc; tc.ncls = 0; return tc; }
-
-// KVX_SYRK_DIRECT=1: the round-3 kernels (every wave loads its operands from global memory) instead of the LDS-staged tiles
-static bool syrk_direct()
-{
-    static const bool v = [] { const char *e = getenv("KVX_SYRK_DIRECT"); return e && e[0] == '1'; }();
-    return v;
-}
 
 void launch_syrk_trailing(hipStream_t st, const DevSym &ds, const int32_t *list, int count, int max_m, int jb,
                           double *Lx, double *Uout, double *Linv, int *status, int col_lim)

@@ -12,7 +12,7 @@
 //   * the only sequential part is the 16 x 16 diagonal block of a small front: one row per register, one right-hand side per
 //     lane, the 120 multipliers read as LDS broadcasts; big fronts use the inverted 64 x 64 diagonal blocks the factorisation
 //     leaves behind (a GEMM as well);
-//   * the children's update vectors are pulled per parent row through an inverse map (built once per analysis, api.cpp),
+//   * the children's update vectors are pulled per parent row through an inverse map (built once per analysis, chol_setup.cpp ensure_wide),
 //     children in list order: no accumulator indexed by a run-time row number is needed, and the sum order is fixed.
 // One wavefront per (small front, chunk); one 1024-thread workgroup per (big front, chunk).  The columns agree with the
 // single-rhs kernels to rounding (the summation order of a GEMM differs from the substitution chains), not bit for bit.

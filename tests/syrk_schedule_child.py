@@ -1,12 +1,12 @@
 """Child process of the trailing-update schedule tests (test_syrk_schedules_gpu.py, test_chol_gpu.py::test_syrk128_variant_parity).
 
 The schedule knobs of the big fronts' pivot chain (KVX_DEFER_U, KVX_SYRK_DIRECT, KVX_PAIR_TILES, KVX_BLOCKED_GF, KVX_U_STREAM,
-KVX_SYRK_LDS_TILES, KVX_FAR_WGS) are read once per process, so every setting runs in a process of its own.  For each matrix named
+KVX_SYRK_LDS_TILES, KVX_FAR_WGS) are read once per factor or once per process (chol_internal.hpp CholKnobs), so every setting runs in a process of its own.  For each matrix named
 on the command line the child factors three times -- eagerly, under capture, from the replayed graph -- and checks the factor
 entries, diag() and the solves of sys 0-8 against the CPU oracle (prepared once by the parent: `prepare`), the residual, the bits
 of the three factorisations, and reports the trailing-update launches per kernel (kvx_dbg_syrk_counts) as one RESULT line.
 
-Also imported by the tests for the matrices and for the chain lists of a factor (rebuilt from the analysis, as api.cpp
+Also imported by the tests for the matrices and for the chain lists of a factor (rebuilt from the analysis, as chol_setup.cpp
 build_chain_lists does)."""
 import hashlib
 import json
@@ -96,7 +96,7 @@ def matrix(name):
 ALL_MATRICES = list(GADGETS) + ["rand2500", "lap150", "stencil21_40", "dense_rows"]
 
 
-# ---- the chain lists of a factor (api.cpp build_chain_lists) ----------------------------------------------------------------
+# ---- the chain lists of a factor (chol_setup.cpp build_chain_lists) ----------------------------------------------------------------
 def front_class_big(m, k):
     return m > 128 or k > 64
 
