@@ -453,6 +453,18 @@ int kvx_cone_pattern(kvx_cone *C, int64_t *snz, int64_t *Sp, int64_t *Si);
  * MFMA).  Every entry is summed in a fixed order (no floating-point atomics).  Null stream, enqueue only. */
 int kvx_cone_assemble_dev(kvx_cone *C, const double *Gx_dev, const double *di_dev, const double *v_dev, const double *beta_dev,
                           const double *rti_dev, double *Sx_dev);
+/* The same with a symmetric n x n matrix H added: S = H + Gs' Gs (coneqp with H = P, misc.py:1275-1277: K += H).  Hp, Hi: CCS
+ * pattern of H; its lower triangle is used and entries above the diagonal are ignored.  The pattern of S (kvx_cone_pattern) is
+ * the union of the cliques and tril(H).  Hp == NULL: exactly kvx_cone_plan.  An entry stored twice is KVX_EINVAL.  Host only. */
+int kvx_cone_plan_h(int64_t ml, int64_t nq, const int64_t *q, int64_t ns, const int64_t *s, int64_t n, const int64_t *Gp,
+                    const int64_t *Gi, const int64_t *Hp, const int64_t *Hi, kvx_cone **out);
+/* Sx_dev[snz] := H + Gs' Gs on a plan of kvx_cone_plan_h; Hx_dev: the values on (Hp, Hi), all of them (those above the diagonal
+ * are not read).  H is added inside the gather of the 'q' and 's' parts, last: cones, then blocks, then H; no floating-point
+ * atomics.  Hx_dev == NULL on a plan without H: exactly kvx_cone_assemble_dev.  A plan made with a non-empty H pattern is
+ * assembled through this entry only: kvx_cone_assemble_dev on it, or Hx_dev == NULL here, is KVX_EINVAL.  Null stream,
+ * enqueue only. */
+int kvx_cone_assemble_h_dev(kvx_cone *C, const double *Gx_dev, const double *di_dev, const double *v_dev, const double *beta_dev,
+                            const double *rti_dev, const double *Hx_dev, double *Sx_dev);
 void kvx_cone_free(kvx_cone *C);
 /* helpers of the general-cone driver (coneprog.py:1273-1280, 1379-1431): y[idx[i]] := x[i] (an 's' diagonal placed into its
  * block), and x_k(i, j) *= sqrt(w_j) for every 's' block (w in the off1 layout of the kvx_nts_* entries) */

@@ -1,6 +1,7 @@
-"""Device-resident cone-LP interior-point driver for general cones ('l' rows, 'q' second-order cones, 's' semidefinite blocks):
+"""Device-resident cone-LP and cone-QP interior-point drivers for general cones ('l' rows, 'q' second-order cones, 's'
+semidefinite blocks):
 
-    minimize c'x  subject to  G x + s = h,  A x = b,  s in C = R^ml_+ x Q^q_1 x ... x S^m_1 x ...
+    minimize c'x (conelp) or (1/2) x'Px + q'x (coneqp)  subject to  G x + s = h,  A x = b,  s in C = R^ml_+ x Q^q_1 x ... x S^m_1 x ...
 
 A restatement of the reference's `coneprog.conelp` (src/python/coneprog.py:31-1436) with its KKT solver `misc.kkt_chol`
 (misc.py:1213-1349): the reduced matrix S = Gs' Gs, Gs = pack2(W^-T G), assembled on a fixed sparsity pattern by
@@ -8,6 +9,10 @@ kvx_cone_assemble_dev (csrc/cone_api.cpp, csrc/kkt_cone.hip) and factored by the
 one analysis.  Equality constraints are eliminated through K = A S^-1 A' (dense in HBM), as lp.KKTGenEqDev does; the reference
 eliminates them by a QR factorisation of A' instead (same solution, different roundings).  Iterates, the scaling W (d, di, v,
 beta, r, rti) and all work vectors stay in HBM; the host reads scalars only (inner products, step lengths).
+
+`coneqp` restates the reference's `coneprog.coneqp` (coneprog.py:1440-2547) the same way, with the reduced matrix
+S = P + Gs' Gs: the plan takes the lower pattern of P (kvx_cone_plan_h) and the gather of the assembly adds its values
+(kvx_cone_assemble_h_dev).
 """
 import ctypes
 import math
@@ -18,7 +23,7 @@ import numpy as np
 from . import _lib, base
 from ._lib import DeviceBuffer, lib, raise_for
 from .chol import Factor
-from .lp import DVec, SpMatDev, dense_schur
+from .lp import DVec, SpMatDev, SymSpMatDev, _lower_ccs, dense_schur
 
 EXPON = 3          # coneprog.py:423
 STEP = 0.99        # coneprog.py:424
@@ -213,6 +218,51 @@ def put_diag(D, dst, srcp):
         raise_for(lib().kvx_vec_scatter_dev(D.tot1, srcp + 8 * D.ind, D.d_sdiag.ptr, dst.ptr + 8 * D.ind))
 
 
+def compute_scaling(D, s, z, W, lmbda):
+    """misc.compute_scaling (misc.py:250-419): W and lmbda from the interior points s, z."""
+    ind = D.ind
+    if D.ml:
+        raise_for(lib().kvx_nt_compute_scaling_dev(D.ml, s.ptr, z.ptr, W.d.ptr, W.di.ptr, lmbda.ptr))
+    if D.nq:
+        raise_for(lib().kvx_ntq_compute_scaling_dev(D.nq, D.d_qoff.ptr, s.ptr + 8 * D.ml, z.ptr + 8 * D.ml, W.v.ptr,
+                                                    W.beta.ptr, lmbda.ptr + 8 * D.ml))
+    if D.tot2:
+        stb = DeviceBuffer.from_array(np.array([2 ** 31 - 1], dtype=np.int32))
+        raise_for(lib().kvx_nts_compute_scaling_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, s.ptr + 8 * ind, z.ptr + 8 * ind,
+                                                    W.r.ptr, W.rti.ptr, lmbda.ptr + 8 * ind, D.work.ptr, stb.ptr))
+        if int(stb.download(np.int32, 1)[0]) != 2 ** 31 - 1:
+            raise ArithmeticError("compute_scaling: an 's' block of s or z is not positive definite")
+
+
+def step_and_update_scaling(D, W, lmbda, ds, dz, sigs, sigz, step):
+    """The end of an iteration (coneprog.py:1336-1431, 2463-2519): ds, dz (scaled by scale2, their 's' blocks replaced by the
+    eigenvectors whose eigenvalues are in sigs, sigz) become the updated iterates in the current scaling, then
+    misc.update_scaling (misc.py:422-634) refreshes W and lmbda."""
+    ind = D.ind
+    if ind:
+        raise_for(lib().kvx_vec_scal_dev(ind, step, ds.ptr))
+        raise_for(lib().kvx_vec_scal_dev(ind, step, dz.ptr))
+        raise_for(lib().kvx_vec_axpy_dev(ind, 1.0, D.e.ptr, ds.ptr))
+        raise_for(lib().kvx_vec_axpy_dev(ind, 1.0, D.e.ptr, dz.ptr))
+    scale2(D, lmbda.ptr, ds.ptr, inverse="I")
+    scale2(D, lmbda.ptr, dz.ptr, inverse="I")
+    if D.tot1:
+        for sg in (sigs, sigz):
+            sg.scal(step)
+            sg.addc(1.0)
+            raise_for(lib().kvx_nt_sinv_dev(D.tot1, sg.ptr, lmbda.ptr + 8 * ind))     # blas.tbsv(lmbda, sig, k = 0)
+        raise_for(lib().kvx_nts_colscale_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, ds.ptr + 8 * ind, sigs.ptr))
+        raise_for(lib().kvx_nts_colscale_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, dz.ptr + 8 * ind, sigz.ptr))
+    if D.ml:
+        raise_for(lib().kvx_nt_update_scaling_dev(D.ml, ds.ptr, dz.ptr, W.d.ptr, W.di.ptr, lmbda.ptr))
+    if D.nq:
+        raise_for(lib().kvx_ntq_update_scaling_dev(D.nq, D.d_qoff.ptr, ds.ptr + 8 * D.ml, dz.ptr + 8 * D.ml, W.v.ptr, W.beta.ptr,
+                                                   lmbda.ptr + 8 * D.ml))
+    if D.tot2:
+        raise_for(lib().kvx_nts_update_scaling_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, ds.ptr + 8 * ind, dz.ptr + 8 * ind, W.r.ptr,
+                                                   W.rti.ptr, lmbda.ptr + 8 * ind, D.work.ptr))
+
+
 def _ccs(M):
     """CCS of a dense or sparse matrix (ours or kvxopt's, or a 2-D numpy array); a dense matrix keeps every entry."""
     from .misc import _full_pattern
@@ -223,16 +273,28 @@ def _ccs(M):
 
 
 class ConePlan:
-    """kvx_cone_plan: the pattern of S = Gs' Gs and its assembly (host plan, device assembly)."""
+    """kvx_cone_plan / kvx_cone_plan_h: the pattern of S = Gs' Gs (+ H with a pattern Hp, Hi: the union with its lower triangle)
+    and its assembly (host plan, device assembly)."""
 
-    def __init__(self, D, n, Gp, Gi):
+    def __init__(self, D, n, Gp, Gi, Hp=None, Hi=None):
         h = ctypes.c_void_p()
         q = np.asarray(D.q, dtype=np.int64)
         s = np.asarray(D.s, dtype=np.int64)
         Gp = np.ascontiguousarray(Gp, dtype=np.int64)
         Gi = np.ascontiguousarray(Gi, dtype=np.int64)
-        raise_for(lib().kvx_cone_plan(D.ml, D.nq, _lib.pi(q) if q.size else None, D.ns, _lib.pi(s) if s.size else None, n,
-                                      _lib.pi(Gp), _lib.pi(Gi) if Gi.size else None, ctypes.byref(h)))
+        self.has_h = Hp is not None
+        if self.has_h:
+            Hp = np.ascontiguousarray(Hp, dtype=np.int64)
+            Hi = np.ascontiguousarray(Hi, dtype=np.int64)
+            if Hp.size != n + 1:
+                raise TypeError("the pattern of H must have %d columns" % n)
+            self.hnz = int(Hp[-1]) if n else 0
+            raise_for(lib().kvx_cone_plan_h(D.ml, D.nq, _lib.pi(q) if q.size else None, D.ns, _lib.pi(s) if s.size else None, n,
+                                            _lib.pi(Gp), _lib.pi(Gi) if Gi.size else None, _lib.pi(Hp), _lib.pi(Hi) if Hi.size else None,
+                                            ctypes.byref(h)))
+        else:
+            raise_for(lib().kvx_cone_plan(D.ml, D.nq, _lib.pi(q) if q.size else None, D.ns, _lib.pi(s) if s.size else None, n,
+                                          _lib.pi(Gp), _lib.pi(Gi) if Gi.size else None, ctypes.byref(h)))
         self._h = h
         snz = ctypes.c_int64()
         raise_for(lib().kvx_cone_pattern(h, ctypes.byref(snz), None, None))
@@ -241,8 +303,15 @@ class ConePlan:
         raise_for(lib().kvx_cone_pattern(h, ctypes.byref(snz), _lib.pi(self.Sp), _lib.pi(Si)))
         self.Si = Si[:snz.value].copy()
 
-    def assemble(self, Gx_dev, W, Sx):
-        raise_for(lib().kvx_cone_assemble_dev(self._h, Gx_dev.ptr, W.di.ptr, W.v.ptr, W.beta.ptr, W.rti.ptr, Sx.ptr))
+    def assemble(self, Gx_dev, W, Sx, Hx_dev=None):
+        """Sx := Gs' Gs, or H + Gs' Gs with the values Hx_dev of a plan made with an H pattern."""
+        if self.has_h:
+            if Hx_dev is None:
+                raise ValueError("the plan has an H pattern: its values are needed")
+            raise_for(lib().kvx_cone_assemble_h_dev(self._h, Gx_dev.ptr, W.di.ptr, W.v.ptr, W.beta.ptr, W.rti.ptr,
+                                                    Hx_dev.ptr if self.hnz else None, Sx.ptr))
+        else:
+            raise_for(lib().kvx_cone_assemble_dev(self._h, Gx_dev.ptr, W.di.ptr, W.v.ptr, W.beta.ptr, W.rti.ptr, Sx.ptr))
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -255,13 +324,21 @@ class KKTConeDev:
     analysis made at construction; solve(x, y, z) overwrites (bx, by, bz) with (ux, uy, W uz):
         x := bx + G' W^-1 W^-T bz   ('s' part of G' in sgemv form: trisc),  ux = S^-1 x  (p = 0),
         uz := W^-T (G ux - bz).
-    p > 0: u = S^-1 x, uy = K^-1 (A u - by) with K = A S^-1 A' dense, ux = S^-1 (x - A' uy)  (lp.KKTGenEqDev's elimination)."""
+    p > 0: u = S^-1 x, uy = K^-1 (A u - by) with K = A S^-1 A' dense, ux = S^-1 (x - A' uy)  (lp.KKTGenEqDev's elimination).
+
+    With H = (Hp, Hi, Hx), a symmetric n x n matrix in CCS form whose lower triangle is used (coneqp: H = P; misc.py:1275-1277),
+    the (1, 1) block of the KKT system is H and S = H + Gs' Gs on the union of the two patterns; the solve keeps its form.  S
+    is then positive definite when Rank([H; G]) = n, which is weaker than the Rank(G) = n that the path without H needs."""
 
     BLOCK_BYTES = 1 << 30
 
-    def __init__(self, D, n, Gp, Gi, Gx, p=0, Ap=None, Ai=None, Ax=None, chol_opts=None):
+    def __init__(self, D, n, Gp, Gi, Gx, p=0, Ap=None, Ai=None, Ax=None, chol_opts=None, Hp=None, Hi=None, Hx=None):
         self.D, self.n, self.p = D, n, p
-        self.plan = ConePlan(D, n, Gp, Gi)
+        self.plan = ConePlan(D, n, Gp, Gi, Hp, Hi)
+        self.Hx = None
+        if Hp is not None:
+            self.Hx = DVec(max(self.plan.hnz, 1))
+            self.set_hessian(Hx)
         self.fac = Factor(n, self.plan.Sp, self.plan.Si, "L", None, chol_opts)
         self.G = SpMatDev(D.N, n, Gp, Gi, Gx)
         self.Sx = DVec(max(self.plan.Si.size, 1))
@@ -289,8 +366,18 @@ class KKTConeDev:
             self.xs = DVec(n)
             self.kscale = 1.0
 
+    def set_hessian(self, Hx):
+        """New values of H on the pattern given at construction."""
+        if self.Hx is None:
+            raise ValueError("the KKT system was built without an H pattern")
+        Hx = np.ascontiguousarray(Hx, dtype=np.float64).reshape(-1)
+        if Hx.size != self.plan.hnz:
+            raise TypeError("H has %d values, its pattern %d" % (Hx.size, self.plan.hnz))
+        if Hx.size:
+            self.Hx.set(Hx)
+
     def assemble(self, W):
-        self.plan.assemble(self.G.vx, W, self.Sx)
+        self.plan.assemble(self.G.vx, W, self.Sx, self.Hx)
 
     def factor(self, W):
         """ArithmeticError if S (or K) is not positive definite."""
@@ -605,18 +692,7 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
             return finish("dual infeasible", iters, None, None, -1.0, None, None, None, None, dinfres, zs=False, ts=ts)
 
         if iters == 0:
-            # misc.compute_scaling (misc.py:250-419)
-            if D.ml:
-                raise_for(lib().kvx_nt_compute_scaling_dev(D.ml, s.ptr, z.ptr, W.d.ptr, W.di.ptr, lmbda.ptr))
-            if D.nq:
-                raise_for(lib().kvx_ntq_compute_scaling_dev(D.nq, D.d_qoff.ptr, s.ptr + 8 * D.ml, z.ptr + 8 * D.ml, W.v.ptr,
-                                                            W.beta.ptr, lmbda.ptr + 8 * D.ml))
-            if D.tot2:
-                stb = DeviceBuffer.from_array(np.array([2 ** 31 - 1], dtype=np.int32))
-                raise_for(lib().kvx_nts_compute_scaling_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, s.ptr + 8 * ind, z.ptr + 8 * ind,
-                                                            W.r.ptr, W.rti.ptr, lmbda.ptr + 8 * ind, D.work.ptr, stb.ptr))
-                if int(stb.download(np.int32, 1)[0]) != 2 ** 31 - 1:
-                    raise ArithmeticError("compute_scaling: an 's' block of s or z is not positive definite")
+            compute_scaling(D, s, z, W, lmbda)
             dg = math.sqrt(kappa / tau)
             dgi = math.sqrt(tau / kappa)
             lmbda_g = math.sqrt(tau * kappa)
@@ -714,29 +790,7 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
         # update (coneprog.py:1336-1436)
         x.axpy(dx, step)
         y.axpy(dy, step)
-        if ind:
-            raise_for(lib().kvx_vec_scal_dev(ind, step, ds.ptr))
-            raise_for(lib().kvx_vec_scal_dev(ind, step, dz.ptr))
-            raise_for(lib().kvx_vec_axpy_dev(ind, 1.0, D.e.ptr, ds.ptr))
-            raise_for(lib().kvx_vec_axpy_dev(ind, 1.0, D.e.ptr, dz.ptr))
-        scale2(D, lmbda.ptr, ds.ptr, inverse="I")
-        scale2(D, lmbda.ptr, dz.ptr, inverse="I")
-        if D.tot1:
-            for sg in (sigs, sigz):
-                sg.scal(step)
-                sg.addc(1.0)
-                raise_for(lib().kvx_nt_sinv_dev(D.tot1, sg.ptr, lmbda.ptr + 8 * ind))     # blas.tbsv(lmbda, sig, k = 0)
-            raise_for(lib().kvx_nts_colscale_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, ds.ptr + 8 * ind, sigs.ptr))
-            raise_for(lib().kvx_nts_colscale_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, dz.ptr + 8 * ind, sigz.ptr))
-        # misc.update_scaling (misc.py:422-634)
-        if D.ml:
-            raise_for(lib().kvx_nt_update_scaling_dev(D.ml, ds.ptr, dz.ptr, W.d.ptr, W.di.ptr, lmbda.ptr))
-        if D.nq:
-            raise_for(lib().kvx_ntq_update_scaling_dev(D.nq, D.d_qoff.ptr, ds.ptr + 8 * D.ml, dz.ptr + 8 * D.ml, W.v.ptr, W.beta.ptr,
-                                                       lmbda.ptr + 8 * D.ml))
-        if D.tot2:
-            raise_for(lib().kvx_nts_update_scaling_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, ds.ptr + 8 * ind, dz.ptr + 8 * ind, W.r.ptr,
-                                                       W.rti.ptr, lmbda.ptr + 8 * ind, D.work.ptr))
+        step_and_update_scaling(D, W, lmbda, ds, dz, sigs, sigz, step)
         dg *= math.sqrt(1.0 - step * tk) / math.sqrt(1.0 - step * tt)
         dgi = 1.0 / dg
         lmbda_g *= math.sqrt(1.0 - step * tt) * math.sqrt(1.0 - step * tk)
@@ -746,4 +800,293 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
         scale(D, W, z.ptr, inverse="I")
         kappa, tau = lmbda_g / dgi, lmbda_g * dgi
         gap = (math.sqrt(lmbda.dot(lmbda)) / tau) ** 2
+    raise AssertionError("unreachable")
+
+
+def lower_ccs(M, n, name="P"):
+    """Lower triangle (i >= j) of an n x n matrix (dense `matrix` or 2-D numpy array: every entry of the triangle stored; or an
+    spmatrix) as CCS; what lies above the diagonal is ignored, as the reference's symmetric kernels ignore it."""
+    from .misc import _full_pattern
+    if isinstance(M, np.ndarray):
+        M = base.matrix(np.asarray(M, dtype=np.float64).reshape(M.shape[0], -1))
+    return _lower_ccs(_full_pattern(M), n, name)
+
+
+def coneqp(P, q, G, h, dims, A=None, b=None, initvals=None, options=None, chol_opts=None):
+    """coneprog.coneqp (coneprog.py:1440-2547) for dims with 'q' / 's' cones, on the GPU:
+
+        minimize (1/2) x'Px + q'x  subject to  G x + s = h,  A x = b,  s in C,
+
+    with the reference's kktsolver='chol' system (coneprog.py:1806-1809, 1969-1981): KKTConeDev with H = P, S = P + Gs' Gs.
+    P: dense or sparse, its lower triangle is used (a dense P with its full lower pattern).  S must be positive definite, i.e.
+    Rank([P; G]) = n (with equality constraints the reference needs that on the null space of A only).  Returns the reference's
+    result dictionary (coneprog.py:2216-2221) with numpy arrays, the 's' blocks of s and z as full symmetric matrices, plus
+    "factorizations"."""
+    _lib.require_device()
+    opts = {"maxiters": 100, "abstol": 1e-7, "reltol": 1e-6, "feastol": 1e-7, "show_progress": False, "use_correction": True}
+    opts.update(options or {})
+    num = (float, int, np.floating, np.integer)
+    correction = opts["use_correction"]
+    MAXITERS, ABSTOL, RELTOL, FEASTOL = opts["maxiters"], opts["abstol"], opts["reltol"], opts["feastol"]
+    if not isinstance(MAXITERS, (int, np.integer)) or MAXITERS < 1:
+        raise ValueError("options['maxiters'] must be a positive integer")
+    if not isinstance(ABSTOL, num):
+        raise ValueError("options['abstol'] must be a scalar")
+    if not isinstance(RELTOL, num):
+        raise ValueError("options['reltol'] must be a scalar")
+    if RELTOL <= 0.0 and ABSTOL <= 0.0:
+        raise ValueError("at least one of options['reltol'] and options['abstol'] must be positive")
+    if not isinstance(FEASTOL, num) or FEASTOL <= 0.0:
+        raise ValueError("options['feastol'] must be a positive scalar")
+    show = opts["show_progress"]
+    if G is None or dims is None:
+        raise NotImplementedError("coneqp without G is not part of the general-cone path")
+    for M in (P, G, A):
+        if callable(M):
+            raise ValueError("use of function valued P, G, A requires a user-provided kktsolver")
+    dims = {"l": dims.get("l", 0), "q": list(dims.get("q") or []), "s": list(dims.get("s") or [])}
+    check_dims(dims)
+    if "refinement" not in opts or opts["refinement"] is None:
+        REFINEMENT = 1 if (dims["q"] or dims["s"]) else 0            # coneprog.py:1862-1865
+    else:
+        REFINEMENT = opts["refinement"]
+        if not isinstance(REFINEMENT, (int, np.integer)) or REFINEMENT < 0:
+            raise ValueError("options['refinement'] must be a nonnegative integer")
+    D = Dims(dims)
+    cdim = D.N
+    if cdim == 0:
+        raise NotImplementedError("coneqp without cone constraints is not part of the general-cone path")
+    q_h = np.ascontiguousarray(np.asarray(base._dense_buffer(q)[0] if not isinstance(q, np.ndarray) else q, dtype=np.float64).reshape(-1))
+    n = q_h.size
+    Pp, Pi, Px = lower_ccs(P, n)
+    h_h = _vec(h, "h", cdim)
+    Gm, Gn, Gp, Gi, Gx = _ccs(G)
+    if (Gm, Gn) != (cdim, n):
+        raise TypeError("'G' must be a 'd' matrix of size (%d, %d)" % (cdim, n))
+    p = 0
+    Ap = Ai = Ax = None
+    if A is not None:
+        p, na, Ap, Ai, Ax = _ccs(A)
+        if na != n:
+            raise TypeError("'A' must be a 'd' matrix with %d columns" % n)
+    b_h = np.zeros(0) if b is None else np.asarray(base._dense_buffer(b)[0] if not isinstance(b, np.ndarray) else b, dtype=np.float64).reshape(-1)
+    if b_h.size != p:
+        raise TypeError("'b' must have length %d" % p)
+    if p > n:
+        raise ValueError("Rank(A) < p or Rank([P; G; A]) < n")        # coneprog.py:1970-1971
+    kkt = KKTConeDev(D, n, Gp, Gi, Gx, p, Ap, Ai, Ax, chol_opts, Pp, Pi, Px)
+    Gd, Pd = kkt.G, SymSpMatDev(n, Pp, Pi, Px)
+    vec = DVec
+    tg = vec(cdim)
+
+    def Gf(u, v, trans="N", alpha=1.0, beta=0.0):                     # misc.sgemv (misc.py:801-833)
+        if trans == "N":
+            Gd.gemv(u, v, trans="N", alpha=alpha, beta=beta)
+        else:
+            tg.copy_from(u)
+            tri(D, tg.ptr, 1)
+            Gd.gemv(tg, v, trans="T", alpha=alpha, beta=beta)
+
+    def Af(u, v, trans="N", alpha=1.0, beta=0.0):                     # base.gemv with A (p x n); p = 0: v := beta v
+        if p:
+            kkt.A.gemv(u, v, trans=trans, alpha=alpha, beta=beta)
+        elif trans == "T" and beta == 0.0:
+            v.fill(0.0)
+        elif trans == "T" and beta != 1.0:
+            v.scal(beta)
+
+    qv, hv, bv = vec(n, q_h), vec(cdim, h_h), vec(p, b_h if p else None)
+    ws3, wz3, dtmp = vec(cdim), vec(cdim), vec(cdim)
+    W = WDev(D)
+    lmbda, lmbdasq = vec(D.Nd), vec(D.Nd)
+
+    def res(ux, uy, uz, us, vx, vy, vz, vs):                          # coneprog.py:1930-1960
+        Pd.symv(ux, vx, alpha=-1.0, beta=1.0)
+        Af(uy, vx, alpha=-1.0, beta=1.0, trans="T")
+        wz3.copy_from(uz)
+        scale(D, W, wz3.ptr, inverse="I")
+        Gf(wz3, vx, alpha=-1.0, beta=1.0, trans="T")
+        Af(ux, vy, alpha=-1.0, beta=1.0)
+        Gf(ux, vz, alpha=-1.0, beta=1.0)
+        ws3.copy_from(us)
+        scale(D, W, ws3.ptr, trans="T")
+        vz.axpy(ws3, -1.0)
+        ws3.copy_from(us)
+        ws3.axpy(uz)
+        sprod(D, ws3.ptr, lmbda.ptr, diag="D")
+        vs.axpy(ws3, -1.0)
+
+    resx0 = max(1.0, math.sqrt(qv.dot(qv)))
+    resy0 = max(1.0, math.sqrt(bv.dot(bv))) if p else 1.0
+    resz0 = max(1.0, snrm2(D, hv.ptr))
+    x, y = vec(n), vec(p)
+    s, z = vec(cdim), vec(cdim)
+    y.fill(0.0)
+
+    def finish(status, iters, gap, relgap, pcost, dcost, pres, dres, msg):
+        tri(D, s.ptr, 0); tri(D, z.ptr, 0)                            # misc.symm of the 's' blocks
+        ts, tz = max_step(D, s.ptr), max_step(D, z.ptr)
+        if show:
+            print(msg)
+        return {"x": x.get(), "y": y.get() if p else np.zeros(0), "s": s.get(), "z": z.get(), "status": status, "gap": gap,
+                "relative gap": relgap, "primal objective": pcost, "dual objective": dcost, "primal infeasibility": pres,
+                "dual infeasibility": dres, "primal slack": -ts, "dual slack": -tz, "iterations": iters,
+                "factorizations": kkt.nfactor}
+
+    # ---- starting point (coneprog.py:2044-2150)
+    if initvals is None:
+        W.identity()
+        try:
+            kkt.factor(W)
+        except ArithmeticError:
+            raise ValueError("Rank(A) < p or Rank([P; A; G]) < n")
+        x.copy_from(qv).scal(-1.0)
+        y.copy_from(bv)
+        z.copy_from(hv)
+        try:
+            kkt.solve(x, y, z)
+        except ArithmeticError:
+            raise ValueError("Rank(A) < p or Rank([P; G; A]) < n")
+        s.copy_from(z).scal(-1.0)
+        nrms = snrm2(D, s.ptr)
+        ts = max_step(D, s.ptr)
+        if ts >= -1e-8 * max(nrms, 1.0):
+            s.axpy(D.e, 1.0 + ts)
+        nrmz = snrm2(D, z.ptr)
+        tz = max_step(D, z.ptr)
+        if tz >= -1e-8 * max(nrmz, 1.0):
+            z.axpy(D.e, 1.0 + tz)
+    else:
+        x.set(_vec(initvals["x"], "initvals['x']", n)) if "x" in initvals else x.fill(0.0)
+        if "s" in initvals:
+            s.set(_vec(initvals["s"], "initvals['s']", cdim))
+            if max_step(D, s.ptr) >= 0:
+                raise ValueError("initial s is not positive")
+        else:
+            s.copy_from(D.e)
+        if "y" in initvals and p:
+            y.set(_vec(initvals["y"], "initvals['y']", p))
+        if "z" in initvals:
+            z.set(_vec(initvals["z"], "initvals['z']", cdim))
+            if max_step(D, z.ptr) >= 0:
+                raise ValueError("initial z is not positive")
+        else:
+            z.copy_from(D.e)
+
+    rx, ry, rz = vec(n), vec(p), vec(cdim)
+    dx, dy = vec(n), vec(p)
+    dz, ds = vec(cdim), vec(cdim)
+    sigs, sigz = vec(D.tot1), vec(D.tot1)
+    if REFINEMENT:
+        wx, wy, wz, ws = vec(n), vec(p), vec(cdim), vec(cdim)
+        wx2, wy2, wz2, ws2 = vec(n), vec(p), vec(cdim), vec(cdim)
+    tmpx = vec(n)
+    gap = sdot(D, s.ptr, z.ptr)
+
+    def f4_no_ir(bx, by_, bz, bs):                                    # coneprog.py:2288-2316
+        sinv(D, bs.ptr, lmbda.ptr)
+        ws3.copy_from(bs)
+        scale(D, W, ws3.ptr, trans="T")
+        bz.axpy(ws3, -1.0)
+        kkt.solve(bx, by_, bz)
+        bs.axpy(bz, -1.0)
+
+    def f4(bx, by_, bz, bs):                                          # coneprog.py:2330-2347
+        if REFINEMENT:
+            wx.copy_from(bx); wy.copy_from(by_); wz.copy_from(bz); ws.copy_from(bs)
+        f4_no_ir(bx, by_, bz, bs)
+        for _ in range(REFINEMENT):
+            wx2.copy_from(wx); wy2.copy_from(wy); wz2.copy_from(wz); ws2.copy_from(ws)
+            res(bx, by_, bz, bs, wx2, wy2, wz2, ws2)
+            f4_no_ir(wx2, wy2, wz2, ws2)
+            bx.axpy(wx2); by_.axpy(wy2); bz.axpy(wz2); bs.axpy(ws2)
+
+    for iters in range(MAXITERS + 1):
+        # f0 = (1/2) x'Px + q'x, rx = Px + q + A'y + G'z, ry = Ax - b, rz = s + Gx - h  (coneprog.py:2169-2186)
+        rx.copy_from(qv)
+        Pd.symv(x, rx, alpha=1.0, beta=1.0)
+        tmpx.copy_from(rx)
+        f0 = 0.5 * (x.dot(tmpx) + x.dot(qv))
+        Af(y, rx, beta=1.0, trans="T")
+        Gf(z, rx, beta=1.0, trans="T")
+        resx = math.sqrt(rx.dot(rx))
+        ry.copy_from(bv)
+        Af(x, ry, alpha=1.0, beta=-1.0)
+        resy = math.sqrt(ry.dot(ry)) if p else 0.0
+        rz.copy_from(s)
+        rz.axpy(hv, -1.0)
+        Gf(x, rz, beta=1.0)
+        resz = snrm2(D, rz.ptr)
+        pcost = f0
+        dcost = f0 + (y.dot(ry) if p else 0.0) + sdot(D, z.ptr, rz.ptr) - gap
+        relgap = gap / -pcost if pcost < 0.0 else (gap / dcost if dcost > 0.0 else None)
+        pres = max(resy / resy0, resz / resz0)
+        dres = resx / resx0
+        if show:
+            if iters == 0:
+                print("% 10s% 12s% 10s% 8s% 7s" % ("pcost", "dcost", "gap", "pres", "dres"))
+            print("%2d: % 8.4e % 8.4e % 4.0e% 7.0e% 7.0e" % (iters, pcost, dcost, gap, pres, dres))
+        if (pres <= FEASTOL and dres <= FEASTOL and (gap <= ABSTOL or (relgap is not None and relgap <= RELTOL))) or iters == MAXITERS:
+            if iters == MAXITERS:
+                return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, "Terminated (maximum number of iterations reached).")
+            return finish("optimal", iters, gap, relgap, pcost, dcost, pres, dres, "Optimal solution found.")
+
+        if iters == 0:
+            compute_scaling(D, s, z, W, lmbda)
+        ssqr(D, lmbdasq.ptr, lmbda.ptr)
+        try:
+            kkt.factor(W)
+        except ArithmeticError:
+            if iters == 0:
+                raise ValueError("Rank(A) < p or Rank([P; A; G]) < n")
+            return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, "Terminated (singular KKT matrix).")
+
+        mu = gap / (D.ml + D.nq + D.tot1)
+        sigma, eta = 0.0, 0.0
+        for i in (0, 1):
+            # ds = -lmbdasq + sigma mu e (i = 0), -lmbdasq - dsa o dza + sigma mu e (i = 1)  (coneprog.py:2376-2392)
+            ds.fill(0.0)
+            if correction and i == 1:
+                ds.axpy(ws3, -1.0)
+            put_diag(D, dtmp, lmbdasq.ptr)
+            ds.axpy(dtmp, -1.0)
+            ds.axpy(D.e, sigma * mu)
+            dx.fill(0.0).axpy(rx, -1.0 + eta)
+            dy.fill(0.0).axpy(ry, -1.0 + eta)
+            dz.fill(0.0).axpy(rz, -1.0 + eta)
+            try:
+                f4(dx, dy, dz, ds)
+            except ArithmeticError:
+                if iters == 0:
+                    raise ValueError("Rank(A) < p or Rank([P; A; G]) < n")
+                return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, "Terminated (singular KKT matrix).")
+            dsdz = sdot(D, ds.ptr, dz.ptr)
+            if correction and i == 0:                                 # ds o dz for the Mehrotra correction
+                ws3.copy_from(ds)
+                sprod(D, ws3.ptr, dz.ptr)
+            # step to the boundary; i = 1: also the eigen-decompositions of the 's' blocks of ds, dz (coneprog.py:2431-2456)
+            scale2(D, lmbda.ptr, ds.ptr)
+            scale2(D, lmbda.ptr, dz.ptr)
+            if i == 0:
+                ts, tz = max_step(D, ds.ptr), max_step(D, dz.ptr)
+            else:
+                ts, tz = max_step(D, ds.ptr, sigma=sigs), max_step(D, dz.ptr, sigma=sigz)
+            t = max([0.0, ts, tz])
+            if t == 0:
+                step = 1.0
+            else:
+                step = min(1.0, 1.0 / t) if i == 0 else min(1.0, STEP / t)
+            if i == 0:
+                sigma = min(1.0, max(0.0, 1.0 - step + dsdz / gap * step ** 2)) ** EXPON
+                eta = 0.0
+
+        # update (coneprog.py:2459-2547)
+        x.axpy(dx, step)
+        y.axpy(dy, step)
+        step_and_update_scaling(D, W, lmbda, ds, dz, sigs, sigz, step)
+        put_diag(D, s, lmbda.ptr)
+        scale(D, W, s.ptr, trans="T")
+        put_diag(D, z, lmbda.ptr)
+        scale(D, W, z.ptr, inverse="I")
+        gap = lmbda.dot(lmbda)
     raise AssertionError("unreachable")

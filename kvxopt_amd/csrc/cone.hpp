@@ -22,9 +22,10 @@ void launch_cone_pq(hipStream_t st, int64_t npairs, const int64_t *ptr, const in
 void launch_cone_gram(hipStream_t st, int64_t ntiles, const int32_t *tblk, const int32_t *ti, const int32_t *tj, const int64_t *yoff,
                       const int64_t *mp, const int64_t *ncol, const int64_t *goff, const double *Y, double *C);
 // Px[e] = sum over the 'q' items of entry e of (4 |v_k|^2 p_a p_b - 2 (p_a q_b + q_a p_b)) / beta_k^2 + sum of its 's' Gram entries
+// (+ Hx[hidx[e]] last when hidx is given and hidx[e] >= 0; hidx == NULL: no H, the operations of the plain assembly)
 void launch_cone_pgather(hipStream_t st, int64_t pnz, const int64_t *qptr, const int32_t *qk, const int64_t *qa, const int64_t *qb,
                          const double *p, const double *q, const double *nv2, const double *beta, const int64_t *sptr,
-                         const int64_t *sidx, const double *C, double *Px);
+                         const int64_t *sidx, const double *C, const int64_t *hidx, const double *Hx, double *Px);
 // x_k(i, j) *= sqrt(w_j) for every 's' block (lower and upper triangle)
 void launch_nts_colscale(hipStream_t st, int64_t ns, const int64_t *off2, const int64_t *off1, double *x, const double *w);
 }  // namespace kvx

@@ -10,6 +10,10 @@
 //   's' block k: Y_k' Y_k with Y_k = pack2 of the congruence rti_k' G_k(:, j) rti_k of every clique column j (misc.py:1271-1272).
 // The 'q' and 's' parts are gathered per entry of the P pattern in a fixed order (cones, then blocks, each by index) into
 // the P values of the kvx_atda assembly: no floating-point atomics, the same bits on every run.
+//
+// kvx_cone_plan_h / kvx_cone_assemble_h_dev: S = H + Gs' Gs with a symmetric H given by its lower CCS pattern (coneqp: H = P,
+// misc.py:1275-1277: K += H; symm(K)).  The P pattern is then the union of the cliques and tril(H), and the same gather adds
+// the H value of an entry last (cones, then blocks, then H); an entry outside the cliques has no other source.
 #include "../../include/kvxhip.h"
 #include "abi_guard.hpp"
 #include "cone.hpp"
@@ -55,13 +59,16 @@ struct kvx_cone {
     std::vector<int64_t> Pp, Pi;
     std::vector<int64_t> qptr, qa, qb, sptr, sidx;
     std::vector<int32_t> qk;
+    bool hasH = false;                          // planned with an H pattern (kvx_cone_plan_h with Hp != NULL)
+    int64_t hnz = 0;                            // entries of the caller's H pattern (both triangles)
+    std::vector<int64_t> hidx;                  // per entry of the P pattern: position of its H value, or -1
     // device
     bool dev = false;
     int64_t *d_lq = nullptr, *d_qoff = nullptr, *d_prptr = nullptr, *d_prpos = nullptr, *d_prvrow = nullptr;
     int32_t *d_rcone = nullptr, *d_prhead = nullptr, *d_qk = nullptr, *d_tblk = nullptr, *d_ti = nullptr, *d_tj = nullptr;
     int64_t *d_dsrc = nullptr, *d_ddst = nullptr, *d_tab = nullptr, *d_f2 = nullptr, *d_f1 = nullptr, *d_fp = nullptr;
     int64_t *d_yoff = nullptr, *d_mp = nullptr, *d_sc = nullptr, *d_goff = nullptr;
-    int64_t *d_qptr = nullptr, *d_qa = nullptr, *d_qb = nullptr, *d_sptr = nullptr, *d_sidx = nullptr;
+    int64_t *d_qptr = nullptr, *d_qa = nullptr, *d_qb = nullptr, *d_sptr = nullptr, *d_sidx = nullptr, *d_hidx = nullptr;
     double *d_w = nullptr, *d_glq = nullptr, *d_nv2 = nullptr, *d_p = nullptr, *d_q = nullptr, *d_D = nullptr, *d_work = nullptr,
            *d_Y = nullptr, *d_C = nullptr, *d_px = nullptr;
     std::vector<void *> owned;
@@ -96,6 +103,7 @@ int cone_device(kvx_cone *C)
     UP(d_prhead, pr_head); UP(d_dsrc, dsrc); UP(d_ddst, ddst); UP(d_tab, tab); UP(d_f2, f2); UP(d_f1, f1); UP(d_fp, fp);
     UP(d_tblk, tblk); UP(d_ti, ti); UP(d_tj, tj); UP(d_yoff, yoff); UP(d_mp, mpv); UP(d_sc, sc); UP(d_goff, goff);
     UP(d_qptr, qptr); UP(d_qk, qk); UP(d_qa, qa); UP(d_qb, qb); UP(d_sptr, sptr); UP(d_sidx, sidx);
+    if (C->hasH) UP(d_hidx, hidx);
 #undef UP
     if ((rc = scratch(C, &C->d_w, C->ml + C->mq)) || (rc = scratch(C, &C->d_glq, (int64_t)C->lq_idx.size())) ||
         (rc = scratch(C, &C->d_nv2, C->nq)) || (rc = scratch(C, &C->d_p, C->npairs)) || (rc = scratch(C, &C->d_q, C->npairs)) ||
@@ -108,8 +116,8 @@ int cone_device(kvx_cone *C)
 
 struct Item {
     int64_t key;        // column * n + row of the entry of S
-    int32_t cone;       // 'q' cone, or -1 for an 's' Gram entry
-    int64_t a, b;       // 'q': indices into p / q;  's': a = index into the Gram buffer
+    int32_t cone;       // 'q' cone, -1 for an 's' Gram entry, -2 for an entry of H
+    int64_t a, b;       // 'q': indices into p / q;  's': a = index into the Gram buffer;  H: a = position in Hx
 };
 
 }  // namespace
@@ -118,7 +126,7 @@ extern "C" {
 
 // misc.py:1213-1277 (kkt_chol: Gs = pack2(W^-T G), K = Gs' Gs) -- the sparsity structure of that product, host only.
 static int kvx_cone_plan_impl(int64_t ml, int64_t nq, const int64_t *q, int64_t ns, const int64_t *s, int64_t n, const int64_t *Gp,
-                              const int64_t *Gi, kvx_cone **out)
+                              const int64_t *Gi, const int64_t *Hp, const int64_t *Hi, kvx_cone **out)
 {
     if (!out || ml < 0 || nq < 0 || ns < 0 || n < 0 || (n > 0 && !Gp) || (nq > 0 && !q) || (ns > 0 && !s)) return KVX_EINVAL;
     *out = nullptr;
@@ -149,6 +157,16 @@ static int kvx_cone_plan_impl(int64_t ml, int64_t nq, const int64_t *q, int64_t 
     for (int64_t p = 0; p < gnz; p++)
         if (Gi[p] < 0 || Gi[p] >= N) { set_last_error("kvx_cone_plan: row index of G out of range"); return KVX_EINVAL; }
     C->gnz = gnz;
+    if (Hp) {
+        if (n && Hp[0] != 0) return KVX_EINVAL;
+        for (int64_t j = 0; j < n; j++)
+            if (Hp[j + 1] < Hp[j]) return KVX_EINVAL;
+        C->hnz = n ? Hp[n] : 0;
+        if (C->hnz > 0 && !Hi) return KVX_EINVAL;
+        for (int64_t p = 0; p < C->hnz; p++)
+            if (Hi[p] < 0 || Hi[p] >= n) { set_last_error("kvx_cone_plan_h: row index of H out of range"); return KVX_EINVAL; }
+        C->hasH = true;
+    }
     C->rcone.resize((size_t)C->mq);
     for (int64_t k = 0; k < nq; k++)
         for (int64_t r = C->qoff[k]; r < C->qoff[k + 1]; r++) C->rcone[r] = (int32_t)k;
@@ -290,6 +308,10 @@ static int kvx_cone_plan_impl(int64_t ml, int64_t nq, const int64_t *q, int64_t 
             for (int64_t a = b; a < c; a++)
                 items.push_back(Item{scol[k][b] * n + scol[k][a], -1, C->goff[k] + a + c * b, 0});
     }
+    if (Hp)                                     // lower triangle of H; what lies above the diagonal is ignored (misc.py:1275-1277)
+        for (int64_t j = 0; j < n; j++)
+            for (int64_t p = Hp[j]; p < Hp[j + 1]; p++)
+                if (Hi[p] >= j) items.push_back(Item{j * n + Hi[p], -2, p, 0});
     std::stable_sort(items.begin(), items.end(), [](const Item &x, const Item &y) { return x.key < y.key; });
     C->Pp.assign((size_t)n + 1, 0);
     C->qptr.push_back(0);
@@ -298,10 +320,14 @@ static int kvx_cone_plan_impl(int64_t ml, int64_t nq, const int64_t *q, int64_t 
         const int64_t key = items[u].key;
         C->Pi.push_back(key % n);
         C->Pp[key / n + 1]++;
+        int64_t hpos = -1;
         for (; u < items.size() && items[u].key == key; u++) {
             if (items[u].cone >= 0) { C->qk.push_back(items[u].cone); C->qa.push_back(items[u].a); C->qb.push_back(items[u].b); }
-            else C->sidx.push_back(items[u].a);
+            else if (items[u].cone == -1) C->sidx.push_back(items[u].a);
+            else if (hpos < 0) hpos = items[u].a;
+            else { set_last_error("kvx_cone_plan_h: the pattern of H holds an entry twice"); return KVX_EINVAL; }
         }
+        if (Hp) C->hidx.push_back(hpos);
         C->qptr.push_back((int64_t)C->qk.size());
         C->sptr.push_back((int64_t)C->sidx.size());
     }
@@ -317,7 +343,13 @@ static int kvx_cone_plan_impl(int64_t ml, int64_t nq, const int64_t *q, int64_t 
 int kvx_cone_plan(int64_t ml, int64_t nq, const int64_t *q, int64_t ns, const int64_t *s, int64_t n, const int64_t *Gp,
                   const int64_t *Gi, kvx_cone **out)
 {
-    return guarded([&] { return kvx_cone_plan_impl(ml, nq, q, ns, s, n, Gp, Gi, out); });
+    return guarded([&] { return kvx_cone_plan_impl(ml, nq, q, ns, s, n, Gp, Gi, nullptr, nullptr, out); });
+}
+
+int kvx_cone_plan_h(int64_t ml, int64_t nq, const int64_t *q, int64_t ns, const int64_t *s, int64_t n, const int64_t *Gp,
+                    const int64_t *Gi, const int64_t *Hp, const int64_t *Hi, kvx_cone **out)
+{
+    return guarded([&] { return kvx_cone_plan_impl(ml, nq, q, ns, s, n, Gp, Gi, Hp, Hi, out); });
 }
 
 int kvx_cone_pattern(kvx_cone *C, int64_t *snz, int64_t *Sp, int64_t *Si)
@@ -327,8 +359,13 @@ int kvx_cone_pattern(kvx_cone *C, int64_t *snz, int64_t *Sp, int64_t *Si)
 }
 
 static int kvx_cone_assemble_impl(kvx_cone *C, const double *Gx, const double *di, const double *v, const double *beta,
-                                  const double *rti, double *Sx)
+                                  const double *rti, const double *Hx, double *Sx)
 {
+    if (C && Hx && !C->hasH) { set_last_error("kvx_cone_assemble_h_dev: the plan has no H pattern"); return KVX_EINVAL; }
+    if (C && C->hasH && C->hnz && !Hx) {
+        set_last_error("kvx_cone_assemble_dev: the plan has an H pattern, its values go through kvx_cone_assemble_h_dev");
+        return KVX_EINVAL;
+    }
     if (!C || !Sx || (C->gnz && !Gx) || (C->ml && !di) || (C->nq && (!v || !beta)) || (C->dtot && !rti)) return KVX_EINVAL;
     int rc = cone_device(C);
     if (rc) return rc;
@@ -356,7 +393,8 @@ static int kvx_cone_assemble_impl(kvx_cone *C, const double *Gx, const double *d
         launch_cone_gram(nullptr, (int64_t)C->tblk.size(), C->d_tblk, C->d_ti, C->d_tj, C->d_yoff, C->d_mp, C->d_sc, C->d_goff, C->d_Y, C->d_C);
     }
     const int64_t pnz = (int64_t)C->Pi.size();
-    launch_cone_pgather(nullptr, pnz, C->d_qptr, C->d_qk, C->d_qa, C->d_qb, C->d_p, C->d_q, C->d_nv2, beta, C->d_sptr, C->d_sidx, C->d_C, C->d_px);
+    launch_cone_pgather(nullptr, pnz, C->d_qptr, C->d_qk, C->d_qa, C->d_qb, C->d_p, C->d_q, C->d_nv2, beta, C->d_sptr, C->d_sidx, C->d_C,
+                        C->hasH && C->hnz ? C->d_hidx : nullptr, Hx, C->d_px);
     HIPCHK(hipGetLastError());
     return kvx_atda_assemble_dev(C->T, C->d_glq, C->d_w, pnz ? C->d_px : nullptr, Sx);
 }
@@ -364,7 +402,13 @@ static int kvx_cone_assemble_impl(kvx_cone *C, const double *Gx, const double *d
 int kvx_cone_assemble_dev(kvx_cone *C, const double *Gx_dev, const double *di_dev, const double *v_dev, const double *beta_dev,
                           const double *rti_dev, double *Sx_dev)
 {
-    return guarded([&] { return kvx_cone_assemble_impl(C, Gx_dev, di_dev, v_dev, beta_dev, rti_dev, Sx_dev); });
+    return guarded([&] { return kvx_cone_assemble_impl(C, Gx_dev, di_dev, v_dev, beta_dev, rti_dev, nullptr, Sx_dev); });
+}
+
+int kvx_cone_assemble_h_dev(kvx_cone *C, const double *Gx_dev, const double *di_dev, const double *v_dev, const double *beta_dev,
+                            const double *rti_dev, const double *Hx_dev, double *Sx_dev)
+{
+    return guarded([&] { return kvx_cone_assemble_impl(C, Gx_dev, di_dev, v_dev, beta_dev, rti_dev, Hx_dev, Sx_dev); });
 }
 
 void kvx_cone_free(kvx_cone *C)

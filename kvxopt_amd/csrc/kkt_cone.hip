@@ -117,10 +117,14 @@ __global__ __launch_bounds__(256) void k_cone_gram(int64_t ntiles, const int32_t
     }
 }
 
+// HAS_H: the entry's value of H (hidx[e] >= 0: its position in Hx) is added last -- cones, then blocks, then H.  Without it the
+// floating-point operations and their order are those of the plain assembly.
+template <bool HAS_H>
 __global__ void k_cone_pgather(int64_t pnz, const int64_t *__restrict__ qptr, const int32_t *__restrict__ qk, const int64_t *__restrict__ qa,
                                const int64_t *__restrict__ qb, const double *__restrict__ p, const double *__restrict__ q,
                                const double *__restrict__ nv2, const double *__restrict__ beta, const int64_t *__restrict__ sptr,
-                               const int64_t *__restrict__ sidx, const double *__restrict__ C, double *__restrict__ Px)
+                               const int64_t *__restrict__ sidx, const double *__restrict__ C, const int64_t *__restrict__ hidx,
+                               const double *__restrict__ Hx, double *__restrict__ Px)
 {
     CONE_LOOP(e, pnz) {
         double acc = 0.0;
@@ -131,6 +135,10 @@ __global__ void k_cone_pgather(int64_t pnz, const int64_t *__restrict__ qptr, co
             acc += (4.0 * nv2[k] * pa * pb - 2.0 * (pa * qb_ + qa_ * pb)) / (bk * bk);
         }
         for (int64_t u = sptr[e]; u < sptr[e + 1]; u++) acc += C[sidx[u]];
+        if (HAS_H) {
+            const int64_t hp = hidx[e];
+            if (hp >= 0) acc += Hx[hp];
+        }
         Px[e] = acc;
     }
 }
@@ -173,10 +181,15 @@ void launch_cone_gram(hipStream_t st, int64_t ntiles, const int32_t *tblk, const
 
 void launch_cone_pgather(hipStream_t st, int64_t pnz, const int64_t *qptr, const int32_t *qk, const int64_t *qa, const int64_t *qb,
                          const double *p, const double *q, const double *nv2, const double *beta, const int64_t *sptr,
-                         const int64_t *sidx, const double *C, double *Px)
+                         const int64_t *sidx, const double *C, const int64_t *hidx, const double *Hx, double *Px)
 {
-    if (pnz > 0)
-        hipLaunchKernelGGL(k_cone_pgather, dim3(grid_of(pnz)), dim3(256), 0, st, pnz, qptr, qk, qa, qb, p, q, nv2, beta, sptr, sidx, C, Px);
+    if (pnz <= 0) return;
+    if (hidx)
+        hipLaunchKernelGGL(k_cone_pgather<true>, dim3(grid_of(pnz)), dim3(256), 0, st, pnz, qptr, qk, qa, qb, p, q, nv2, beta, sptr, sidx, C,
+                           hidx, Hx, Px);
+    else
+        hipLaunchKernelGGL(k_cone_pgather<false>, dim3(grid_of(pnz)), dim3(256), 0, st, pnz, qptr, qk, qa, qb, p, q, nv2, beta, sptr, sidx, C,
+                           hidx, Hx, Px);
 }
 
 void launch_nts_colscale(hipStream_t st, int64_t ns, const int64_t *off2, const int64_t *off1, double *x, const double *w)

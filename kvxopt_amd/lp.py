@@ -1222,12 +1222,12 @@ class SymSpMatDev:
         self.strict.gemv(x, y, trans="T", alpha=alpha, beta=1.0)
 
 
-def _lower_ccs(P, n):
+def _lower_ccs(P, n, name="P"):
     """Lower triangle (i >= j) of a spmatrix-like P as sorted CCS; entries above the diagonal are ignored, as the
     reference's symmetric kernels do."""
     m, n2, Pp, Pi, Px = base._as_ccs(P)
     if m != n or n2 != n:
-        raise TypeError("'P' must be a 'd' matrix of size (%d, %d)" % (n, n))
+        raise TypeError("'%s' must be a 'd' matrix of size (%d, %d)" % (name, n, n))
     Pp = np.asarray(Pp, dtype=np.int64); Pi = np.asarray(Pi, dtype=np.int64); Px = np.asarray(Px, dtype=np.float64)
     cols = np.repeat(np.arange(n, dtype=np.int64), np.diff(Pp))
     keep = Pi >= cols

@@ -656,14 +656,17 @@ def kkt_chol(G, dims, A, mnl=0):
     """KKT solver factory of the reference for general cones (misc.py:1213-1349): returns factor(W, H=None, Df=None), which
     returns solve(x, y, z) overwriting (bx, by, bz) with (ux, uy, W uz) of
 
-        [ 0   A'  G'   ] [ux]   [bx]
-        [ A   0   0    ] [uy] = [by],
+        [ H   A'  G'   ] [ux]   [bx]
+        [ A   0   0    ] [uy] = [by],      H = 0 for cone LPs, H = P for coneqp
         [ G   0  -W'W  ] [uz]   [bz]
 
-    with S = Gs' Gs, Gs = pack2(W^-T G), assembled on the fixed pattern of the cliques of the 'l' rows, 'q' cones and 's' blocks
-    (kvx_cone_assemble_dev) and factored by the sparse Cholesky on one analysis; p > 0 is eliminated with K = A S^-1 A' (the
-    reference uses a QR factorisation of A' there: the same solution, other roundings).  Host vectors in and out, arithmetic on
-    the device.  The nonlinear block (mnl > 0), H and Df are not part of this path."""
+    with S = H + Gs' Gs, Gs = pack2(W^-T G), assembled on the fixed pattern of the cliques of the 'l' rows, 'q' cones and 's'
+    blocks united with the lower pattern of H (kvx_cone_assemble_dev / kvx_cone_assemble_h_dev) and factored by the sparse
+    Cholesky on one analysis; p > 0 is eliminated with K = A S^-1 A' (the reference uses a QR factorisation of A' there: the same
+    solution, other roundings).  H: dense `matrix`, spmatrix or 2-D numpy array, its lower triangle is used (misc.py:1275-1277).
+    The first call fixes the pattern of H; a later call with the same pattern refreshes its values only, one with another pattern
+    (or H appearing or disappearing) builds a new plan and analysis.  Host vectors in and out, arithmetic on the device.  The
+    nonlinear block (mnl > 0) and Df are not part of this path."""
     from . import cone, lp
     if mnl:
         raise NotImplementedError("misc.kkt_chol on the GPU: the nonlinear block (mnl > 0) is not supported")
@@ -671,16 +674,23 @@ def kkt_chol(G, dims, A, mnl=0):
     D = cone.Dims(dims)
     _, n, Gp, Gi, Gx = cone._ccs(G)
     p, _, Ap, Ai, Ax = cone._ccs(A)
-    state = {"kkt": None, "W": None}
+    state = {"kkt": None, "W": None, "hpat": None}
 
     def factor(W, H=None, Df=None):
-        if H is not None or Df is not None:
-            raise NotImplementedError("misc.kkt_chol on the GPU: H and Df (coneqp / cvxprog) are not supported")
+        if Df is not None:
+            raise NotImplementedError("misc.kkt_chol on the GPU: Df (cvxprog) is not supported")
         _lib.require_device()
-        if state["kkt"] is None:
-            state["kkt"] = cone.KKTConeDev(D, n, Gp, Gi, Gx, p, Ap, Ai, Ax)
+        Hp = Hi = Hx = hpat = None
+        if H is not None:
+            Hp, Hi, Hx = cone.lower_ccs(H, n, "H")
+            hpat = (Hp.tobytes(), Hi.tobytes())
+        if state["kkt"] is None or hpat != state["hpat"]:
+            state["kkt"] = cone.KKTConeDev(D, n, Gp, Gi, Gx, p, Ap, Ai, Ax, None, Hp, Hi, Hx)
+            state["hpat"] = hpat
             state["W"] = cone.WDev(D)
             state["x"], state["y"], state["z"] = lp.DVec(n), lp.DVec(p), lp.DVec(D.N)
+        elif H is not None:
+            state["kkt"].set_hessian(Hx)
         state["W"].set_host(W)
         state["kkt"].factor(state["W"])
 

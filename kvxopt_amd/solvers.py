@@ -5,7 +5,8 @@
                                                                                      has 'q' or 's' blocks, coneprog.py:459, 504)
     socp(c, Gl, hl, Gq, hq, A=None, b=None, primalstart=None, dualstart=None)        coneprog.py:3044
     sdp(c, Gl, hl, Gs, hs, A=None, b=None, primalstart=None, dualstart=None)         coneprog.py:3597
-    coneqp(P, q, G, h, dims=None, A=None, b=None, initvals=None)                     coneprog.py:1440
+    coneqp(P, q, G, h, dims=None, A=None, b=None, initvals=None)                     coneprog.py:1440 (-> cone.coneqp when dims
+                                                                                     has 'q' or 's' blocks, coneprog.py:1806-1807)
     lp(c, G, h, A=None, b=None, primalstart=None, dualstart=None)                    coneprog.py:2551 (-> conelp)
     qp(P, q, G, h, A=None, b=None, initvals=None)                                    coneprog.py:4120 (-> coneqp)
     options                                                                          the module-level dict of the reference
@@ -13,8 +14,9 @@
 Like the reference, algorithm parameters come from `solvers.options` ('maxiters', 'abstol', 'reltol', 'feastol',
 'refinement', 'show_progress'); a keyword `options=` overrides it per call.  `conelp / lp / coneqp / qp (..., kktsolver=f)`
 take the reference's plug-in, a function `W -> g(x, y, z)` (coneprog.py:323-344, 1969-1981; host round trips per factorisation
-and solve, lp.KKTUserHost); the named solvers ('ldl', 'ldl2', 'qr', 'chol', 'chol2') and `solver=` (external codes) are not part of
-this path and raise.
+and solve, lp.KKTUserHost) on the orthant; with 'q' / 's' cones the KKT system is misc.kkt_chol on the GPU (for coneqp with H = P)
+and any `kktsolver` raises.  The named solvers ('ldl', 'ldl2', 'qr', 'chol', 'chol2') and `solver=` (external codes) are not part
+of this path and raise.  coneqp reads 'use_correction' as well.
 """
 import numpy as np
 
@@ -57,7 +59,10 @@ def conelp(c, G, h, dims=None, A=None, b=None, primalstart=None, dualstart=None,
 def coneqp(P, q, G, h, dims=None, A=None, b=None, initvals=None, **kw):
     k = _kkt(kw)
     if dims is not None and (dims.get("q") or dims.get("s")):
-        raise NotImplementedError("only the orthant cone runs on the GPU")
+        # the reference's default for these cones (coneprog.py:1806-1807): misc.kkt_chol with H = P, on the GPU
+        if k is not None:
+            raise NotImplementedError("coneqp with 'q' / 's' cones runs misc.kkt_chol on the GPU; kktsolver is not selectable")
+        return _cone.coneqp(P, q, G, h, dims, A=A, b=b, initvals=initvals, options=_opts(kw))
     return _lp.coneqp(P, q, G, h, _opts(kw), None, A=A, b=b, initvals=initvals, kktsolver=k)
 
 

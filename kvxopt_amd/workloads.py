@@ -248,3 +248,33 @@ def sdp_box(n, blocks, density=0.3, seed=32):
         G.append(F.reshape(m * m, n, order="F"))
         h.append((m * np.eye(m)).reshape(-1, order="F"))
     return rng.standard_normal(n), np.vstack(G), np.concatenate(h), {"l": ml, "q": [], "s": list(blocks)}
+
+
+def path_laplacian_psd(n, seed, weight=1.0, shift=1e-3):
+    """Sparse positive definite P = L + shift I, L the Laplacian of the path 0 - 1 - ... - (n - 1) with edge weights
+    `weight` U(0.5, 1.5) (default_rng(seed)); lower CCS (colptr, rowind, values)."""
+    w = weight * np.random.default_rng(seed).uniform(0.5, 1.5, max(n - 1, 0))
+    d = np.full(n, float(shift))
+    d[:-1] += w
+    d[1:] += w
+    cp = np.minimum(2 * np.arange(n + 1, dtype=np.int64), 2 * n - 1) if n else np.zeros(1, dtype=np.int64)
+    ri = np.empty(max(2 * n - 1, 0), dtype=np.int64)
+    vx = np.empty(max(2 * n - 1, 0))
+    ri[0::2], vx[0::2] = np.arange(n), d
+    ri[1::2], vx[1::2] = np.arange(1, n), -w
+    return cp, ri, vx
+
+
+def socp_qp_sum_of_norms(nx, ncones, order=4, nnz_row=3, seed=31, weight=1.0, shift=1e-3):
+    """`socp_sum_of_norms` with a quadratic term: minimize (1/2) u'Pu + c'u over u = (x, t), P = path_laplacian_psd over all
+    nx + ncones variables (neighbouring variables are coupled whether or not a cone couples them, so the pattern of P is not
+    inside the cliques of G).  Returns ((Pp, Pi, Px), q, G as (N, n, colptr, rowind, values), h, dims)."""
+    c, G, h, dims = socp_sum_of_norms(nx, ncones, order, nnz_row, seed)
+    return path_laplacian_psd(nx + ncones, seed + 1000, weight, shift), c, G, h, dims
+
+
+def sdp_qp_box(n, blocks, density=0.3, seed=32, weight=1.0, shift=1e-3):
+    """`sdp_box` with a quadratic term: minimize (1/2) x'Px + c'x, P = path_laplacian_psd(n).
+    Returns ((Pp, Pi, Px), q, G dense (N x n), h, dims)."""
+    c, G, h, dims = sdp_box(n, blocks, density, seed)
+    return path_laplacian_psd(n, seed + 1000, weight, shift), c, G, h, dims
