@@ -259,6 +259,54 @@ def _dense_buffer(B, tc="d"):
     return arr.reshape(-1, order="F") if arr.ndim == 2 else arr, size
 
 
+def flat(v):
+    """A dense vector or matrix (ours, kvxopt's, a numpy array or a sequence) as one contiguous float64 vector, column by column."""
+    if isinstance(v, matrix):
+        a = v._a
+    elif isinstance(v, (np.ndarray, list, tuple)):
+        a = np.asarray(v, dtype=np.float64).reshape(-1, order="F")
+    else:
+        a = _dense_buffer(v)[0]
+    return np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+
+
+# ---- the one conversion family to CCS: dense-or-sparse (a dense matrix keeps every entry) and lower-triangle extraction ----
+def _full_pattern(M, lower=False):
+    """A dense `matrix` as an spmatrix with every entry (or every entry of the lower triangle) stored; anything else unchanged."""
+    if not isinstance(M, matrix):
+        return M
+    r, c = M.size
+    D = np.asarray(M.a, dtype=np.float64).reshape(r, c)
+    if lower:
+        I, J = np.nonzero(np.tril(np.ones((r, c), dtype=bool)).T)       # column by column
+        I, J = J, I
+        return spmatrix(D[I, J], I, J, (r, c))
+    return spmatrix.from_ccs(r, c, np.arange(c + 1, dtype=np.int64) * r, np.tile(np.arange(r, dtype=np.int64), c),
+                             np.ascontiguousarray(D.T).reshape(-1))
+
+
+def ccs(M):
+    """(nrows, ncols, colptr, rowind, values) of a dense or sparse matrix (ours or kvxopt's, or a 2-D numpy array); a dense
+    matrix keeps every entry."""
+    if isinstance(M, np.ndarray):
+        M = matrix(np.asarray(M, dtype=np.float64).reshape(M.shape[0], -1))
+    m, n, cp, ri, v = _as_ccs(_full_pattern(M))
+    return m, n, np.ascontiguousarray(cp, dtype=np.int64), np.ascontiguousarray(ri, dtype=np.int64), np.ascontiguousarray(v, dtype=np.float64)
+
+
+def lower_ccs(M, n, name="P"):
+    """(colptr, rowind, values) of the lower triangle (i >= j) of an n x n matrix (as for `ccs`); what lies above the diagonal
+    is ignored, as the reference's symmetric kernels ignore it."""
+    m, n2, cp, ri, v = ccs(M)
+    if m != n or n2 != n:
+        raise TypeError("'%s' must be a 'd' matrix of size (%d, %d)" % (name, n, n))
+    cols = np.repeat(np.arange(n, dtype=np.int64), np.diff(cp))
+    keep = ri >= cols
+    lp_ = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cols[keep], minlength=n), out=lp_[1:])
+    return lp_, ri[keep].copy(), v[keep].copy()
+
+
 # --------------------------------------------------------------------------------------------
 # sparse BLAS on the GPU
 _plans = {}

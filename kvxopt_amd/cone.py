@@ -20,256 +20,18 @@ import time
 
 import numpy as np
 
-from . import _lib, base
-from ._lib import DeviceBuffer, lib, raise_for
+from . import _ipm, _lib
+from ._lib import lib, raise_for
+from .base import ccs as _ccs, lower_ccs
 from .chol import Factor
-from .lp import DVec, SpMatDev, SymSpMatDev, _lower_ccs, dense_schur
+from .coneops import (Dims, WDev, compute_scaling as _compute_scaling, max_step, put_diag, scale, scale2, sdot, sinv, snrm2,
+                      sprod, ssqr, step_and_update_scaling, tri)
+from .devvec import DVec, SpMatDev, SymSpMatDev
+from .lp import dense_schur
 
 EXPON = 3          # coneprog.py:423
 STEP = 0.99        # coneprog.py:424
 
-
-def _i64dev(a):
-    a = np.ascontiguousarray(a, dtype=np.int64)
-    return DeviceBuffer.from_array(a) if a.size else DeviceBuffer(8)
-
-
-class Dims:
-    """Offsets of the blocks of a cone vector and the device tables of the kvx_ntq_* / kvx_nts_* entries."""
-
-    def __init__(self, dims):
-        self.ml = int(dims["l"])
-        self.q = [int(k) for k in dims["q"]]
-        self.s = [int(k) for k in dims["s"]]
-        self.nq, self.ns = len(self.q), len(self.s)
-        self.mq = sum(self.q)
-        self.ind = self.ml + self.mq                                   # start of the 's' section
-        self.tot2 = sum(m * m for m in self.s)
-        self.tot1 = sum(self.s)
-        self.N = self.ind + self.tot2                                  # cdim
-        self.Nd = self.ind + self.tot1                                 # cdim_diag
-        self.Np = self.ind + sum(m * (m + 1) // 2 for m in self.s)     # cdim_pckd
-        qoff = np.zeros(self.nq + 1, dtype=np.int64)
-        np.cumsum(np.asarray(self.q, dtype=np.int64), out=qoff[1:])
-        self.qoff = qoff
-        self.d_qoff = _i64dev(qoff)
-        sd = np.asarray(self.s, dtype=np.int64)
-        self.off2 = np.zeros(self.ns + 1, dtype=np.int64)
-        self.off1 = np.zeros(self.ns + 1, dtype=np.int64)
-        np.cumsum(sd * sd, out=self.off2[1:])
-        np.cumsum(sd, out=self.off1[1:])
-        self.d_off2, self.d_off1 = _i64dev(self.off2), _i64dev(self.off1)
-        # identity e: 1 on the 'l' entries, the heads of the 'q' cones and the diagonals of the 's' blocks
-        e = np.zeros(self.N)
-        e[:self.ml] = 1.0
-        e[self.ml + qoff[:-1]] = 1.0
-        self.sdiag = np.concatenate([self.off2[k] + np.arange(m) * (m + 1) for k, m in enumerate(self.s)]).astype(np.int64) \
-            if self.tot1 else np.zeros(0, dtype=np.int64)
-        e[self.ind + self.sdiag] = 1.0
-        self.e = DVec(self.N, e)
-        self.d_sdiag = _i64dev(self.sdiag)
-        self.work = DVec(max(4 * self.tot2, 3 * self.tot2 + 2 * self.tot1, 1))
-        self.out = DVec(max(self.ns, self.nq, 1))
-
-    def key(self):
-        return (self.ml, tuple(self.q), tuple(self.s))
-
-
-class WDev:
-    """The Nesterov-Todd scaling W in HBM: d, di ('l'), v (the 'q' vectors back to back), beta (nq), r, rti (the 's' blocks)."""
-
-    def __init__(self, D):
-        self.D = D
-        self.d, self.di = DVec(D.ml), DVec(D.ml)
-        self.v, self.beta = DVec(D.mq), DVec(D.nq)
-        self.r, self.rti = DVec(D.tot2), DVec(D.tot2)
-
-    def identity(self):
-        """W = I (coneprog.py:662-672)."""
-        D = self.D
-        self.d.fill(1.0); self.di.fill(1.0)
-        v = np.zeros(D.mq)
-        v[D.qoff[:-1]] = 1.0
-        self.v.set(v); self.beta.fill(1.0)
-        r = np.zeros(D.tot2)
-        r[D.sdiag] = 1.0
-        self.r.set(r); self.rti.set(r)
-
-    def set_host(self, W):
-        """From the reference's dictionary W (host matrices)."""
-        D = self.D
-        cat = lambda xs: np.concatenate([np.asarray(base._dense_buffer(x)[0], dtype=np.float64) for x in xs]) if xs else np.zeros(0)
-        if D.ml:
-            self.d.set(base._dense_buffer(W["d"])[0]); self.di.set(base._dense_buffer(W["di"])[0])
-        if D.nq:
-            self.v.set(cat(W["v"])); self.beta.set(np.asarray(W["beta"], dtype=np.float64))
-        if D.tot2:
-            self.r.set(cat(W["r"])); self.rti.set(cat(W["rti"]))
-
-
-# ---- the operations of misc on device vectors (pointer + the layout of Dims) -------------------------------------------------
-def scale(D, W, xp, trans="N", inverse="N"):
-    """misc.scale (misc_solvers.c:85-240) of one vector at xp."""
-    inv = inverse != "N"
-    if D.ml:
-        raise_for(lib().kvx_nt_scale_dev(D.ml, 1, D.N, xp, (W.di if inv else W.d).ptr))
-    if D.nq:
-        raise_for(lib().kvx_ntq_scale_dev(D.nq, D.d_qoff.ptr, W.v.ptr, W.beta.ptr, xp + 8 * D.ml, D.N, 1, 1 if inv else 0))
-    if D.tot2:
-        R = W.rti if inv else W.r
-        form = 1 if (inverse == "N") == (trans == "T") else 0
-        raise_for(lib().kvx_nts_scale_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, R.ptr, xp + 8 * D.ind, D.N, 1, form, D.work.ptr, D.tot2))
-
-
-def scale2(D, lp_, xp, inverse="N"):
-    """misc.scale2 (misc_solvers.c:256-397); lp_: lmbda (cdim_diag layout)."""
-    inv = 1 if inverse == "I" else 0
-    if D.ml:
-        raise_for(lib().kvx_nt_scale2_dev(D.ml, lp_, xp, inv))
-    if D.nq:
-        raise_for(lib().kvx_ntq_scale2_dev(D.nq, D.d_qoff.ptr, lp_ + 8 * D.ml, xp + 8 * D.ml, inv))
-    if D.tot2:
-        raise_for(lib().kvx_nts_scale2_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, lp_ + 8 * D.ind, xp + 8 * D.ind, inv))
-
-
-def sprod(D, xp, yp, diag="N"):
-    """misc.sprod (misc_solvers.c:634-770): x := y o x; diag 'D': the 's' part of y holds diagonals only."""
-    if D.ml:
-        raise_for(lib().kvx_nt_sprod_dev(D.ml, xp, yp))
-    if D.nq:
-        raise_for(lib().kvx_ntq_prod_dev(D.nq, D.d_qoff.ptr, xp + 8 * D.ml, yp + 8 * D.ml, 0))
-    if D.tot2:
-        if diag == "N":
-            raise_for(lib().kvx_nts_prod_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, xp + 8 * D.ind, yp + 8 * D.ind, 0, D.work.ptr))
-        else:
-            raise_for(lib().kvx_nts_prod_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, xp + 8 * D.ind, yp + 8 * D.ind, 1, None))
-
-
-def sinv(D, xp, yp):
-    """misc.sinv (misc_solvers.c:775-882), y in the cdim_diag layout."""
-    if D.ml:
-        raise_for(lib().kvx_nt_sinv_dev(D.ml, xp, yp))
-    if D.nq:
-        raise_for(lib().kvx_ntq_prod_dev(D.nq, D.d_qoff.ptr, xp + 8 * D.ml, yp + 8 * D.ml, 1))
-    if D.tot2:
-        raise_for(lib().kvx_nts_prod_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, xp + 8 * D.ind, yp + 8 * D.ind, 2, None))
-
-
-def ssqr(D, xp, yp):
-    """misc.ssqr (misc.py:945-959), both in the cdim_diag layout."""
-    if D.ml:
-        raise_for(lib().kvx_nt_ssqr_dev(D.ml, xp, yp))
-    if D.nq:
-        raise_for(lib().kvx_ntq_prod_dev(D.nq, D.d_qoff.ptr, xp + 8 * D.ml, yp + 8 * D.ml, 2))
-    if D.tot1:
-        raise_for(lib().kvx_nt_ssqr_dev(D.tot1, xp + 8 * D.ind, yp + 8 * D.ind))
-
-
-def sdot(D, xp, yp):
-    """misc.sdot (misc_solvers.c:991-1046)."""
-    a = 0.0
-    if D.ind:
-        r = ctypes.c_double()
-        raise_for(lib().kvx_nt_sdot_dev(D.ind, xp, yp, ctypes.byref(r)))
-        a = r.value
-    if D.tot2:
-        raise_for(lib().kvx_nts_dot_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, xp + 8 * D.ind, yp + 8 * D.ind, D.out.ptr))
-        for v in D.out.get()[:D.ns]:
-            a += float(v)
-    return a
-
-
-def snrm2(D, xp):
-    return math.sqrt(sdot(D, xp, xp))
-
-
-def max_step(D, xp, sigma=None):
-    """misc.max_step (misc_solvers.c:1052-1160); with sigma (a DVec of sum(dims['s'])) the eigenvalues of the 's' blocks are
-    stored there and their eigenvectors replace the blocks of x."""
-    if D.ind + D.tot2 == 0:
-        return 0.0
-    t = -np.finfo(np.float32).max
-    if D.ml:
-        r = ctypes.c_double()
-        raise_for(lib().kvx_nt_max_step_dev(D.ml, xp, ctypes.byref(r)))
-        t = max(t, r.value)
-    if D.nq:
-        raise_for(lib().kvx_ntq_max_step_dev(D.nq, D.d_qoff.ptr, xp + 8 * D.ml, D.out.ptr))
-        t = max(t, float(D.out.get()[:D.nq].max()))
-    if D.tot2:
-        raise_for(lib().kvx_nts_max_step_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, xp + 8 * D.ind, sigma.ptr if sigma is not None else None,
-                                             D.out.ptr, D.work.ptr))
-        t = max(t, float(D.out.get()[:D.ns].max()))
-    return t
-
-
-def tri(D, xp, mode):
-    """mode 0: misc.symm of every 's' block, 1: trisc, 2: triusc (misc_solvers.c:610-632, 887-988)."""
-    if D.tot2:
-        raise_for(lib().kvx_nts_tri_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, xp + 8 * D.ind, mode))
-
-
-def put_diag(D, dst, srcp):
-    """dst := src ('l' and 'q' entries), 's' blocks := diag(src_k) (coneprog.py:1273-1280, 1413-1421)."""
-    if D.ind:
-        raise_for(lib().kvx_vec_copy_dev(D.ind, srcp, dst.ptr))
-    if D.tot2:
-        raise_for(lib().kvx_vec_fill_dev(D.tot2, 0.0, dst.ptr + 8 * D.ind))
-        raise_for(lib().kvx_vec_scatter_dev(D.tot1, srcp + 8 * D.ind, D.d_sdiag.ptr, dst.ptr + 8 * D.ind))
-
-
-def compute_scaling(D, s, z, W, lmbda):
-    """misc.compute_scaling (misc.py:250-419): W and lmbda from the interior points s, z."""
-    ind = D.ind
-    if D.ml:
-        raise_for(lib().kvx_nt_compute_scaling_dev(D.ml, s.ptr, z.ptr, W.d.ptr, W.di.ptr, lmbda.ptr))
-    if D.nq:
-        raise_for(lib().kvx_ntq_compute_scaling_dev(D.nq, D.d_qoff.ptr, s.ptr + 8 * D.ml, z.ptr + 8 * D.ml, W.v.ptr,
-                                                    W.beta.ptr, lmbda.ptr + 8 * D.ml))
-    if D.tot2:
-        stb = DeviceBuffer.from_array(np.array([2 ** 31 - 1], dtype=np.int32))
-        raise_for(lib().kvx_nts_compute_scaling_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, s.ptr + 8 * ind, z.ptr + 8 * ind,
-                                                    W.r.ptr, W.rti.ptr, lmbda.ptr + 8 * ind, D.work.ptr, stb.ptr))
-        if int(stb.download(np.int32, 1)[0]) != 2 ** 31 - 1:
-            raise ArithmeticError("compute_scaling: an 's' block of s or z is not positive definite")
-
-
-def step_and_update_scaling(D, W, lmbda, ds, dz, sigs, sigz, step):
-    """The end of an iteration (coneprog.py:1336-1431, 2463-2519): ds, dz (scaled by scale2, their 's' blocks replaced by the
-    eigenvectors whose eigenvalues are in sigs, sigz) become the updated iterates in the current scaling, then
-    misc.update_scaling (misc.py:422-634) refreshes W and lmbda."""
-    ind = D.ind
-    if ind:
-        raise_for(lib().kvx_vec_scal_dev(ind, step, ds.ptr))
-        raise_for(lib().kvx_vec_scal_dev(ind, step, dz.ptr))
-        raise_for(lib().kvx_vec_axpy_dev(ind, 1.0, D.e.ptr, ds.ptr))
-        raise_for(lib().kvx_vec_axpy_dev(ind, 1.0, D.e.ptr, dz.ptr))
-    scale2(D, lmbda.ptr, ds.ptr, inverse="I")
-    scale2(D, lmbda.ptr, dz.ptr, inverse="I")
-    if D.tot1:
-        for sg in (sigs, sigz):
-            sg.scal(step)
-            sg.addc(1.0)
-            raise_for(lib().kvx_nt_sinv_dev(D.tot1, sg.ptr, lmbda.ptr + 8 * ind))     # blas.tbsv(lmbda, sig, k = 0)
-        raise_for(lib().kvx_nts_colscale_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, ds.ptr + 8 * ind, sigs.ptr))
-        raise_for(lib().kvx_nts_colscale_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, dz.ptr + 8 * ind, sigz.ptr))
-    if D.ml:
-        raise_for(lib().kvx_nt_update_scaling_dev(D.ml, ds.ptr, dz.ptr, W.d.ptr, W.di.ptr, lmbda.ptr))
-    if D.nq:
-        raise_for(lib().kvx_ntq_update_scaling_dev(D.nq, D.d_qoff.ptr, ds.ptr + 8 * D.ml, dz.ptr + 8 * D.ml, W.v.ptr, W.beta.ptr,
-                                                   lmbda.ptr + 8 * D.ml))
-    if D.tot2:
-        raise_for(lib().kvx_nts_update_scaling_dev(D.ns, D.d_off2.ptr, D.d_off1.ptr, ds.ptr + 8 * ind, dz.ptr + 8 * ind, W.r.ptr,
-                                                   W.rti.ptr, lmbda.ptr + 8 * ind, D.work.ptr))
-
-
-def _ccs(M):
-    """CCS of a dense or sparse matrix (ours or kvxopt's, or a 2-D numpy array); a dense matrix keeps every entry."""
-    from .misc import _full_pattern
-    if isinstance(M, np.ndarray):
-        M = base.matrix(np.asarray(M, dtype=np.float64).reshape(M.shape[0], -1))
-    m, n, cp, ri, v = base._as_ccs(_full_pattern(M))
-    return m, n, np.ascontiguousarray(cp, dtype=np.int64), np.ascontiguousarray(ri, dtype=np.int64), np.ascontiguousarray(v, dtype=np.float64)
 
 
 class ConePlan:
@@ -418,90 +180,33 @@ class KKTConeDev:
         z.copy_from(self.u)
 
 
-def _vec(v, name, size):
-    a = np.ascontiguousarray(np.asarray(base._dense_buffer(v)[0] if not isinstance(v, np.ndarray) else v, dtype=np.float64).reshape(-1))
-    if a.size != size:
-        raise TypeError("'%s' must be a 'd' matrix of size (%d,1)" % (name, size))
-    return a
+_vec = _ipm.vector
+
+
+def compute_scaling(D, s, z, W, lmbda):
+    if _compute_scaling(D, s, z, W, lmbda) is not None:
+        raise ArithmeticError("compute_scaling: an 's' block of s or z is not positive definite")
 
 
 def check_dims(dims, h_size=None):
     """coneprog.py:499-521: the dims checks and their TypeErrors."""
-    if not isinstance(dims.get("l"), (int, np.integer)) or dims["l"] < 0:
-        raise TypeError("'dims['l']' must be a nonnegative integer")
-    if [k for k in dims.get("q", []) if not isinstance(k, (int, np.integer)) or k < 1]:
-        raise TypeError("'dims['q']' must be a list of positive integers")
-    if [k for k in dims.get("s", []) if not isinstance(k, (int, np.integer)) or k < 0]:
-        raise TypeError("'dims['s']' must be a list of nonnegative integers")
+    _ipm.check_dims(dims)
 
 
 def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualstart=None, kktsolver=None, chol_opts=None):
     """coneprog.conelp (coneprog.py:31-1436) for dims with 'q' / 's' cones, on the GPU.  Returns the reference's result dictionary
     with numpy arrays ('s' blocks of s and z as full symmetric matrices)."""
-    _lib.require_device()
     if kktsolver is not None:
         raise NotImplementedError("conelp with 'q' / 's' cones runs misc.kkt_chol on the GPU; kktsolver is not selectable")
-    opts = {"maxiters": 100, "abstol": 1e-7, "reltol": 1e-6, "feastol": 1e-7, "show_progress": False, "refinement": None}
-    opts.update(options or {})
-    MAXITERS, ABSTOL, RELTOL, FEASTOL = opts["maxiters"], opts["abstol"], opts["reltol"], opts["feastol"]
-    if not isinstance(MAXITERS, (int, np.integer)) or MAXITERS < 1:
-        raise ValueError("options['maxiters'] must be a positive integer")
-    if RELTOL <= 0.0 and ABSTOL <= 0.0:
-        raise ValueError("at least one of options['reltol'] and options['abstol'] must be positive")
-    if FEASTOL <= 0.0:
-        raise ValueError("options['feastol'] must be a positive scalar")
-    show = opts["show_progress"]
-    dims = {"l": dims.get("l", 0), "q": list(dims.get("q") or []), "s": list(dims.get("s") or [])}
-    check_dims(dims)
-    REFINEMENT = opts["refinement"]
-    if REFINEMENT is None:
-        REFINEMENT = 1 if (dims["q"] or dims["s"]) else 0            # coneprog.py:502-507
-    elif not isinstance(REFINEMENT, (int, np.integer)) or REFINEMENT < 0:
-        raise ValueError("options['refinement'] must be a nonnegative integer")
-    D = Dims(dims)
-    cdim = D.N
-    c_h = np.asarray(base._dense_buffer(c)[0] if not isinstance(c, np.ndarray) else c, dtype=np.float64).reshape(-1)
-    n = c_h.size
-    h_h = _vec(h, "h", cdim)
-    Gm, Gn, Gp, Gi, Gx = _ccs(G)
-    if (Gm, Gn) != (cdim, n):
-        raise TypeError("'G' must be a 'd' matrix of size (%d, %d)" % (cdim, n))
-    p = 0
-    Ap = Ai = Ax = None
-    if A is not None:
-        p, na, Ap, Ai, Ax = _ccs(A)
-        if na != n:
-            raise TypeError("'A' must be a 'd' matrix with %d columns " % n)
-    b_h = np.zeros(0) if b is None else np.asarray(base._dense_buffer(b)[0] if not isinstance(b, np.ndarray) else b, dtype=np.float64).reshape(-1)
-    if b_h.size != p:
-        raise TypeError("'b' must have length %d" % p)
-    if p > n or p + D.Np < n:
-        raise ValueError("Rank(A) < p or Rank([G; A]) < n")           # coneprog.py:565-566
-    kkt = KKTConeDev(D, n, Gp, Gi, Gx, p, Ap, Ai, Ax, chol_opts)
-    Gd = kkt.G
-
-    def Gf(u, v, trans="N", alpha=1.0, beta=0.0):                     # misc.sgemv (misc.py:801-833)
-        if trans == "N":
-            Gd.gemv(u, v, trans="N", alpha=alpha, beta=beta)
-        else:
-            tg.copy_from(u)
-            if alpha:
-                tri(D, tg.ptr, 1)
-            Gd.gemv(tg, v, trans="T", alpha=alpha, beta=beta)
-
-    def Af(u, v, trans="N", alpha=1.0, beta=0.0):                     # base.gemv with A (p x n)
-        if p:
-            kkt.A.gemv(u, v, trans=trans, alpha=alpha, beta=beta)
-        elif trans == "T":
-            if beta == 0.0:
-                v.fill(0.0)
-            else:
-                v.scal(beta)
-
-    def vec(nn, init=None):
-        return DVec(nn, init)
-
-    tg = vec(cdim)
+    opt = _ipm.options(options, dims)
+    MAXITERS, ABSTOL, RELTOL, FEASTOL, REFINEMENT, show = opt.maxiters, opt.abstol, opt.reltol, opt.feastol, opt.refinement, opt.show
+    pb = _ipm.problem(c, G, h, dims, A, b)
+    n, p, cdim, c_h, h_h, b_h = pb.n, pb.p, pb.cdim, pb.c, pb.h, pb.b
+    _lib.require_device()
+    D = Dims(pb.dims)
+    kkt = KKTConeDev(D, n, *pb.G, p, *pb.A, chol_opts)
+    vec = DVec
+    Gf, Af = _ipm.operators(kkt.G, kkt.A if p else None, (lambda t: tri(D, t.ptr, 1)) if D.tot2 else None, vec(cdim))
     cv, hv, bv = vec(n, c_h), vec(cdim, h_h), vec(p, b_h if p else None)
     ws3, wz3 = vec(cdim), vec(cdim)
     W = WDev(D)
@@ -536,15 +241,9 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
     t_start = time.perf_counter()
 
     def finish(status, iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, xs=True, zs=True, ts=None, tz=None, msg=None):
-        if show:
-            print(msg or {"optimal": "Optimal solution found.", "primal infeasible": "Certificate of primal infeasibility found.",
-                          "dual infeasible": "Certificate of dual infeasibility found."}[status])
-        return {"x": x.get() if xs else None, "y": y.get() if zs else None, "s": s.get() if xs else None, "z": z.get() if zs else None,
-                "status": status, "gap": gap, "relative gap": relgap, "primal objective": pcost, "dual objective": dcost,
-                "primal infeasibility": pres, "dual infeasibility": dres,
-                "primal slack": -ts if ts is not None else None, "dual slack": -tz if tz is not None else None,
-                "residual as primal infeasibility certificate": pinfres, "residual as dual infeasibility certificate": dinfres,
-                "iterations": iters, "factorizations": kkt.nfactor, "loop seconds": time.perf_counter() - t_start}
+        return _ipm.conelp_result(show, status, x.get() if xs else None, y.get() if zs else None, s.get() if xs else None,
+                                  z.get() if zs else None, (gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres), ts, tz, iters,
+                                  kkt.nfactor, msg, **{"loop seconds": time.perf_counter() - t_start})
 
     rank_msg = "Rank(A) < p or Rank([G; A]) < n"
     if p:
@@ -668,9 +367,7 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
         pinfres = hresx / resx0 / (-hz - by) if hz + by < 0.0 else None
         dinfres = max(hresy / resy0, hresz / resz0) / (-cx) if cx < 0.0 else None
         if show:
-            if iters == 0:
-                print("% 10s% 12s% 10s% 8s% 7s % 5s" % ("pcost", "dcost", "gap", "pres", "dres", "k/t"))
-            print("%2d: % 8.4e % 8.4e % 4.0e% 7.0e% 7.0e% 7.0e" % (iters, pcost, dcost, gap, pres, dres, kappa / tau))
+            _ipm.progress(iters, pcost, dcost, gap, pres, dres, kappa / tau)
 
         if (pres <= FEASTOL and dres <= FEASTOL and (gap <= ABSTOL or (relgap is not None and relgap <= RELTOL))) or iters == MAXITERS:
             x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
@@ -678,7 +375,7 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
             ts, tz = max_step(D, s.ptr), max_step(D, z.ptr)
             if iters == MAXITERS:
                 return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, ts=ts, tz=tz,
-                              msg="Terminated (maximum number of iterations reached).")
+                              msg=_ipm.MAXITERS_MSG)
             return finish("optimal", iters, gap, relgap, pcost, dcost, pres, dres, None, None, ts=ts, tz=tz)
         elif pinfres is not None and pinfres <= FEASTOL:
             y.scal(1.0 / (-hz - by)); z.scal(1.0 / (-hz - by))
@@ -714,7 +411,7 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
             tri(D, s.ptr, 0); tri(D, z.ptr, 0)
             ts, tz = max_step(D, s.ptr), max_step(D, z.ptr)
             return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, ts=ts, tz=tz,
-                          msg="Terminated (singular KKT matrix).")
+                          msg=_ipm.SINGULAR_MSG)
 
         th.copy_from(hv)
         scale(D, W, th.ptr, trans="T", inverse="I")
@@ -736,20 +433,7 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
             bs.axpy(bz, -1.0)
             bkappa[0] -= btau[0]
 
-        def f6(bx, by_, bz, btau, bs, bkappa):                        # coneprog.py:1211-1235
-            if REFINEMENT:
-                wx.copy_from(bx); wy.copy_from(by_); wz.copy_from(bz); ws.copy_from(bs)
-                wtau, wkappa = btau[0], bkappa[0]
-            f6_no_ir(bx, by_, bz, btau, bs, bkappa)
-            for _ in range(REFINEMENT):
-                wx2.copy_from(wx); wy2.copy_from(wy); wz2.copy_from(wz); ws2.copy_from(ws)
-                wtau2, wkappa2 = [wtau], [wkappa]
-                res(bx, by_, bz, btau, bs, bkappa, wx2, wy2, wz2, wtau2, ws2, wkappa2, dg, lmbda_g)
-                f6_no_ir(wx2, wy2, wz2, wtau2, ws2, wkappa2)
-                bx.axpy(wx2); by_.axpy(wy2); bz.axpy(wz2)
-                btau[0] += wtau2[0]
-                bs.axpy(ws2)
-                bkappa[0] += wkappa2[0]
+        f6 = _ipm.f6(f6_no_ir, lambda *a: res(*a, dg, lmbda_g), REFINEMENT, (wx, wy, wz, ws), (wx2, wy2, wz2, ws2))
 
         mu = lmbda.dot(lmbda) + 0.0
         mu = (mu + lmbda_g ** 2) / (1 + D.Nd)                          # blas.nrm2(lmbda)**2 / (1 + cdim_diag)
@@ -803,15 +487,6 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
     raise AssertionError("unreachable")
 
 
-def lower_ccs(M, n, name="P"):
-    """Lower triangle (i >= j) of an n x n matrix (dense `matrix` or 2-D numpy array: every entry of the triangle stored; or an
-    spmatrix) as CCS; what lies above the diagonal is ignored, as the reference's symmetric kernels ignore it."""
-    from .misc import _full_pattern
-    if isinstance(M, np.ndarray):
-        M = base.matrix(np.asarray(M, dtype=np.float64).reshape(M.shape[0], -1))
-    return _lower_ccs(_full_pattern(M), n, name)
-
-
 def coneqp(P, q, G, h, dims, A=None, b=None, initvals=None, options=None, chol_opts=None):
     """coneprog.coneqp (coneprog.py:1440-2547) for dims with 'q' / 's' cones, on the GPU:
 
@@ -822,78 +497,24 @@ def coneqp(P, q, G, h, dims, A=None, b=None, initvals=None, options=None, chol_o
     Rank([P; G]) = n (with equality constraints the reference needs that on the null space of A only).  Returns the reference's
     result dictionary (coneprog.py:2216-2221) with numpy arrays, the 's' blocks of s and z as full symmetric matrices, plus
     "factorizations"."""
-    _lib.require_device()
-    opts = {"maxiters": 100, "abstol": 1e-7, "reltol": 1e-6, "feastol": 1e-7, "show_progress": False, "use_correction": True}
-    opts.update(options or {})
-    num = (float, int, np.floating, np.integer)
-    correction = opts["use_correction"]
-    MAXITERS, ABSTOL, RELTOL, FEASTOL = opts["maxiters"], opts["abstol"], opts["reltol"], opts["feastol"]
-    if not isinstance(MAXITERS, (int, np.integer)) or MAXITERS < 1:
-        raise ValueError("options['maxiters'] must be a positive integer")
-    if not isinstance(ABSTOL, num):
-        raise ValueError("options['abstol'] must be a scalar")
-    if not isinstance(RELTOL, num):
-        raise ValueError("options['reltol'] must be a scalar")
-    if RELTOL <= 0.0 and ABSTOL <= 0.0:
-        raise ValueError("at least one of options['reltol'] and options['abstol'] must be positive")
-    if not isinstance(FEASTOL, num) or FEASTOL <= 0.0:
-        raise ValueError("options['feastol'] must be a positive scalar")
-    show = opts["show_progress"]
     if G is None or dims is None:
         raise NotImplementedError("coneqp without G is not part of the general-cone path")
     for M in (P, G, A):
         if callable(M):
             raise ValueError("use of function valued P, G, A requires a user-provided kktsolver")
-    dims = {"l": dims.get("l", 0), "q": list(dims.get("q") or []), "s": list(dims.get("s") or [])}
-    check_dims(dims)
-    if "refinement" not in opts or opts["refinement"] is None:
-        REFINEMENT = 1 if (dims["q"] or dims["s"]) else 0            # coneprog.py:1862-1865
-    else:
-        REFINEMENT = opts["refinement"]
-        if not isinstance(REFINEMENT, (int, np.integer)) or REFINEMENT < 0:
-            raise ValueError("options['refinement'] must be a nonnegative integer")
-    D = Dims(dims)
-    cdim = D.N
+    opt = _ipm.options(options, dims, qp=True)
+    MAXITERS, ABSTOL, RELTOL, FEASTOL, REFINEMENT, show = opt.maxiters, opt.abstol, opt.reltol, opt.feastol, opt.refinement, opt.show
+    correction = opt.correction
+    pb = _ipm.problem(q, G, h, dims, A, b, P, qp=True)
+    n, p, cdim, q_h, h_h, b_h = pb.n, pb.p, pb.cdim, pb.c, pb.h, pb.b
     if cdim == 0:
         raise NotImplementedError("coneqp without cone constraints is not part of the general-cone path")
-    q_h = np.ascontiguousarray(np.asarray(base._dense_buffer(q)[0] if not isinstance(q, np.ndarray) else q, dtype=np.float64).reshape(-1))
-    n = q_h.size
-    Pp, Pi, Px = lower_ccs(P, n)
-    h_h = _vec(h, "h", cdim)
-    Gm, Gn, Gp, Gi, Gx = _ccs(G)
-    if (Gm, Gn) != (cdim, n):
-        raise TypeError("'G' must be a 'd' matrix of size (%d, %d)" % (cdim, n))
-    p = 0
-    Ap = Ai = Ax = None
-    if A is not None:
-        p, na, Ap, Ai, Ax = _ccs(A)
-        if na != n:
-            raise TypeError("'A' must be a 'd' matrix with %d columns" % n)
-    b_h = np.zeros(0) if b is None else np.asarray(base._dense_buffer(b)[0] if not isinstance(b, np.ndarray) else b, dtype=np.float64).reshape(-1)
-    if b_h.size != p:
-        raise TypeError("'b' must have length %d" % p)
-    if p > n:
-        raise ValueError("Rank(A) < p or Rank([P; G; A]) < n")        # coneprog.py:1970-1971
-    kkt = KKTConeDev(D, n, Gp, Gi, Gx, p, Ap, Ai, Ax, chol_opts, Pp, Pi, Px)
-    Gd, Pd = kkt.G, SymSpMatDev(n, Pp, Pi, Px)
+    _lib.require_device()
+    D = Dims(pb.dims)
+    kkt = KKTConeDev(D, n, *pb.G, p, *pb.A, chol_opts, *pb.P)
+    Pd = SymSpMatDev(n, *pb.P)
     vec = DVec
-    tg = vec(cdim)
-
-    def Gf(u, v, trans="N", alpha=1.0, beta=0.0):                     # misc.sgemv (misc.py:801-833)
-        if trans == "N":
-            Gd.gemv(u, v, trans="N", alpha=alpha, beta=beta)
-        else:
-            tg.copy_from(u)
-            tri(D, tg.ptr, 1)
-            Gd.gemv(tg, v, trans="T", alpha=alpha, beta=beta)
-
-    def Af(u, v, trans="N", alpha=1.0, beta=0.0):                     # base.gemv with A (p x n); p = 0: v := beta v
-        if p:
-            kkt.A.gemv(u, v, trans=trans, alpha=alpha, beta=beta)
-        elif trans == "T" and beta == 0.0:
-            v.fill(0.0)
-        elif trans == "T" and beta != 1.0:
-            v.scal(beta)
+    Gf, Af = _ipm.operators(kkt.G, kkt.A if p else None, (lambda t: tri(D, t.ptr, 1)) if D.tot2 else None, vec(cdim))
 
     qv, hv, bv = vec(n, q_h), vec(cdim, h_h), vec(p, b_h if p else None)
     ws3, wz3, dtmp = vec(cdim), vec(cdim), vec(cdim)
@@ -926,12 +547,8 @@ def coneqp(P, q, G, h, dims, A=None, b=None, initvals=None, options=None, chol_o
     def finish(status, iters, gap, relgap, pcost, dcost, pres, dres, msg):
         tri(D, s.ptr, 0); tri(D, z.ptr, 0)                            # misc.symm of the 's' blocks
         ts, tz = max_step(D, s.ptr), max_step(D, z.ptr)
-        if show:
-            print(msg)
-        return {"x": x.get(), "y": y.get() if p else np.zeros(0), "s": s.get(), "z": z.get(), "status": status, "gap": gap,
-                "relative gap": relgap, "primal objective": pcost, "dual objective": dcost, "primal infeasibility": pres,
-                "dual infeasibility": dres, "primal slack": -ts, "dual slack": -tz, "iterations": iters,
-                "factorizations": kkt.nfactor}
+        return _ipm.coneqp_result(show, status, x.get(), y.get() if p else np.zeros(0), s.get(), z.get(),
+                                  (gap, relgap, pcost, dcost, pres, dres), ts, tz, iters, kkt.nfactor, msg)
 
     # ---- starting point (coneprog.py:2044-2150)
     if initvals is None:
@@ -991,15 +608,7 @@ def coneqp(P, q, G, h, dims, A=None, b=None, initvals=None, options=None, chol_o
         kkt.solve(bx, by_, bz)
         bs.axpy(bz, -1.0)
 
-    def f4(bx, by_, bz, bs):                                          # coneprog.py:2330-2347
-        if REFINEMENT:
-            wx.copy_from(bx); wy.copy_from(by_); wz.copy_from(bz); ws.copy_from(bs)
-        f4_no_ir(bx, by_, bz, bs)
-        for _ in range(REFINEMENT):
-            wx2.copy_from(wx); wy2.copy_from(wy); wz2.copy_from(wz); ws2.copy_from(ws)
-            res(bx, by_, bz, bs, wx2, wy2, wz2, ws2)
-            f4_no_ir(wx2, wy2, wz2, ws2)
-            bx.axpy(wx2); by_.axpy(wy2); bz.axpy(wz2); bs.axpy(ws2)
+    f4 = _ipm.f4(f4_no_ir, res, REFINEMENT, (wx, wy, wz, ws) if REFINEMENT else (), (wx2, wy2, wz2, ws2) if REFINEMENT else ())
 
     for iters in range(MAXITERS + 1):
         # f0 = (1/2) x'Px + q'x, rx = Px + q + A'y + G'z, ry = Ax - b, rz = s + Gx - h  (coneprog.py:2169-2186)
@@ -1023,12 +632,10 @@ def coneqp(P, q, G, h, dims, A=None, b=None, initvals=None, options=None, chol_o
         pres = max(resy / resy0, resz / resz0)
         dres = resx / resx0
         if show:
-            if iters == 0:
-                print("% 10s% 12s% 10s% 8s% 7s" % ("pcost", "dcost", "gap", "pres", "dres"))
-            print("%2d: % 8.4e % 8.4e % 4.0e% 7.0e% 7.0e" % (iters, pcost, dcost, gap, pres, dres))
+            _ipm.progress(iters, pcost, dcost, gap, pres, dres)
         if (pres <= FEASTOL and dres <= FEASTOL and (gap <= ABSTOL or (relgap is not None and relgap <= RELTOL))) or iters == MAXITERS:
             if iters == MAXITERS:
-                return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, "Terminated (maximum number of iterations reached).")
+                return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, _ipm.MAXITERS_MSG)
             return finish("optimal", iters, gap, relgap, pcost, dcost, pres, dres, "Optimal solution found.")
 
         if iters == 0:
@@ -1039,7 +646,7 @@ def coneqp(P, q, G, h, dims, A=None, b=None, initvals=None, options=None, chol_o
         except ArithmeticError:
             if iters == 0:
                 raise ValueError("Rank(A) < p or Rank([P; A; G]) < n")
-            return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, "Terminated (singular KKT matrix).")
+            return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, _ipm.SINGULAR_MSG)
 
         mu = gap / (D.ml + D.nq + D.tot1)
         sigma, eta = 0.0, 0.0
@@ -1059,7 +666,7 @@ def coneqp(P, q, G, h, dims, A=None, b=None, initvals=None, options=None, chol_o
             except ArithmeticError:
                 if iters == 0:
                     raise ValueError("Rank(A) < p or Rank([P; A; G]) < n")
-                return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, "Terminated (singular KKT matrix).")
+                return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, _ipm.SINGULAR_MSG)
             dsdz = sdot(D, ds.ptr, dz.ptr)
             if correction and i == 0:                                 # ds o dz for the Mehrotra correction
                 ws3.copy_from(ds)

@@ -22,10 +22,12 @@ import time
 
 import numpy as np
 
-from . import _lib, base
+from . import _ipm, _lib, base
 from ._lib import DeviceBuffer, lib, raise_for
 from .chol import Factor
+from .devvec import DVec, SpMatDev, SymSpMatDev, reduce_multi      # noqa: F401  (lp.DVec, lp.SpMatDev, ... are public names)
 
+_lower_ccs = base.lower_ccs
 EXPON = 3          # coneprog.py:423
 STEP = 0.99        # coneprog.py:424
 # KVX_LP_UNFUSED=1: one launch per BLAS-1-sized operation, as in rounds 1-2 (the library reads the same variable); the fused launches
@@ -45,138 +47,6 @@ def _sides(items):
         a.xin, a.xscale, a.zin = xin.ptr, float(xs), zin.ptr
         a.xout, a.xoscale, a.zout, a.zoscale = xout.ptr, float(xos), zout.ptr, float(zos)
     return arr
-
-
-class DVec:
-    """A float64 vector in HBM with the BLAS-1 / NT-scaling operations of the C ABI."""
-
-    def __init__(self, n, init=None):
-        self.n = int(n)
-        self.buf = DeviceBuffer(8 * max(self.n, 1))
-        if init is not None:
-            self.set(init)
-
-    @property
-    def ptr(self):
-        return self.buf.ptr
-
-    def set(self, a):
-        self.buf.upload(np.ascontiguousarray(a, dtype=np.float64).reshape(-1))
-        return self
-
-    def get(self):
-        return self.buf.download(np.float64, self.n)
-
-    def fill(self, v):
-        raise_for(lib().kvx_vec_fill_dev(self.n, float(v), self.ptr)); return self
-
-    def copy_from(self, x):
-        raise_for(lib().kvx_vec_copy_dev(self.n, x.ptr, self.ptr)); return self
-
-    def axpy(self, x, alpha=1.0):                       # self += alpha * x
-        raise_for(lib().kvx_vec_axpy_dev(self.n, float(alpha), x.ptr, self.ptr)); return self
-
-    def lincomb(self, a, x, b=0.0, y=None):             # self := a * x + b * y (one pass; copy + axpy / copy + scal)
-        raise_for(lib().kvx_vec_lincomb_dev(self.n, float(a), x.ptr, float(b) if y is not None else 0.0,
-                                            (y if y is not None else x).ptr, self.ptr)); return self
-
-    def scal(self, alpha):
-        raise_for(lib().kvx_vec_scal_dev(self.n, float(alpha), self.ptr)); return self
-
-    def addc(self, c):
-        raise_for(lib().kvx_vec_addc_dev(self.n, float(c), self.ptr)); return self
-
-    def mul(self, y):                                   # self .*= y   (misc.scale / sprod / scale2 'I')
-        raise_for(lib().kvx_nt_sprod_dev(self.n, self.ptr, y.ptr)); return self
-
-    def div(self, y):                                   # self ./= y   (sinv / scale2 'N')
-        raise_for(lib().kvx_nt_sinv_dev(self.n, self.ptr, y.ptr)); return self
-
-    def sqr_of(self, y):                                # self := y.*y  (misc.ssqr)
-        raise_for(lib().kvx_nt_ssqr_dev(self.n, self.ptr, y.ptr)); return self
-
-    def xmy(self, a, x, y, b=0.0):                      # self := a * x.*y + b * self
-        raise_for(lib().kvx_vec_xmy_dev(self.n, float(a), x.ptr, y.ptr, float(b), self.ptr)); return self
-
-    def dot(self, y):
-        if self.n == 0:
-            return 0.0
-        r = ctypes.c_double()
-        raise_for(lib().kvx_nt_sdot_dev(self.n, self.ptr, y.ptr, ctypes.byref(r)))
-        return r.value
-
-    def nrm2(self):
-        return math.sqrt(self.dot(self))
-
-    def max_step(self):                                 # misc.max_step 'l' block: max_i(-x_i)
-        r = ctypes.c_double()
-        raise_for(lib().kvx_nt_max_step_dev(self.n, self.ptr, ctypes.byref(r)))
-        return r.value
-
-
-def reduce_multi(items):
-    """Several reductions with ONE host synchronisation (kvx_nt_reduce_multi_dev).  items: ("dot", x, y) or ("max", x)
-    with DVec operands; entries whose operand is not a DVec (the empty y-blocks of p = 0) yield 0.0.  Bitwise the values
-    of DVec.dot / DVec.max_step."""
-    live = [(k, it) for k, it in enumerate(items) if isinstance(it[1], DVec) and it[1].n > 0]
-    out = [0.0] * len(items)
-    if not live:
-        return out
-    m = len(live)
-    kind = (ctypes.c_int32 * m)(*[0 if it[0] == "dot" else 1 for _, it in live])
-    n = (ctypes.c_int64 * m)(*[it[1].n for _, it in live])
-    xs = (ctypes.c_void_p * m)(*[it[1].ptr for _, it in live])
-    ys = (ctypes.c_void_p * m)(*[(it[2].ptr if it[0] == "dot" else None) for _, it in live])
-    res = (ctypes.c_double * m)()
-    raise_for(lib().kvx_nt_reduce_multi_dev(m, kind, n, xs, ys, res))
-    for j, (k, _) in enumerate(live):
-        out[k] = float(res[j])
-    return out
-
-
-class SpMatDev:
-    """CCS matrix resident in HBM (int64 indices as in the reference, kvxopt.h:46), together with the CCS of its
-    transpose: both directions of the mat-vec then run as row gathers (kvx_spmv_dev 'T') -- the column-scatter form of
-    'N' needs FP64 atomics, whose rounding depends on the order of arrival: with it two runs of the interior-point loop
-    differ in the last bits, without it they are bitwise identical (like the factorisation and the solves)."""
-
-    def __init__(self, m, n, colptr, rowind, values):
-        self.m, self.n = int(m), int(n)
-        colptr = np.ascontiguousarray(colptr, dtype=np.int64)
-        rowind = np.ascontiguousarray(rowind, dtype=np.int64)
-        values = np.ascontiguousarray(values, dtype=np.float64)
-        self.cp = DeviceBuffer.from_array(colptr)
-        self.ri = DeviceBuffer.from_array(rowind) if len(rowind) else DeviceBuffer(8)
-        self.vx = DeviceBuffer.from_array(values) if len(values) else DeviceBuffer(8)
-        cols = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(colptr))
-        # (row, column) order: the entries come column by column, so a STABLE sort by row is the two-key sort; counts by bincount
-        # (lexsort + np.add.at were 6 of the 8 ms this constructor took for 400 000 entries)
-        order = np.argsort(rowind, kind="stable")
-        self._order = order                               # CCS position of every entry of the transposed copy
-        tp = np.zeros(self.m + 1, dtype=np.int64)
-        if len(rowind):
-            np.cumsum(np.bincount(rowind, minlength=self.m), out=tp[1:])
-        self.max_row = int(np.diff(tp).max()) if self.m else 0         # most entries in a row / column (the fused kernels size
-        self.max_col = int(np.diff(colptr).max()) if self.n else 0     # their lane groups by them)
-        self.tcp = DeviceBuffer.from_array(tp)
-        self.tri = DeviceBuffer.from_array(cols[order]) if len(rowind) else DeviceBuffer(8)
-        self.tvx = DeviceBuffer.from_array(values[order]) if len(values) else DeviceBuffer(8)
-
-    def set_values(self, values):
-        """New values on the same pattern (both copies)."""
-        values = np.ascontiguousarray(values, dtype=np.float64)
-        if values.size:
-            self.vx.upload(values)
-            self.tvx.upload(np.ascontiguousarray(values[self._order]))
-
-    def gemv(self, x, y, trans="N", alpha=1.0, beta=0.0):
-        """y := alpha*op(A)*x + beta*y  (base.gemv -> sparse.c:1073-1104)."""
-        if trans == "N":                                  # A x = (A')' x: gather over the rows of A
-            raise_for(lib().kvx_spmv_dev(ord("T"), self.n, self.m, self.tcp.ptr, self.tri.ptr, self.tvx.ptr,
-                                         float(alpha), x.ptr, float(beta), y.ptr))
-        else:
-            raise_for(lib().kvx_spmv_dev(ord("T"), self.m, self.n, self.cp.ptr, self.ri.ptr, self.vx.ptr,
-                                         float(alpha), x.ptr, float(beta), y.ptr))
 
 
 class KKTChol2Dev:
@@ -706,63 +576,24 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
     (ml x n, sparse); A (p x n, sparse), b (p,) optional -- with equality constraints either G has at most one entry per
     row (standard form: KKTDiagEqDev, sparse K on a fixed pattern) or any other sparse G (KKTGenEqDev, dense K in HBM).  primalstart = {'x', 's'},
     dualstart = {'y', 'z'} (y optional) as in the reference (coneprog.py:683-737): s and z must be strictly positive.  Returns the reference's result dictionary (coneprog.py:962-974) with numpy arrays."""
-    _lib.require_device()
-    opts = {"maxiters": 100, "abstol": 1e-7, "reltol": 1e-6, "feastol": 1e-7, "show_progress": False, "refinement": 0}
-    opts.update(options or {})
-    MAXITERS, ABSTOL, RELTOL, FEASTOL = opts["maxiters"], opts["abstol"], opts["reltol"], opts["feastol"]
-    show = opts["show_progress"]
-    REFINEMENT = opts["refinement"]                      # coneprog.py:502-507: default 0 when there are no 'q' / 's' cones
-    if not isinstance(REFINEMENT, (int, np.integer)) or REFINEMENT < 0:
-        raise ValueError("options['refinement'] must be a nonnegative integer")
-    ml, n, Gp, Gi, Gx = base._as_ccs(G)
+    opt = _ipm.options(options, {})
+    MAXITERS, ABSTOL, RELTOL, FEASTOL, REFINEMENT, show = opt.maxiters, opt.abstol, opt.reltol, opt.feastol, opt.refinement, opt.show
+    pb = _ipm.problem(c, G, h, None, A, b)
+    n, p, ml, c_h, h_h, b_h = pb.n, pb.p, pb.cdim, pb.c, pb.h, pb.b
+    (Gp, Gi, Gx), (Ap, Ai, Ax) = pb.G, pb.A
     if dims is not None and (dims.get("q") or dims.get("s") or dims.get("l", ml) != ml):
         raise NotImplementedError("only the orthant cone dims = {'l': G.size[0], 'q': [], 's': []} runs on the GPU")
-    c_h = np.asarray(c._a if isinstance(c, base.matrix) else c, dtype=np.float64).reshape(-1)
-    h_h = np.asarray(h._a if isinstance(h, base.matrix) else h, dtype=np.float64).reshape(-1)
-    if c_h.size != n or h_h.size != ml:
-        raise TypeError("dimensions of c, G, h do not match")
-    p = 0
-    if A is not None:
-        p, na, Ap, Ai, Ax = base._as_ccs(A)
-        if na != n:
-            raise TypeError("'A' must have %d columns" % n)
-        b_h = np.asarray(b._a if isinstance(b, base.matrix) else b, dtype=np.float64).reshape(-1)
-        if b_h.size != p:
-            raise TypeError("'b' must have length %d" % p)
-    if p > n or p + ml < n:
-        raise ValueError("Rank(A) < p or Rank([G; A]) < n")          # coneprog.py:572-573
-
-    class _NoY:                                                      # p = 0: the y-blocks of the algorithm are empty
-        def __getattr__(self, name):
-            return lambda *a, **k: self
-        def dot(self, other):
-            return 0.0
-        def nrm2(self):
-            return 0.0
-        def get(self):
-            return np.zeros(0)
+    _lib.require_device()
+    _NoY = _ipm.NoVec                                                # p = 0: the y-blocks of the algorithm are empty
 
     if kktsolver is not None:
         # the reference's plug-in point (coneprog.py:323-344): kktsolver(W) returns f(x, y, z); host round trips per call
         if not callable(kktsolver):
             raise ValueError("kktsolver must be a function W -> f(x, y, z) (the reference's named solvers 'ldl', 'ldl2', 'qr', "
                              "'chol', 'chol2' are not part of this path: 'chol2' is what runs on the GPU by default)")
-        if p == 0:
-            Ap, Ai, Ax = np.zeros(n + 1, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0)
         kkt = KKTUserHost(ml, n, Gp, Gi, Gx, p, Ap, Ai, Ax, kktsolver)
         fused = False
         kfactor_solve2 = None
-        if p > 0:
-            Ad = kkt.A
-            bv = DVec(p, b_h)
-            y, dy, y1, ry, hry = (DVec(p) for _ in range(5))
-            def Af(u, v, trans="N", alpha=1.0, beta=0.0):
-                Ad.gemv(u, v, trans=trans, alpha=alpha, beta=beta)
-        else:
-            bv = y = dy = y1 = ry = hry = _NoY()
-            def Af(u, v, trans="N", alpha=1.0, beta=0.0):
-                if trans == "T" and beta == 0.0:
-                    v.fill(0.0)
         ksolve = kkt.solve
         def ksolve2(xa, ya, za, xb, yb, zb):
             kkt.solve(xa, ya, za)
@@ -773,19 +604,13 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
         cls = KKTDiagEqDev if diag_s else KKTGenEqDev
         kkt = _kkt_for(cls.__name__, (ml, n, p), (Gp, Gi, Ap, Ai), chol_opts,
                        lambda: cls(ml, n, Gp, Gi, Gx, p, Ap, Ai, Ax, chol_opts), lambda k: k.reset(Gx, Ax))
-        Ad = kkt.A
-        bv = DVec(p, b_h)
-        y, dy, y1, ry, hry = (DVec(p) for _ in range(5))
         ksolve = kkt.solve
         ksolve2 = kkt.solve2
         kfactor_solve2 = None
         fused = False
-        def Af(u, v, trans="N", alpha=1.0, beta=0.0):
-            Ad.gemv(u, v, trans=trans, alpha=alpha, beta=beta)
     else:
         kkt = _kkt_for("KKTChol2Dev", (ml, n, 0), (Gp, Gi), chol_opts,
                        lambda: KKTChol2Dev(ml, n, Gp, Gi, Gx, chol_opts), lambda k: k.reset(Gx))
-        bv = y = dy = y1 = ry = hry = _NoY()
         def ksolve(xx, yy, zz):
             kkt.solve(xx, zz)
         def ksolve2(xa, ya, za, xb, yb, zb):
@@ -793,9 +618,12 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
         def kfactor_solve2(dd, xa, ya, za, xb, yb, zb):
             kkt.factor_solve2(dd, xa, za, xb, zb)
         fused = not _UNFUSED and REFINEMENT == 0         # p = 0: the short launches of an iteration fused (kkt.hip, "round 3")
-        def Af(u, v, trans="N", alpha=1.0, beta=0.0):
-            if trans == "T" and beta == 0.0:
-                v.fill(0.0)                                          # A' y with p = 0: the zero vector
+    if p > 0:
+        bv = DVec(p, b_h)
+        y, dy, y1, ry, hry = (DVec(p) for _ in range(5))
+    else:
+        bv = y = dy = y1 = ry = hry = _NoY()
+    _, Af = _ipm.operators(kkt.G, kkt.A if p else None)
     Gd = kkt.G
     cv, hv = DVec(n, c_h), DVec(ml, h_h)
     x, dx, x1, rx, hrx = (DVec(n) for _ in range(5))
@@ -854,39 +682,20 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
             vs.axpy(rs3)
             vkappa[0] += sc["lmbda_g"] * (utau[0] + ukappa[0])
 
-        def f6_g(sc, bx, by, bz, btau, bs, bkappa):
-            wx.copy_from(bx); wy.copy_from(by); wz.copy_from(bz); ws.copy_from(bs)
-            wtau, wkappa = [btau[0]], [bkappa[0]]
-            f6_no_ir_g(sc, bx, by, bz, btau, bs, bkappa)
-            for _ in range(REFINEMENT):
-                wx2.copy_from(wx); wy2.copy_from(wy); wz2.copy_from(wz); ws2.copy_from(ws)
-                wtau2, wkappa2 = [wtau[0]], [wkappa[0]]
-                res_g(sc, bx, by, bz, btau, bs, bkappa, wx2, wy2, wz2, wtau2, ws2, wkappa2)
-                f6_no_ir_g(sc, wx2, wy2, wz2, wtau2, ws2, wkappa2)
-                bx.axpy(wx2); by.axpy(wy2); bz.axpy(wz2)
-                btau[0] += wtau2[0]
-                bs.axpy(ws2)
-                bkappa[0] += wkappa2[0]
+        def f6_g(sc, *rhs):
+            _ipm.f6(lambda *a: f6_no_ir_g(sc, *a), lambda *a: res_g(sc, *a), REFINEMENT, (wx, wy, wz, ws), (wx2, wy2, wz2, ws2))(*rhs)
 
     def result(status, iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, xs=True, zs=True, msg=None):
-        if show:                                         # the reference's closing line (coneprog.py:791,941,961,985,1010,1094)
-            print(msg or {"optimal": "Optimal solution found.", "primal infeasible": "Certificate of primal infeasibility found.",
-                          "dual infeasible": "Certificate of dual infeasibility found."}[status])
-        return {"x": x.get() if xs else None, "y": y.get() if zs else None,
-                "s": s.get() if xs else None, "z": z.get() if zs else None,
-                "status": status, "gap": gap, "relative gap": relgap,
-                "primal objective": pcost, "dual objective": dcost,
-                "primal infeasibility": pres, "dual infeasibility": dres,
-                "primal slack": -s.max_step() if xs else None, "dual slack": -z.max_step() if zs else None,
-                "residual as primal infeasibility certificate": pinfres,
-                "residual as dual infeasibility certificate": dinfres,
-                "iterations": iters, "factorizations": kkt.nfactor,
+        return _ipm.conelp_result(
+            show, status, x.get() if xs else None, y.get() if zs else None, s.get() if xs else None, z.get() if zs else None,
+            (gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres), s.max_step() if xs else None, z.max_step() if zs else None,
+            iters, kkt.nfactor, msg, **{
                 # wall time of the interior-point loop proper (coneprog.py:859-1436), i.e. without the symbolic
                 # analysis and the starting point; not a key of the reference's dictionary
                 "loop seconds": (time.perf_counter() - t_loop[0]) if t_loop[0] is not None else 0.0,
                 # the same, split at the three host synchronisations of an iteration: [residual norms -> first direction
                 # (assembly, factorisation, two solves), -> second direction (one solve), -> update + residuals of the next]
-                "phase seconds": list(t_phase)}
+                "phase seconds": list(t_phase)})
 
     # ---- starting point (coneprog.py:662-822): factor with W = I ------------------------------------
     d.fill(1.0); di.fill(1.0)
@@ -894,18 +703,12 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
         kkt.factor(di)
     except ArithmeticError:
         raise ValueError("Rank(A) < p or Rank([G; A]) < n")
-    def _vec(v):
-        return np.ascontiguousarray(np.asarray(v._a if isinstance(v, base.matrix) else v, dtype=np.float64).reshape(-1))
-
     if primalstart is None:
         x.fill(0.0); dy.copy_from(bv); s.copy_from(hv)
         ksolve(x, dy, s)
         s.scal(-1.0)
     else:                                                        # coneprog.py:703-705
-        xs0, ss0 = _vec(primalstart["x"]), _vec(primalstart["s"])
-        if xs0.size != n or ss0.size != ml:
-            raise TypeError("primalstart has the wrong dimensions")
-        x.set(xs0); s.set(ss0)
+        x.set(_ipm.vector(primalstart["x"], "primalstart['x']", n)); s.set(_ipm.vector(primalstart["s"], "primalstart['s']", ml))
     ts = s.max_step()
     if ts >= 0 and primalstart is not None:
         raise ValueError("initial s is not positive")
@@ -913,14 +716,11 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
         dx.copy_from(cv).scal(-1.0); y.fill(0.0); z.fill(0.0)
         ksolve(dx, y, z)
     else:                                                        # coneprog.py:731-733
-        zs0 = _vec(dualstart["z"])
-        if zs0.size != ml:
-            raise TypeError("dualstart has the wrong dimensions")
         if p and "y" in dualstart:
-            y.set(_vec(dualstart["y"]))
+            y.set(_ipm.vector(dualstart["y"], "dualstart['y']", p))
         elif p:
             y.fill(0.0)
-        z.set(zs0)
+        z.set(_ipm.vector(dualstart["z"], "dualstart['z']", ml))
     tz = z.max_step()
     if tz >= 0 and dualstart is not None:
         raise ValueError("initial z is not positive")
@@ -990,16 +790,14 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
         pinfres = hresx / resx0 / (-hz - by) if hz + by < 0.0 else None
         dinfres = max(hresy / resy0, hresz / resz0) / (-cx) if cx < 0.0 else None
         if show:
-            if iters == 0:
-                print("% 10s% 12s% 10s% 8s% 7s % 5s" % ("pcost", "dcost", "gap", "pres", "dres", "k/t"))
-            print("%2d: % 8.4e % 8.4e % 4.0e% 7.0e% 7.0e% 7.0e" % (iters, pcost, dcost, gap, pres, dres, kappa / tau))
+            _ipm.progress(iters, pcost, dcost, gap, pres, dres, kappa / tau)
 
         if (pres <= FEASTOL and dres <= FEASTOL and (gap <= ABSTOL or (relgap is not None and relgap <= RELTOL))) \
                 or iters == MAXITERS:
             x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
             if iters == MAXITERS:
                 return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres,
-                              msg="Terminated (maximum number of iterations reached).")
+                              msg=_ipm.MAXITERS_MSG)
             return result("optimal", iters, gap, relgap, pcost, dcost, pres, dres, None, None)
         elif pinfres is not None and pinfres <= FEASTOL:
             y.scal(1.0 / (-hz - by)); z.scal(1.0 / (-hz - by))
@@ -1079,7 +877,7 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
         except ArithmeticError:
             kkt.async_solves = False
             x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
-            return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, msg="Terminated (singular KKT matrix).")
+            return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, msg=_ipm.SINGULAR_MSG)
 
         z1z1 = -1.0                                      # computed on the device with the first direction
         out4 = (ctypes.c_double * 4)()
@@ -1095,7 +893,7 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
                         kkt.async_solves = False
                         x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
                         return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres,
-                                      msg="Terminated (singular KKT matrix).")
+                                      msg=_ipm.SINGULAR_MSG)
                 ds.copy_from(lmbdasq)
                 dkap = [lmbdasq_g]
                 if i == 1:
@@ -1134,7 +932,7 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
                 except ArithmeticError:
                     kkt.async_solves = False
                     x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
-                    return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, msg="Terminated (singular KKT matrix).")
+                    return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, msg=_ipm.SINGULAR_MSG)
             elif i == 1:
                 newton_rhs(1)
                 if fused:
@@ -1163,7 +961,7 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
                     kkt.async_solves = False
                     x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
                     return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres,
-                                  msg="Terminated (singular KKT matrix).")
+                                  msg=_ipm.SINGULAR_MSG)
             dkappa -= dtau
             if i == 0:
                 wkappa3 = dtau * dkappa
@@ -1198,79 +996,25 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
     raise AssertionError("unreachable")
 
 
-class SymSpMatDev:
-    """Symmetric sparse matrix resident in HBM, given by its lower triangle (the 'L' storage base.symv reads for
-    the quadratic term, coneprog.py:1889-1893): y := alpha*P*x + beta*y as one pass over the lower triangle and one
-    transposed pass over its strictly lower part."""
-
-    def __init__(self, n, colptr, rowind, values):
-        colptr = np.ascontiguousarray(colptr, dtype=np.int64)
-        rowind = np.ascontiguousarray(rowind, dtype=np.int64)
-        values = np.ascontiguousarray(values, dtype=np.float64)
-        cols = np.repeat(np.arange(n, dtype=np.int64), np.diff(colptr))
-        if np.any(rowind < cols):
-            raise ValueError("P must be given by its lower triangle")
-        strict = rowind > cols
-        sp = np.zeros(n + 1, dtype=np.int64)
-        np.add.at(sp, cols[strict] + 1, 1)
-        np.cumsum(sp, out=sp)
-        self.low = SpMatDev(n, n, colptr, rowind, values)
-        self.strict = SpMatDev(n, n, sp, rowind[strict], values[strict])
-
-    def symv(self, x, y, alpha=1.0, beta=0.0):
-        self.low.gemv(x, y, trans="N", alpha=alpha, beta=beta)
-        self.strict.gemv(x, y, trans="T", alpha=alpha, beta=1.0)
-
-
-def _lower_ccs(P, n, name="P"):
-    """Lower triangle (i >= j) of a spmatrix-like P as sorted CCS; entries above the diagonal are ignored, as the
-    reference's symmetric kernels do."""
-    m, n2, Pp, Pi, Px = base._as_ccs(P)
-    if m != n or n2 != n:
-        raise TypeError("'%s' must be a 'd' matrix of size (%d, %d)" % (name, n, n))
-    Pp = np.asarray(Pp, dtype=np.int64); Pi = np.asarray(Pi, dtype=np.int64); Px = np.asarray(Px, dtype=np.float64)
-    cols = np.repeat(np.arange(n, dtype=np.int64), np.diff(Pp))
-    keep = Pi >= cols
-    cp = np.zeros(n + 1, dtype=np.int64)
-    np.add.at(cp, cols[keep] + 1, 1)
-    np.cumsum(cp, out=cp)
-    return cp, Pi[keep].copy(), Px[keep].copy()
-
-
 def coneqp(P, q, G, h, options=None, chol_opts=None, A=None, b=None, initvals=None, kktsolver=None):
     """Solve the convex QP  minimize (1/2) x'Px + q'x  s.t.  Gx <= h, Ax = b  on the GPU (orthant cone): the reference's coneqp (coneprog.py:1440-2547) with its default KKT solver for sparse G,
     misc.kkt_chol2 with H = P.  P: spmatrix-like, its lower triangle is used.  Returns the reference's result
     dictionary (coneprog.py:2216-2221) with numpy arrays, plus "factorizations"."""
-    _lib.require_device()
-    opts = {"maxiters": 100, "abstol": 1e-7, "reltol": 1e-6, "feastol": 1e-7, "show_progress": False,
-            "refinement": 0, "use_correction": True}                        # coneprog.py:1768-1781, 1862-1865
-    opts.update(options or {})
-    MAXITERS, ABSTOL, RELTOL, FEASTOL = opts["maxiters"], opts["abstol"], opts["reltol"], opts["feastol"]
-    show, refinement, correction = opts["show_progress"], int(opts["refinement"]), bool(opts["use_correction"])
-    ml, n, Gp, Gi, Gx = base._as_ccs(G)
-    q_h = np.asarray(q._a if isinstance(q, base.matrix) else q, dtype=np.float64).reshape(-1)
-    h_h = np.asarray(h._a if isinstance(h, base.matrix) else h, dtype=np.float64).reshape(-1)
-    if q_h.size != n or h_h.size != ml:
-        raise TypeError("dimensions of q, G, h do not match")
+    opt = _ipm.options(options, {}, qp=True)                                    # coneprog.py:1768-1781, 1862-1865
+    MAXITERS, ABSTOL, RELTOL, FEASTOL, refinement, show = opt.maxiters, opt.abstol, opt.reltol, opt.feastol, opt.refinement, opt.show
+    correction = opt.correction
+    pb = _ipm.problem(q, G, h, None, A, b, P, qp=True)
+    n, p, ml, q_h, h_h, b_h = pb.n, pb.p, pb.cdim, pb.c, pb.h, pb.b
+    (Gp, Gi, Gx), (Ap, Ai, Ax), (Pp, Pi, Px) = pb.G, pb.A, pb.P
     if ml == 0:
         raise ValueError("coneqp on the GPU needs at least one inequality (dims['l'] > 0)")
-    Pp, Pi, Px = _lower_ccs(P, n)
-    p = 0
-    if A is not None:
-        p, na, Ap, Ai, Ax = base._as_ccs(A)
-        if na != n:
-            raise TypeError("'A' must have %d columns" % n)
-        b_h = np.asarray(b._a if isinstance(b, base.matrix) else b, dtype=np.float64).reshape(-1)
-        if b_h.size != p:
-            raise TypeError("'b' must have length %d" % p)
+    _lib.require_device()
     if kktsolver is not None:
         # the reference's plug-in point (coneprog.py:1969-1981): kktsolver(W) returns f(x, y, z) for the system with H = P; host
         # round trips per factorisation and solve (KKTUserHost, as under conelp)
         if not callable(kktsolver):
             raise ValueError("kktsolver must be a function W -> f(x, y, z) (the reference's named solvers are not part of this path: "
                              "'chol2' is what runs on the GPU by default)")
-        if p == 0:
-            Ap, Ai, Ax = np.zeros(n + 1, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0)
         kkt = KKTUserHost(ml, n, Gp, Gi, Gx, p, Ap, Ai, Ax, kktsolver)
     elif p > 0:
         kkt = _kkt_for("KKTGenEqDev+P", (ml, n, p), (Gp, Gi, Ap, Ai, Pp, Pi), chol_opts,
@@ -1287,7 +1031,7 @@ def coneqp(P, q, G, h, options=None, chol_opts=None, A=None, b=None, initvals=No
         resy0 = max(1.0, bv.nrm2())
         ksolve = kkt.solve
     else:
-        y = dy = ry = wy = wy2 = None
+        y = dy = ry = wy = wy2 = _ipm.NoVec()
         resy0 = 1.0
         if kktsolver is not None:
             ksolve = kkt.solve
@@ -1305,13 +1049,8 @@ def coneqp(P, q, G, h, options=None, chol_opts=None, A=None, b=None, initvals=No
     resz0 = max(1.0, hv.nrm2())
 
     def result(status, iters, gap, relgap, pcost, dcost, pres, dres, msg=None):
-        if show:                                         # coneprog.py:2222-2227, 2269
-            print(msg or "Optimal solution found.")
-        return {"x": x.get(), "y": y.get() if p else np.zeros(0), "s": s.get(), "z": z.get(), "status": status, "gap": gap,
-                "relative gap": relgap, "primal objective": pcost, "dual objective": dcost,
-                "primal infeasibility": pres, "dual infeasibility": dres,
-                "primal slack": -s.max_step(), "dual slack": -z.max_step(), "iterations": iters,
-                "factorizations": kkt.nfactor}
+        return _ipm.coneqp_result(show, status, x.get(), y.get() if p else np.zeros(0), s.get(), z.get(),
+                                  (gap, relgap, pcost, dcost, pres, dres), s.max_step(), z.max_step(), iters, kkt.nfactor, msg)
 
     # ---- starting point (coneprog.py:2044-2150)
     if initvals is None:
@@ -1341,10 +1080,7 @@ def coneqp(P, q, G, h, options=None, chol_opts=None, A=None, b=None, initvals=No
     else:
         # user-supplied values (coneprog.py:2108-2150): missing x, y default to 0, missing s, z to the cone's identity
         def _vec(v, length):
-            a = np.ascontiguousarray(np.asarray(v._a if isinstance(v, base.matrix) else v, dtype=np.float64).reshape(-1))
-            if a.size != length:
-                raise TypeError("initvals has the wrong dimensions")
-            return a
+            return _ipm.vector(v, "initvals", length)
         x.set(_vec(initvals["x"], n)) if "x" in initvals else x.fill(0.0)
         if "s" in initvals:
             s.set(_vec(initvals["s"], ml))
@@ -1385,21 +1121,7 @@ def coneqp(P, q, G, h, options=None, chol_opts=None, A=None, b=None, initvals=No
         tmp.mul(lmbda)
         vs.axpy(tmp, -1.0)
 
-    def f4(bx, by, bz, bs):
-        if refinement:
-            wx.copy_from(bx); wz.copy_from(bz); ws.copy_from(bs)
-            if p:
-                wy.copy_from(by)
-        f4_no_ir(bx, by, bz, bs)
-        for _ in range(refinement):
-            wx2.copy_from(wx); wz2.copy_from(wz); ws2.copy_from(ws)
-            if p:
-                wy2.copy_from(wy)
-            res(bx, by, bz, bs, wx2, wy2, wz2, ws2)
-            f4_no_ir(wx2, wy2, wz2, ws2)
-            bx.axpy(wx2); bz.axpy(wz2); bs.axpy(ws2)
-            if p:
-                by.axpy(wy2)
+    f4 = _ipm.f4(f4_no_ir, res, refinement, (wx, wy, wz, ws) if refinement else (), (wx2, wy2, wz2, ws2) if refinement else ())
 
     for iters in range(MAXITERS + 1):
         # residuals and objectives (coneprog.py:2167-2203): one reduction call for the five inner products
@@ -1422,13 +1144,11 @@ def coneqp(P, q, G, h, options=None, chol_opts=None, A=None, b=None, initvals=No
         relgap = gap / -pcost if pcost < 0.0 else (gap / dcost if dcost > 0.0 else None)
         pres, dres = max(resy / resy0, resz / resz0), resx / resx0
         if show:
-            if iters == 0:
-                print("% 10s% 12s% 10s% 8s% 7s" % ("pcost", "dcost", "gap", "pres", "dres"))
-            print("%2d: % 8.4e % 8.4e % 4.0e% 7.0e% 7.0e" % (iters, pcost, dcost, gap, pres, dres))
+            _ipm.progress(iters, pcost, dcost, gap, pres, dres)
         if (pres <= FEASTOL and dres <= FEASTOL and (gap <= ABSTOL or (relgap is not None and relgap <= RELTOL))) \
                 or iters == MAXITERS:
             if iters == MAXITERS:
-                return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, msg="Terminated (maximum number of iterations reached).")
+                return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, msg=_ipm.MAXITERS_MSG)
             return result("optimal", iters, gap, relgap, pcost, dcost, pres, dres)
 
         # scaling (coneprog.py:2230-2231) and KKT factorisation
@@ -1442,7 +1162,7 @@ def coneqp(P, q, G, h, options=None, chol_opts=None, A=None, b=None, initvals=No
         except ArithmeticError:
             if iters == 0:
                 raise ValueError("Rank(A) < p or Rank([P; A; G]) < n")
-            return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, msg="Terminated (singular KKT matrix).")
+            return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, msg=_ipm.SINGULAR_MSG)
 
         mu = gap / ml
         sigma, eta = 0.0, 0.0

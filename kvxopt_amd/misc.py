@@ -5,475 +5,214 @@ meaning and in-place semantics as the reference (src/python/misc.py, src/C/misc_
 entries scaled by W['dnl'], misc.py:262-270, 432-442, 48-60) is one more diagonal block in front of the 'l' block, so
 every kernel simply runs over mnl + ml entries.
 
-Host-array compatibility layer: arguments are host `matrix` objects (ours or kvxopt's); every
-operation runs through the HIP kernels of libkvxhip.so (upload, kernel, download).  The device-
-resident fast path for whole interior-point iterations is `kvxopt_amd.lp`.
+Host-array compatibility layer: arguments are host `matrix` objects (ours or kvxopt's); every operation uploads its
+vectors whole, calls the device operation of `kvxopt_amd.coneops` on the cached layout (`Dims`) of the cone vector and
+downloads what the reference's function modifies, with one synchronisation.  The device-resident paths for whole
+interior-point iterations are `kvxopt_amd.lp` and `kvxopt_amd.cone`.
 """
-import ctypes
-
 import numpy as np
 
-from . import _lib, base
-from ._lib import DeviceBuffer, lib, raise_for
-from .base import matrix, spmatrix
-
-
-class _SBlocks:
-    """Device tables of the 's' section of a vector: offsets of the m_k x m_k blocks, of their diagonals / eigenvalues and
-    of their packed lower triangles (csrc/kkt_s.hip: one workgroup per block, all blocks in one launch)."""
-
-    def __init__(self, sdims):
-        self.dims = [int(m) for m in sdims]
-        if any(m < 0 or m > 4096 for m in self.dims):
-            raise ValueError("semidefinite blocks must have an order between 0 and 4096 (one workgroup per block)")
-        self.ns = len(self.dims)
-        d = np.asarray(self.dims, dtype=np.int64)
-        self.off2, self.off1, self.offp = (np.zeros(self.ns + 1, dtype=np.int64) for _ in range(3))
-        np.cumsum(d * d, out=self.off2[1:])
-        np.cumsum(d, out=self.off1[1:])
-        np.cumsum(d * (d + 1) // 2, out=self.offp[1:])
-        self.tot2, self.tot1, self.totp = int(self.off2[-1]), int(self.off1[-1]), int(self.offp[-1])
-        self.d2, self.d1, self.dp = (DeviceBuffer.from_array(a) for a in (self.off2, self.off1, self.offp))
-
-    def split(self, flat):
-        """list of m_k x m_k matrices from the concatenated blocks"""
-        return [matrix(flat[self.off2[k]:self.off2[k + 1]].copy(), (m, m)) for k, m in enumerate(self.dims)]
-
-
-def _s_blocks(dims):
-    sd = [int(m) for m in (dims.get("s") or [])]
-    return _SBlocks(sd) if sd and sum(sd) else None
-
-
-def _cat(mats):
-    return np.concatenate([np.asarray(_buf(a)[0], dtype=np.float64) for a in mats]) if mats else np.zeros(0)
-
-
-def _scratch(n):
-    return DeviceBuffer(8 * max(int(n), 1))
-
-
-def _q_offsets(q):
-    """Device table of the cone boundaries inside the 'q' section: [0, q0, q0 + q1, ...]."""
-    off = np.zeros(len(q) + 1, dtype=np.int64)
-    np.cumsum(np.asarray(q, dtype=np.int64), out=off[1:])
-    return off, DeviceBuffer.from_array(off)
-
-
-def _q_apply(dims, m, call, *host_vecs):
-    """Run one 'q'-block kernel on the slices [m, m + sum(q)) of the host vectors: `call(nq, off_dev, *device slices)`;
-    the first vector is written back."""
-    q = list(dims.get("q") or [])
-    if not q:
-        return
-    off, doff = _q_offsets(q)
-    tot = int(off[-1])
-    bufs = [_buf(v)[0] for v in host_vecs]
-    devs = [_up(b[m:m + tot]) for b in bufs]
-    raise_for(call(len(q), doff.ptr, *[d.ptr for d in devs]))
-    _sync()
-    bufs[0][m:m + tot] = devs[0].download(np.float64, tot)
+from . import _lib, base, cone, coneops, lp
+from ._lib import lib, raise_for
+from .base import _full_pattern
+from .coneops import WDev, dims_for, dims_of
+from .devvec import DVec, SpMatDev
 
 
 def _buf(x):
-    return base._dense_buffer(x)
+    return base._dense_buffer(x)[0]
 
 
-def _up(a):
-    return DeviceBuffer.from_array(np.ascontiguousarray(a, dtype=np.float64))
+def _dims(dims, mnl=0):
+    """The device layout of a cone vector; the mnl leading nonlinear entries are more 'l' entries."""
+    _lib.require_device()
+    return dims_for(int(mnl or 0) + dims["l"], dims.get("q") or [], dims.get("s") or [])
 
 
 def _sync():
     raise_for(lib().kvx_dev_sync())
 
 
+def _copy_without_s(x, y, dims, mnl, offsetx, offsety):
+    """Without 's' blocks pack / unpack are the plain copy y := x, which needs no device; True when that was all."""
+    if any(dims.get("s") or []):
+        return False
+    n = mnl + dims["l"] + sum(dims.get("q") or [])
+    _buf(y)[offsety:offsety + n] = _buf(x)[offsetx:offsetx + n]
+    return True
+
+
 def compute_scaling(s, z, lmbda, dims, mnl=None):
-    """misc.py:250-352 (nonlinear, 'l' and 'q' blocks): W['d'] = sqrt(s./z), W['di'] = 1./d, lmbda = sqrt(s.*z); with
-    mnl given (cvxprog), the first mnl entries make W['dnl'], W['dnli'] by the same formulas; for every second-order cone
-    the unit-hyperbolic-norm vector W['v'][k] and W['beta'][k] with (beta_k (2 v_k v_k' - J)) z_k = lambda_k."""
-    k = 0 if mnl is None else int(mnl)
-    m = k + dims["l"]
-    sb, _ = _buf(s)
-    zb, _ = _buf(z)
-    lb, _ = _buf(lmbda)
-    _lib.require_device()
-    ds, dz = _up(sb[:m]), _up(zb[:m])
-    dd, ddi, dl = DeviceBuffer(8 * max(m, 1)), DeviceBuffer(8 * max(m, 1)), DeviceBuffer(8 * max(m, 1))
-    raise_for(lib().kvx_nt_compute_scaling_dev(m, ds.ptr, dz.ptr, dd.ptr, ddi.ptr, dl.ptr))
+    """misc.py:250-419: W['d'] = sqrt(s./z), W['di'] = 1./d, lmbda = sqrt(s.*z) on the 'l' entries; with mnl given (cvxprog),
+    the first mnl entries make W['dnl'], W['dnli'] by the same formulas; for every second-order cone the unit-hyperbolic-norm
+    vector W['v'][k] and W['beta'][k] with (beta_k (2 v_k v_k' - J)) z_k = lambda_k; for every 's' block r_k, rti_k = r_k^-T with
+    r_k' z_k r_k = r_k^-1 s_k r_k^-T = diag(lambda_k).  ArithmeticError (lapack.potrf's) on a block that is not positive
+    definite."""
+    D = _dims(dims, mnl)
+    W, lm = WDev(D), DVec(D.Nd)
+    ds, dz = DVec(D.N, _buf(s)[:D.N]), DVec(D.N, _buf(z)[:D.N])
+    bad = coneops.compute_scaling(D, ds, dz, W, lm)
     _sync()
-    d, di = dd.download(np.float64, m), ddi.download(np.float64, m)
-    W = {}
-    if mnl is not None:
-        W["dnl"], W["dnli"] = matrix(d[:k].copy(), (k, 1)), matrix(di[:k].copy(), (k, 1))
-    W.update({"d": matrix(d[k:].copy(), (m - k, 1)), "di": matrix(di[k:].copy(), (m - k, 1)),
-              "v": [], "beta": [], "r": [], "rti": []})
-    lb[:m] = dl.download(np.float64, m)
-    q = list(dims.get("q") or [])
-    if q:
-        # 'q' blocks (misc.py:290-352): hyperbolic Householder scaling beta_k (2 v_k v_k' - J), one workgroup per cone
-        off, doff = _q_offsets(q)
-        tot = int(off[-1])
-        dsq, dzq = _up(sb[m:m + tot]), _up(zb[m:m + tot])
-        dv, dlq, db = DeviceBuffer(8 * tot), DeviceBuffer(8 * tot), DeviceBuffer(8 * len(q))
-        raise_for(lib().kvx_ntq_compute_scaling_dev(len(q), doff.ptr, dsq.ptr, dzq.ptr, dv.ptr, db.ptr, dlq.ptr))
-        _sync()
-        vall = dv.download(np.float64, tot)
-        W["v"] = [matrix(vall[off[i]:off[i + 1]].copy(), (q[i], 1)) for i in range(len(q))]
-        W["beta"] = [float(b) for b in db.download(np.float64, len(q))]
-        lb[m:m + tot] = dlq.download(np.float64, tot)
-    S = _s_blocks(dims)
-    if S is not None:
-        # 's' blocks (misc.py:354-419): r_k' z_k r_k = r_k^-1 s_k r_k^-T = diag(lambda_k), rti_k = r_k^-T; lambda_k is the
-        # vector of singular values of Lz' Ls (descending), stored behind the 'q' part of lmbda
-        ind = m + sum(q)
-        dss, dzs = _up(sb[ind:ind + S.tot2]), _up(zb[ind:ind + S.tot2])
-        dr, drt, dls, wk = _scratch(S.tot2), _scratch(S.tot2), _scratch(S.tot1), _scratch(4 * S.tot2)
-        st = DeviceBuffer.from_array(np.array([_NOFAIL], dtype=np.int32))
-        raise_for(lib().kvx_nts_compute_scaling_dev(S.ns, S.d2.ptr, S.d1.ptr, dss.ptr, dzs.ptr, dr.ptr, drt.ptr, dls.ptr, wk.ptr, st.ptr))
-        _sync()
-        bad = int(st.download(np.int32, 1)[0])
-        if bad != _NOFAIL:
-            raise ArithmeticError(bad + 1)                  # lapack.potrf on a block that is not positive definite
-        W["r"], W["rti"] = S.split(dr.download(np.float64, S.tot2)), S.split(drt.download(np.float64, S.tot2))
-        lb[ind:ind + S.tot1] = dls.download(np.float64, S.tot1)
-    return W
-
-
-_NOFAIL = 2 ** 31 - 1
-
-
-def _diag_of(W, inverse=False):
-    """[dnl; d] (or the inverses) as one contiguous vector, and the length of the nonlinear part."""
-    d, _ = _buf(W["di"] if inverse else W["d"])
-    if "dnl" in W:
-        dn, _ = _buf(W["dnli"] if inverse else W["dnl"])
-        return np.concatenate([dn, d]), dn.size
-    return np.ascontiguousarray(d), 0
+    if bad is not None:
+        raise ArithmeticError(bad + 1)
+    _buf(lmbda)[:D.Nd] = lm.get()
+    return W.to_host(mnl)
 
 
 def update_scaling(W, lmbda, s, z):
-    """misc.py:422-634, in place.  Nonlinear and 'l' blocks: s:=sqrt(s), z:=sqrt(z), d:=d.*s./z, di:=1./d, lmbda:=s.*z
-    (W['dnl'], W['dnli'] likewise on the leading mnl entries); 'q' and 's' blocks below."""
-    dcat, k = _diag_of(W)
-    m = dcat.size
-    sb, _ = _buf(s)
-    zb, _ = _buf(z)
-    lb, _ = _buf(lmbda)
+    """misc.py:422-634, in place: W, lmbda and s, z (which leave as the reference leaves them: sqrt's on the 'l' entries, st / a
+    and zt / b in the 'q' cones, the singular vectors U and V' in the 's' blocks)."""
     _lib.require_device()
-    ds, dz, dd = _up(sb[:m]), _up(zb[:m]), _up(dcat)
-    ddi, dl = DeviceBuffer(8 * max(m, 1)), DeviceBuffer(8 * max(m, 1))
-    raise_for(lib().kvx_nt_update_scaling_dev(m, ds.ptr, dz.ptr, dd.ptr, ddi.ptr, dl.ptr))
+    D, k = dims_of(W)
+    Wd, lm = WDev(D).set_host(W), DVec(D.Nd, _buf(lmbda)[:D.Nd])
+    ds, dz = DVec(D.N, _buf(s)[:D.N]), DVec(D.N, _buf(z)[:D.N])
+    coneops.update_scaling(D, Wd, lm, ds, dz)
     _sync()
-    sb[:m] = ds.download(np.float64, m)
-    zb[:m] = dz.download(np.float64, m)
-    d, di = dd.download(np.float64, m), ddi.download(np.float64, m)
-    if k:
-        _buf(W["dnl"])[0][:] = d[:k]
-        _buf(W["dnli"])[0][:] = di[:k]
-    _buf(W["d"])[0][:] = d[k:]
-    _buf(W["di"])[0][:] = di[k:]
-    lb[:m] = dl.download(np.float64, m)
-    if W.get("v"):
-        # 'q' blocks (misc.py:467-580): s, z leave as st / a, zt / b; v, beta, lambda are updated
-        q = [int(_buf(v)[1][0]) for v in W["v"]]
-        off, doff = _q_offsets(q)
-        tot = int(off[-1])
-        dsq, dzq, dlq = _up(sb[m:m + tot]), _up(zb[m:m + tot]), DeviceBuffer(8 * tot)
-        dv = _up(np.concatenate([np.asarray(_buf(v)[0], dtype=np.float64) for v in W["v"]]))
-        db = _up(np.asarray(W["beta"], dtype=np.float64))
-        raise_for(lib().kvx_ntq_update_scaling_dev(len(q), doff.ptr, dsq.ptr, dzq.ptr, dv.ptr, db.ptr, dlq.ptr))
-        _sync()
-        sb[m:m + tot] = dsq.download(np.float64, tot)
-        zb[m:m + tot] = dzq.download(np.float64, tot)
-        lb[m:m + tot] = dlq.download(np.float64, tot)
-        vall = dv.download(np.float64, tot)
-        for i, v in enumerate(W["v"]):
-            _buf(v)[0][:] = vall[off[i]:off[i + 1]]
-        W["beta"][:] = [float(b) for b in db.download(np.float64, len(q))]
-    if W.get("r"):
-        # 's' blocks (misc.py:582-634): s_k, z_k hold the Cholesky factors Ls, Lz of the new iterates in the current scaling;
-        # with Lz' Ls = U diag(lambda_k) V':  r_k := r_k Ls V diag(lambda_k)^-1/2, rti_k := rti_k Lz U diag(lambda_k)^-1/2;
-        # s_k, z_k leave as U and V' (what lapack.gesvd stores there)
-        S = _SBlocks([int(_buf(r)[1][0]) for r in W["r"]])
-        ind = m + sum(int(_buf(v)[1][0]) for v in (W.get("v") or []))
-        dss, dzs = _up(sb[ind:ind + S.tot2]), _up(zb[ind:ind + S.tot2])
-        dr, drt = _up(_cat(W["r"])), _up(_cat(W["rti"]))
-        dls, wk = _scratch(S.tot1), _scratch(4 * S.tot2)
-        raise_for(lib().kvx_nts_update_scaling_dev(S.ns, S.d2.ptr, S.d1.ptr, dss.ptr, dzs.ptr, dr.ptr, drt.ptr, dls.ptr, wk.ptr))
-        _sync()
-        sb[ind:ind + S.tot2] = dss.download(np.float64, S.tot2)
-        zb[ind:ind + S.tot2] = dzs.download(np.float64, S.tot2)
-        lb[ind:ind + S.tot1] = dls.download(np.float64, S.tot1)
-        rall, tall = dr.download(np.float64, S.tot2), drt.download(np.float64, S.tot2)
-        for i in range(S.ns):
-            _buf(W["r"][i])[0][:] = rall[S.off2[i]:S.off2[i + 1]]
-            _buf(W["rti"][i])[0][:] = tall[S.off2[i]:S.off2[i + 1]]
+    _buf(s)[:D.N], _buf(z)[:D.N], _buf(lmbda)[:D.Nd] = ds.get(), dz.get(), lm.get()
+    for key, new in Wd.to_host(k if "dnl" in W else None).items():
+        if key == "beta":
+            W["beta"][:] = new
+        elif isinstance(new, list):
+            for old, blk in zip(W[key], new):
+                _buf(old)[:] = blk._a
+        else:
+            _buf(W[key])[:] = new._a
 
 
 def scale(x, W, trans="N", inverse="N"):
-    """misc_solvers.c:85-240 / misc.py:36-164.  Nonlinear and 'l' blocks: x := [dnl; d].*x ('N') or [dnli; di].*x ('I') for
-    every column of x (trans is irrelevant for a diagonal scaling); 'q' and 's' blocks below."""
-    w, _ = _diag_of(W, inverse != "N")
-    xb, size = _buf(x)
-    m = w.size
-    nq = len(W.get("v") or [])
-    nsb = len(W.get("r") or [])
-    if m == 0 and nq == 0 and nsb == 0:
-        return
+    """misc_solvers.c:85-240 / misc.py:36-164, every column of x: the 'l' (and nonlinear) entries times d or di, the 'q' cones by
+    beta_k (2 v_k v_k' - J) or its inverse, the 's' blocks x_k := r' X r ('N','N'), r X r' ('T','N'), rti X rti' ('N','I'),
+    rti' X rti ('T','I') with X the symmetric matrix in the lower triangle of x_k (only that triangle is written)."""
     _lib.require_device()
-    dx = _up(xb)
-    if m:
-        dw = _up(w)
-        raise_for(lib().kvx_nt_scale_dev(m, size[1], size[0], dx.ptr, dw.ptr))
-    if nq:
-        # 'q' blocks (misc_solvers.c:144-186): x_k := beta_k (2 v_k v_k' - J) x_k, or the inverse; symmetric, so `trans` is moot
-        q = [int(_buf(v)[1][0]) for v in W["v"]]
-        off, doff = _q_offsets(q)
-        dv = _up(np.concatenate([np.asarray(_buf(v)[0], dtype=np.float64) for v in W["v"]]))
-        db = _up(np.asarray(W["beta"], dtype=np.float64))
-        raise_for(lib().kvx_ntq_scale_dev(nq, doff.ptr, dv.ptr, db.ptr, dx.ptr + 8 * m, size[0], size[1], 1 if inverse != "N" else 0))
-    if nsb:
-        # 's' blocks (misc_solvers.c:188-240): x_k := r' X r ('N','N'), r X r' ('T','N'), rti X rti' ('N','I'), rti' X rti
-        # ('T','I'), X the symmetric matrix in the lower triangle of x_k; only the lower triangle is written
-        R = W["r"] if inverse == "N" else W["rti"]
-        S = _SBlocks([int(_buf(r)[1][0]) for r in R])
-        ind = m + sum(int(_buf(v)[1][0]) for v in (W.get("v") or []))
-        dR, wk = _up(_cat(R)), _scratch(S.tot2 * size[1])
-        form = 1 if (inverse == "N") == (trans == "T") else 0
-        raise_for(lib().kvx_nts_scale_dev(S.ns, S.d2.ptr, S.d1.ptr, dR.ptr, dx.ptr + 8 * ind, size[0], size[1], form, wk.ptr, S.tot2))
+    D, _ = dims_of(W)
+    xb, size = base._dense_buffer(x)
+    if D.N == 0:
+        return
+    dx, Wd = DVec(xb.size, xb), WDev(D).set_host(W)
+    coneops.scale(D, Wd, dx.ptr, trans, inverse, ncols=size[1], ld=size[0])
     _sync()
-    xb[:] = dx.download(np.float64, xb.size)
+    xb[:] = dx.get()
+
+
+def _apply(op, D, x, nx, y, ny, **kw):
+    """x[:nx] := op(x[:nx], y[:ny]) through the device."""
+    dx, dy = DVec(nx, _buf(x)[:nx]), DVec(ny, _buf(y)[:ny])
+    op(D, dx.ptr, dy.ptr, **kw)
+    _sync()
+    _buf(x)[:nx] = dx.get()
+    return dy
 
 
 def scale2(lmbda, x, dims, mnl=0, inverse="N"):
-    """misc_solvers.c:256-397.  Nonlinear and 'l' blocks: x := x./lmbda ('N') or x.*lmbda ('I'); 'q' blocks: the hyperbolic
-    form (:301-341); 's' blocks: x_k(i, j) divided ('N') or multiplied ('I') by sqrt(l_i) sqrt(l_j) (:343-397)."""
-    m = mnl + dims["l"]
-    lb, _ = _buf(lmbda)
-    xb, _ = _buf(x)
-    _lib.require_device()
-    if m:
-        dx, dl = _up(xb[:m]), _up(lb[:m])
-        raise_for(lib().kvx_nt_scale2_dev(m, dl.ptr, dx.ptr, 1 if inverse == "I" else 0))
-        _sync()
-        xb[:m] = dx.download(np.float64, m)
-    inv = 1 if inverse == "I" else 0                      # 'q' blocks: misc_solvers.c:301-341
-    _q_apply(dims, m, lambda nq, off, dxq, dlq: lib().kvx_ntq_scale2_dev(nq, off, dlq, dxq, inv), x, lmbda)
-    S = _s_blocks(dims)
-    if S is not None:
-        ind = m + sum(dims.get("q") or [])
-        dxs, dls = _up(xb[ind:ind + S.tot2]), _up(lb[ind:ind + S.tot1])
-        raise_for(lib().kvx_nts_scale2_dev(S.ns, S.d2.ptr, S.d1.ptr, dls.ptr, dxs.ptr, inv))
-        _sync()
-        xb[ind:ind + S.tot2] = dxs.download(np.float64, S.tot2)
-
-
-def _binary(kernel, x, y, m):
-    xb, _ = _buf(x)
-    yb, _ = _buf(y)
-    if m == 0:
-        return
-    _lib.require_device()
-    dx, dy = _up(xb[:m]), _up(yb[:m])
-    raise_for(kernel(m, dx.ptr, dy.ptr))
-    _sync()
-    xb[:m] = dx.download(np.float64, m)
+    """misc_solvers.c:256-397: x := x./lmbda ('N') or x.*lmbda ('I') on the 'l' entries, the hyperbolic form in the 'q' cones,
+    x_k(i, j) divided or multiplied by sqrt(l_i) sqrt(l_j) in the 's' blocks."""
+    D = _dims(dims, mnl)
+    _apply(lambda D, xp, lp_: coneops.scale2(D, lp_, xp, inverse), D, x, D.N, lmbda, D.Nd)
 
 
 def sprod(x, y, dims, mnl=0, diag="N"):
-    """misc_solvers.c:634-770: x := y o x.  'l' block: x.*y; 'q' blocks :671-700; 's' blocks :700-770: the lower triangle of
-    (Y X + X Y) / 2, with y holding full blocks (diag 'N'; their upper triangles are filled in as the reference does) or
-    only their diagonals (diag 'D')."""
-    _binary(lib().kvx_nt_sprod_dev, x, y, mnl + dims["l"])
-    _q_apply(dims, mnl + dims["l"], lambda nq, off, dx, dy: lib().kvx_ntq_prod_dev(nq, off, dx, dy, 0), x, y)   # misc_solvers.c:671-700
-    S = _s_blocks(dims)
-    if S is not None:
-        ind = mnl + dims["l"] + sum(dims.get("q") or [])
-        xb, yb = _buf(x)[0], _buf(y)[0]
-        dxs = _up(xb[ind:ind + S.tot2])
-        if diag == "N":
-            dys, wk = _up(yb[ind:ind + S.tot2]), _scratch(S.tot2)
-            raise_for(lib().kvx_nts_prod_dev(S.ns, S.d2.ptr, S.d1.ptr, dxs.ptr, dys.ptr, 0, wk.ptr))
-            _sync()
-            yb[ind:ind + S.tot2] = dys.download(np.float64, S.tot2)
-        else:
-            dys = _up(yb[ind:ind + S.tot1])
-            raise_for(lib().kvx_nts_prod_dev(S.ns, S.d2.ptr, S.d1.ptr, dxs.ptr, dys.ptr, 1, None))
-            _sync()
-        xb[ind:ind + S.tot2] = dxs.download(np.float64, S.tot2)
+    """misc_solvers.c:634-770: x := y o x; the 's' blocks of y are full (diag 'N'; their upper triangles are filled in as the
+    reference does) or diagonals only (diag 'D')."""
+    D = _dims(dims, mnl)
+    dy = _apply(coneops.sprod, D, x, D.N, y, D.N if diag == "N" else D.Nd, diag=diag)
+    if diag == "N":
+        _buf(y)[:D.N] = dy.get()
 
 
 def sinv(x, y, dims, mnl=0):
-    """misc_solvers.c:775-882: the inverse of x := y o x.  'l' block: x./y; 'q' blocks :803-835; 's' blocks :845-882 (y holds
-    only the diagonals): the lower triangle of x_k divided entrywise by (y_i + y_j) / 2."""
-    _binary(lib().kvx_nt_sinv_dev, x, y, mnl + dims["l"])
-    _q_apply(dims, mnl + dims["l"], lambda nq, off, dx, dy: lib().kvx_ntq_prod_dev(nq, off, dx, dy, 1), x, y)   # misc_solvers.c:803-835
-    S = _s_blocks(dims)
-    if S is not None:
-        ind = mnl + dims["l"] + sum(dims.get("q") or [])
-        xb, yb = _buf(x)[0], _buf(y)[0]
-        dxs, dys = _up(xb[ind:ind + S.tot2]), _up(yb[ind:ind + S.tot1])
-        raise_for(lib().kvx_nts_prod_dev(S.ns, S.d2.ptr, S.d1.ptr, dxs.ptr, dys.ptr, 2, None))
-        _sync()
-        xb[ind:ind + S.tot2] = dxs.download(np.float64, S.tot2)
+    """misc_solvers.c:775-882: the inverse of x := y o x; y holds only the diagonals of its 's' blocks."""
+    D = _dims(dims, mnl)
+    _apply(coneops.sinv, D, x, D.N, y, D.Nd)
 
 
 def ssqr(x, y, dims, mnl=0):
-    """misc.py:945-959: x := y o y; the 's' components of x and y are diagonal and only the diagonals are stored, so they are
-    squared entrywise like the 'l' block."""
-    _binary(lib().kvx_nt_ssqr_dev, x, y, mnl + dims["l"])
-    _q_apply(dims, mnl + dims["l"], lambda nq, off, dx, dy: lib().kvx_ntq_prod_dev(nq, off, dx, dy, 2), x, y)   # misc.py:951-959
-    ns1 = sum(int(m) for m in (dims.get("s") or []))
-    if ns1:
-        ind = mnl + dims["l"] + sum(dims.get("q") or [])
-        xb, yb = _buf(x)[0], _buf(y)[0]
-        dxs, dys = _up(xb[ind:ind + ns1]), _up(yb[ind:ind + ns1])
-        raise_for(lib().kvx_nt_ssqr_dev(ns1, dxs.ptr, dys.ptr))
-        _sync()
-        xb[ind:ind + ns1] = dxs.download(np.float64, ns1)
+    """misc.py:945-959: x := y o y; the 's' components of x and y are diagonal and only the diagonals are stored."""
+    D = _dims(dims, mnl)
+    _apply(coneops.ssqr, D, x, D.Nd, y, D.Nd)
 
 
 def sdot(x, y, dims, mnl=0):
     """misc_solvers.c:991-1046: sum_i x_i*y_i over the nonlinear, 'l' and 'q' entries plus, per 's' block, the trace inner
-    product of the symmetric matrices stored in the lower triangles (diagonal + twice the strict lower part)."""
-    m = mnl + dims["l"] + sum(dims.get("q") or [])          # misc_solvers.c:1009-1012: one dot over the 'l' and 'q' entries
-    xb, _ = _buf(x)
-    yb, _ = _buf(y)
-    S = _s_blocks(dims)
-    if m == 0 and S is None:
-        return 0.0
-    _lib.require_device()
-    a = 0.0
-    if m:
-        dx, dy = _up(xb[:m]), _up(yb[:m])
-        r = ctypes.c_double()
-        raise_for(lib().kvx_nt_sdot_dev(m, dx.ptr, dy.ptr, ctypes.byref(r)))
-        a = r.value
-    if S is not None:
-        dxs, dys, dout = _up(xb[m:m + S.tot2]), _up(yb[m:m + S.tot2]), _scratch(S.ns)
-        raise_for(lib().kvx_nts_dot_dev(S.ns, S.d2.ptr, S.d1.ptr, dxs.ptr, dys.ptr, dout.ptr))
-        _sync()
-        for v in dout.download(np.float64, S.ns):          # block after block, as the reference accumulates
-            a += float(v)
-    return a
+    product of the symmetric matrices stored in the lower triangles."""
+    D = _dims(dims, mnl)
+    dx, dy = DVec(D.N, _buf(x)[:D.N]), DVec(D.N, _buf(y)[:D.N])      # (held until the result is on the host)
+    return coneops.sdot(D, dx.ptr, dy.ptr) if D.N else 0.0
 
 
 def max_step(x, dims, mnl=0, sigma=None):
-    """misc_solvers.c:1052-1160: min {t | x + t e >= 0} = max(max_i(-x_i), max_k(|x_k1| - x_k0), max_k(-lambda_min(x_k)));
-    0.0 for an empty x (misc_solvers.c:1099).  With `sigma` the eigenvalues of the 's' blocks (ascending) are stored there and
-    their eigenvectors replace the blocks of x (:1128-1133)."""
-    m = mnl + dims["l"]
-    q = list(dims.get("q") or [])
-    xb, _ = _buf(x)
-    S = _s_blocks(dims)
-    if m + sum(q) == 0 and S is None:
-        return 0.0
-    _lib.require_device()
-    t = -np.finfo(np.float32).max                        # the reference starts from -FLT_MAX (misc_solvers.c:1063)
-    if m:
-        dx = _up(xb[:m])
-        r = ctypes.c_double()
-        raise_for(lib().kvx_nt_max_step_dev(m, dx.ptr, ctypes.byref(r)))
-        t = max(t, r.value)
-    if q:
-        off, doff = _q_offsets(q)
-        tot = int(off[-1])
-        dxq, dout = _up(xb[m:m + tot]), DeviceBuffer(8 * len(q))
-        raise_for(lib().kvx_ntq_max_step_dev(len(q), doff.ptr, dxq.ptr, dout.ptr))
-        _sync()
-        t = max(t, float(dout.download(np.float64, len(q)).max()))
-    if S is not None:
-        ind = m + sum(q)
-        dxs, dout, wk = _up(xb[ind:ind + S.tot2]), _scratch(S.ns), _scratch(3 * S.tot2 + 2 * S.tot1)
-        dsg = _scratch(S.tot1) if sigma is not None else None
-        raise_for(lib().kvx_nts_max_step_dev(S.ns, S.d2.ptr, S.d1.ptr, dxs.ptr, dsg.ptr if dsg else None, dout.ptr, wk.ptr))
-        _sync()
-        t = max(t, float(dout.download(np.float64, S.ns).max()))
-        if sigma is not None:
-            _buf(sigma)[0][:S.tot1] = dsg.download(np.float64, S.tot1)
-            xb[ind:ind + S.tot2] = dxs.download(np.float64, S.tot2)
+    """misc_solvers.c:1052-1160: min {t | x + t e >= 0}; 0.0 for an empty x.  With `sigma` the eigenvalues of the 's' blocks
+    (ascending) are stored there and their eigenvectors replace the blocks of x."""
+    D = _dims(dims, mnl)
+    dx = DVec(D.N, _buf(x)[:D.N])
+    dsg = DVec(D.tot1) if sigma is not None else None
+    t = coneops.max_step(D, dx.ptr, sigma=dsg)
+    if sigma is not None and D.tot2:
+        _buf(sigma)[:D.tot1] = dsg.get()
+        _buf(x)[:D.N] = dx.get()
     return t
 
 
 # ---- storage helpers of the 's' blocks (misc_solvers.c:412-632, 887-988) -------------------------------------------------
-def _s_section(dims, mnl):
-    return mnl + dims["l"] + sum(dims.get("q") or [])
-
-
 def pack(x, y, dims, mnl=0, offsetx=0, offsety=0):
     """misc_solvers.c:412-468: y := x with the 's' blocks in packed storage (lower triangles by columns, off-diagonal
     entries scaled by sqrt(2))."""
-    xb, yb = _buf(x)[0], _buf(y)[0]
-    nlq = _s_section(dims, mnl)
-    yb[offsety:offsety + nlq] = xb[offsetx:offsetx + nlq]
-    S = _s_blocks(dims)
-    if S is None:
+    if _copy_without_s(x, y, dims, mnl, offsetx, offsety):
         return
-    _lib.require_device()
-    dfull, dpk = _up(xb[offsetx + nlq:offsetx + nlq + S.tot2]), _scratch(S.totp)
-    raise_for(lib().kvx_nts_pack_dev(S.ns, S.d2.ptr, S.d1.ptr, S.dp.ptr, dfull.ptr, dpk.ptr, 0))
+    D = _dims(dims, mnl)
+    dx, dy = DVec(D.N, _buf(x)[offsetx:offsetx + D.N]), DVec(D.Np)
+    coneops.pack(D, dx.ptr, dy.ptr, 0)
     _sync()
-    yb[offsety + nlq:offsety + nlq + S.totp] = dpk.download(np.float64, S.totp)
+    _buf(y)[offsety:offsety + D.Np] = dy.get()
 
 
 def pack2(x, dims, mnl=0):
     """misc_solvers.c:476-544: in-place pack of every column of the matrix x (the diagonal entries are copied as they are)."""
-    xb, size = _buf(x)
-    S = _s_blocks(dims)
-    if S is None:
+    if not any(dims.get("s") or []):
         return
-    _lib.require_device()
-    nlq = _s_section(dims, mnl)
+    D = _dims(dims, mnl)
+    xb, size = base._dense_buffer(x)
     X = xb.reshape(size, order="F")
+    dx, dp = DVec(xb.size, xb), DVec(D.Np)
     for c in range(size[1]):
-        col = X[:, c]
-        dfull, dpk = _up(col[nlq:nlq + S.tot2]), _scratch(S.totp)
-        raise_for(lib().kvx_nts_pack_dev(S.ns, S.d2.ptr, S.d1.ptr, S.dp.ptr, dfull.ptr, dpk.ptr, 2))
-        _sync()
-        col[nlq:nlq + S.totp] = dpk.download(np.float64, S.totp)
+        coneops.pack(D, dx.ptr + 8 * c * size[0], dp.ptr, 2)
+        X[:D.Np, c] = dp.get()
 
 
 def unpack(x, y, dims, mnl=0, offsetx=0, offsety=0):
     """misc_solvers.c:552-608: y := x with the 's' blocks unpacked into the lower triangles (off-diagonal entries scaled by
     1/sqrt(2)); the strict upper triangles of y are not touched."""
-    xb, yb = _buf(x)[0], _buf(y)[0]
-    nlq = _s_section(dims, mnl)
-    yb[offsety:offsety + nlq] = xb[offsetx:offsetx + nlq]
-    S = _s_blocks(dims)
-    if S is None:
+    if _copy_without_s(x, y, dims, mnl, offsetx, offsety):
         return
-    _lib.require_device()
-    dfull, dpk = _up(yb[offsety + nlq:offsety + nlq + S.tot2]), _up(xb[offsetx + nlq:offsetx + nlq + S.totp])
-    raise_for(lib().kvx_nts_pack_dev(S.ns, S.d2.ptr, S.d1.ptr, S.dp.ptr, dfull.ptr, dpk.ptr, 1))
+    D = _dims(dims, mnl)
+    dx, dy = DVec(D.Np, _buf(x)[offsetx:offsetx + D.Np]), DVec(D.N, _buf(y)[offsety:offsety + D.N])
+    coneops.pack(D, dy.ptr, dx.ptr, 1)
     _sync()
-    yb[offsety + nlq:offsety + nlq + S.tot2] = dfull.download(np.float64, S.tot2)
+    _buf(y)[offsety:offsety + D.N] = dy.get()
 
 
-def _tri(x, sdims, offset, mode):
-    S = _SBlocks(sdims) if sdims and sum(sdims) else None
-    if S is None:
+def _tri(x, dims, offset, mode):
+    if not any(dims.get("s") or []):
         return
-    _lib.require_device()
-    xb = _buf(x)[0]
-    d = _up(xb[offset:offset + S.tot2])
-    raise_for(lib().kvx_nts_tri_dev(S.ns, S.d2.ptr, S.d1.ptr, d.ptr, mode))
+    D = _dims(dims)
+    d = DVec(D.N, _buf(x)[offset:offset + D.N])
+    coneops.tri(D, d.ptr, mode)
     _sync()
-    xb[offset:offset + S.tot2] = d.download(np.float64, S.tot2)
+    _buf(x)[offset:offset + D.N] = d.get()
 
 
 def symm(x, n, offset=0):
     """misc_solvers.c:610-632: fills in the upper triangle of the n x n symmetric matrix stored at x[offset:] ('L' storage)."""
-    _tri(x, [int(n)], offset, 0)
+    _tri(x, {"l": 0, "s": [int(n)]}, offset, 0)
 
 
 def trisc(x, dims, offset=0):
     """misc_solvers.c:887-938: upper triangles of the 's' blocks := 0, strict lower triangles scaled by 2."""
-    _tri(x, [int(m) for m in (dims.get("s") or [])], offset + dims["l"] + sum(dims.get("q") or []), 1)
+    _tri(x, dims, offset, 1)
 
 
 def triusc(x, dims, offset=0):
     """misc_solvers.c:940-988: strict lower triangles of the 's' blocks scaled by 1/2."""
-    _tri(x, [int(m) for m in (dims.get("s") or [])], offset + dims["l"] + sum(dims.get("q") or []), 2)
+    _tri(x, dims, offset, 2)
 
 
 class _Chol2Device:
@@ -483,7 +222,6 @@ class _Chol2Device:
     too (misc.py:1405-1432) -- and refilled with new values afterwards."""
 
     def __init__(self, G, A, mnl, Df, H, with_A_rows):
-        from . import lp
         gm, n, gcp, gri, gv = base._as_ccs(G)
         self.n, self.ml, self.mnl = n, gm, mnl
         self.p = A.size[0]
@@ -528,10 +266,10 @@ class _Chol2Device:
         else:
             self.kkt = lp.KKTGenEqDev(self.mj, n, self.Jp, self.Ji, Jx, self.p, acp, ari, av, None, Hp, Hi, Hx)
             self.J, self.chol = self.kkt.G, self.kkt.S
-        self.Adev = lp.SpMatDev(am, an, acp, ari, av) if (with_A_rows and self.p) else None
-        self.w = lp.DVec(max(self.mj, 1))
-        self.x, self.z = lp.DVec(max(n, 1)), lp.DVec(max(self.mj, 1))
-        self.y = lp.DVec(max(self.p, 1))
+        self.Adev = SpMatDev(am, an, acp, ari, av) if (with_A_rows and self.p) else None
+        self.w = DVec(max(self.mj, 1))
+        self.x, self.z = DVec(max(n, 1)), DVec(max(self.mj, 1))
+        self.y = DVec(max(self.p, 1))
         self._first = True
 
     def _values(self, Df):
@@ -546,8 +284,8 @@ class _Chol2Device:
     def refactor(self, W, H, Df):
         """New weights (and Df / H values) on the fixed patterns; numeric refactorisation.  ArithmeticError if S (or K) is
         not positive definite."""
-        wl = [np.asarray(_buf(W["dnli"])[0], dtype=np.float64)[:self.mnl]] if self.mnl else []
-        wl.append(np.asarray(_buf(W["di"])[0], dtype=np.float64)[:self.ml])
+        wl = [np.asarray(_buf(W["dnli"]), dtype=np.float64)[:self.mnl]] if self.mnl else []
+        wl.append(np.asarray(_buf(W["di"]), dtype=np.float64)[:self.ml])
         if self.with_A_rows:
             wl.append(np.ones(self.p))
         w = np.concatenate(wl) if self.mj else np.zeros(1)
@@ -569,7 +307,7 @@ class _Chol2Device:
 
     def solve(self, x, y, z):
         """(x, y, z) := (ux, uy, W uz) of the KKT system, host vectors in and out; the arithmetic stays on the device."""
-        xb, yb, zb = _buf(x)[0], _buf(y)[0], _buf(z)[0]
+        xb, yb, zb = _buf(x), _buf(y), _buf(z)
         n, p, m = self.n, self.p, self.mnl + self.ml
         self.x.set(xb[:n])
         zz = np.zeros(max(self.mj, 1))
@@ -585,20 +323,6 @@ class _Chol2Device:
             self.kkt.solve(self.x, self.z)
         xb[:n] = self.x.get()[:n]
         zb[:m] = self.z.get()[:m]
-
-
-def _full_pattern(M, lower=False):
-    """A dense `matrix` as an spmatrix with every entry (or every entry of the lower triangle) stored; anything else unchanged."""
-    if not isinstance(M, matrix):
-        return M
-    r, c = M.size
-    D = np.asarray(M.a, dtype=np.float64).reshape(r, c)
-    if lower:
-        I, J = np.nonzero(np.tril(np.ones((r, c), dtype=bool)).T)       # column by column
-        I, J = J, I
-        return spmatrix(D[I, J], I, J, (r, c))
-    return spmatrix.from_ccs(r, c, np.arange(c + 1, dtype=np.int64) * r, np.tile(np.arange(r, dtype=np.int64), c),
-                             np.ascontiguousarray(D.T).reshape(-1))
 
 
 def kkt_chol2(G, dims, A, mnl=0):
@@ -667,13 +391,12 @@ def kkt_chol(G, dims, A, mnl=0):
     The first call fixes the pattern of H; a later call with the same pattern refreshes its values only, one with another pattern
     (or H appearing or disappearing) builds a new plan and analysis.  Host vectors in and out, arithmetic on the device.  The
     nonlinear block (mnl > 0) and Df are not part of this path."""
-    from . import cone, lp
     if mnl:
         raise NotImplementedError("misc.kkt_chol on the GPU: the nonlinear block (mnl > 0) is not supported")
     dims = {"l": dims["l"], "q": list(dims.get("q") or []), "s": list(dims.get("s") or [])}
-    D = cone.Dims(dims)
-    _, n, Gp, Gi, Gx = cone._ccs(G)
-    p, _, Ap, Ai, Ax = cone._ccs(A)
+    D = coneops.Dims(dims)
+    _, n, Gp, Gi, Gx = base.ccs(G)
+    p, _, Ap, Ai, Ax = base.ccs(A)
     state = {"kkt": None, "W": None, "hpat": None}
 
     def factor(W, H=None, Df=None):
@@ -682,20 +405,20 @@ def kkt_chol(G, dims, A, mnl=0):
         _lib.require_device()
         Hp = Hi = Hx = hpat = None
         if H is not None:
-            Hp, Hi, Hx = cone.lower_ccs(H, n, "H")
+            Hp, Hi, Hx = base.lower_ccs(H, n, "H")
             hpat = (Hp.tobytes(), Hi.tobytes())
         if state["kkt"] is None or hpat != state["hpat"]:
             state["kkt"] = cone.KKTConeDev(D, n, Gp, Gi, Gx, p, Ap, Ai, Ax, None, Hp, Hi, Hx)
             state["hpat"] = hpat
-            state["W"] = cone.WDev(D)
-            state["x"], state["y"], state["z"] = lp.DVec(n), lp.DVec(p), lp.DVec(D.N)
+            state["W"] = WDev(D)
+            state["x"], state["y"], state["z"] = DVec(n), DVec(p), DVec(D.N)
         elif H is not None:
             state["kkt"].set_hessian(Hx)
         state["W"].set_host(W)
         state["kkt"].factor(state["W"])
 
         def solve(x, y, z):
-            xb, yb, zb = _buf(x)[0], _buf(y)[0], _buf(z)[0]
+            xb, yb, zb = _buf(x), _buf(y), _buf(z)
             X, Y, Z = state["x"], state["y"], state["z"]
             X.set(xb[:n]); Z.set(zb[:D.N])
             if p:

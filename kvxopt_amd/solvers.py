@@ -81,12 +81,12 @@ def _stack(blocks, n):
     """[B_0; B_1; ...] (dense or sparse, each with n columns) as one CCS spmatrix."""
     rows, cols, vals, off = [], [], [], 0
     for B in blocks:
-        m, nb, cp, ri, v = _cone._ccs(B)
+        m, nb, cp, ri, v = _base.ccs(B)
         if nb != n:
             raise TypeError("the constraint matrices must have %d columns" % n)
-        rows.append(np.asarray(ri, dtype=np.int64) + off)
-        cols.append(np.repeat(np.arange(n, dtype=np.int64), np.diff(np.asarray(cp, dtype=np.int64))))
-        vals.append(np.asarray(v, dtype=np.float64))
+        rows.append(ri + off)
+        cols.append(np.repeat(np.arange(n, dtype=np.int64), np.diff(cp)))
+        vals.append(v)
         off += m
     r = np.concatenate(rows) if rows else np.zeros(0, np.int64)
     c = np.concatenate(cols) if cols else np.zeros(0, np.int64)
@@ -96,13 +96,11 @@ def _stack(blocks, n):
     return _base.spmatrix.from_ccs(off, n, cp, r[order], (np.concatenate(vals) if vals else np.zeros(0))[order])
 
 
-def _flat(v):
-    return np.asarray(_base._dense_buffer(v)[0], dtype=np.float64).reshape(-1) if not isinstance(v, np.ndarray) else \
-        np.asarray(v, dtype=np.float64).reshape(-1, order="F")
+_flat = _base.flat
 
 
 def _nrows(B):
-    return _cone._ccs(B)[0]
+    return _base.ccs(B)[0]
 
 
 def _common(sol, keys):
