@@ -471,6 +471,27 @@ void kvx_cone_free(kvx_cone *C);
 int kvx_vec_scatter_dev(int64_t n, const double *x_dev, const int64_t *idx_dev, double *y_dev);
 int kvx_nts_colscale_dev(int64_t ns, const int64_t *off2_dev, const int64_t *off1_dev, double *x_dev, const double *w_dev);
 
+/* ---- geometric programs: the log-sum-exp blocks of solvers.gp (cvxprog.py:2094-2153, the Fgp closure) --------------------
+ * f_i(x) = log sum_k exp(F_i x + g_i)_k for the nblk = m + 1 blocks of K[i] rows each of F (sum K rows, n columns, CCS; rows
+ * inside a column in any order).  The plan reorders F by blocks (a CSR view for F x + g, the entries of a block in a column as
+ * one segment) and fixes two patterns: Df ((m + 1) x n, CCS): row i holds the columns met by the rows of block i; H (n x n,
+ * lower CCS): the union over the blocks -- block 0, the objective, included: it enters H through z[0] (cvxprog.py:2148-2150) --
+ * of the cliques on those column sets.  An entry of F stored twice is KVX_EINVAL.  Host only. */
+typedef struct kvx_gp kvx_gp;
+int kvx_gp_plan(int64_t nblk, const int64_t *K, int64_t n, const int64_t *Fp, const int64_t *Fi, kvx_gp **out);
+/* the two patterns (Dfp, Hp: n + 1; Dfi: dnz; Hi: hnz; every pointer may be NULL, e.g. to query dnz and hnz first) */
+int kvx_gp_pattern(kvx_gp *P, int64_t *dnz, int64_t *Dfp, int64_t *Dfi, int64_t *hnz, int64_t *Hp, int64_t *Hi);
+/* cvxprog.py:2106-2153: y = F x + g (Fx_dev: the values on the planned (Fp, Fi)); per block the maximum, exp(y - max), the sum,
+ * f_dev[i] = max + log(sum), y normalised; Dfx_dev[dnz] := the values of Df = [y_i' F_i] on the plan's pattern.  With z_dev
+ * (m + 1 weights) Hx_dev[hnz] := sum_i z_i F_i' (diag(y_i) - y_i y_i') F_i on the plan's lower pattern, formed as the reference
+ * forms it from the centred factors diag(y_i)^1/2 (F_i - 1 Df_i) (FP64 MFMA Gram tiles), the blocks of an entry summed in
+ * order.  z_dev == NULL (the line-search form F(x)): Hx_dev is not touched.  A block of one term gives y = 1, Df_i = F_i and
+ * a zero Hessian term exactly.  No floating-point atomics: a second call on the same inputs gives the same bytes.  KVX_EDEVICE
+ * without a GPU (no CPU fallback).  Null stream, enqueue only. */
+int kvx_gp_eval_dev(kvx_gp *P, const double *Fx_dev, const double *g_dev, const double *x_dev, const double *z_dev, double *f_dev,
+                    double *Dfx_dev, double *Hx_dev);
+void kvx_gp_free(kvx_gp *P);
+
 /* ---- dense helpers of the equality-constrained KKT solve with a general S (misc.py:1476-1487, 1545): K = A S^-1 A' formed
  * as a dense p x p matrix from X = S^-1 A' (kvx_chol_solve_dev with nrhs = p) when p is moderate ------------------------- */
 /* Y(j, c) = sum_i A(i, j) X(i, c) for the CCS matrix A with n columns and every column c < ncols of the dense X */

@@ -1,8 +1,8 @@
-"""Front matter shared by the four interior-point drivers (lp.conelp, lp.coneqp, cone.conelp, cone.coneqp): option defaults
-and the reference's checks of them, conversion and size checks of the problem data, the operators x -> G x, A x, the
-iterative-refinement wrappers around a driver's Newton solve, and the result dictionaries with the progress and closing lines
-(coneprog.py:425-575, 1211-1235, 1768-1975, 2330-2347).  `options` and `problem` are pure host code: they run before a device is
-asked for."""
+"""Front matter shared by the interior-point drivers (lp.conelp, lp.coneqp, cone.conelp, cone.coneqp, and cvx.cpl for its
+options, refinement wrapper and closing lines): option defaults and the reference's checks of them, conversion and size checks
+of the problem data, the operators x -> G x, A x, the iterative-refinement wrappers around a driver's Newton solve, and the
+result dictionaries with the progress and closing lines (coneprog.py:425-575, 1211-1235, 1768-1975, 2330-2347;
+cvxprog.py:392-424, 939-956).  `options` and `problem` are pure host code: they run before a device is asked for."""
 import types
 
 import numpy as np

@@ -205,6 +205,10 @@ _SIGS = {
     "kvx_cone_plan_h": (ctypes.c_int, [i64, i64, i64p, i64, i64p, i64, i64p, i64p, i64p, i64p, ctypes.POINTER(vp)]),
     "kvx_cone_assemble_h_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "kvx_cone_free": (None, [vp]),
+    "kvx_gp_plan": (ctypes.c_int, [i64, i64p, i64, i64p, i64p, ctypes.POINTER(vp)]),
+    "kvx_gp_pattern": (ctypes.c_int, [vp, i64p, i64p, i64p, i64p, i64p, i64p]),
+    "kvx_gp_eval_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "kvx_gp_free": (None, [vp]),
     "kvx_vec_scatter_dev": (ctypes.c_int, [i64, vp, vp, vp]),
     "kvx_nts_colscale_dev": (ctypes.c_int, [i64, vp, vp, vp, vp]),
     "kvx_spmm_t_dev": (ctypes.c_int, [i64, i64, vp, vp, vp, vp, i64, vp, i64]),

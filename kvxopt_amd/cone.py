@@ -138,6 +138,13 @@ class KKTConeDev:
         if Hx.size:
             self.Hx.set(Hx)
 
+    def set_hessian_dev(self, src_ptr, map_dev, count):
+        """New values of H from HBM: Hx[map[i]] := src[i] for the count entries of a device index map (kvx_vec_scatter_dev)."""
+        if self.Hx is None:
+            raise ValueError("the KKT system was built without an H pattern")
+        if count:
+            raise_for(lib().kvx_vec_scatter_dev(count, src_ptr, map_dev.ptr, self.Hx.ptr))
+
     def assemble(self, W):
         self.plan.assemble(self.G.vx, W, self.Sx, self.Hx)
 

@@ -131,6 +131,22 @@ class SpMatDev:
             self.vx.upload(values)
             self.tvx.upload(np.ascontiguousarray(values[self._order]))
 
+    def value_maps(self, positions):
+        """Device index maps of the entries at the CCS `positions`, into the values and into the transposed copy: the operand of
+        scatter_values for a caller whose values of those entries live in HBM (kvxopt_amd.cvx: the rows Df of [Df; G])."""
+        positions = np.ascontiguousarray(positions, dtype=np.int64)
+        inv = np.empty(self._order.size, dtype=np.int64)
+        inv[self._order] = np.arange(self._order.size, dtype=np.int64)
+        up = lambda a: DeviceBuffer.from_array(a) if a.size else DeviceBuffer(8)
+        return up(positions), up(inv[positions]), int(positions.size)
+
+    def scatter_values(self, src_ptr, maps):
+        """values[positions[i]] := src[i] in both copies (kvx_vec_scatter_dev), src a device address; the other entries stay."""
+        a, b, count = maps
+        if count:
+            raise_for(lib().kvx_vec_scatter_dev(count, src_ptr, a.ptr, self.vx.ptr))
+            raise_for(lib().kvx_vec_scatter_dev(count, src_ptr, b.ptr, self.tvx.ptr))
+
     def gemv(self, x, y, trans="N", alpha=1.0, beta=0.0):
         """y := alpha*op(A)*x + beta*y  (base.gemv -> sparse.c:1073-1104)."""
         if trans == "N":                                  # A x = (A')' x: gather over the rows of A

@@ -9,6 +9,9 @@
                                                                                      has 'q' or 's' blocks, coneprog.py:1806-1807)
     lp(c, G, h, A=None, b=None, primalstart=None, dualstart=None)                    coneprog.py:2551 (-> conelp)
     qp(P, q, G, h, A=None, b=None, initvals=None)                                    coneprog.py:4120 (-> coneqp)
+    cpl(c, F, G=None, h=None, dims=None, A=None, b=None)                             cvxprog.py:35   (-> cvx.cpl, 'l' rows only)
+    cp(F, G=None, h=None, dims=None, A=None, b=None)                                 cvxprog.py:1359 (-> cvx.cp: cpl on the epigraph form)
+    gp(K, F, g, G=None, h=None, A=None, b=None)                                      cvxprog.py:1967 (-> cvx.gp: kvx_gp_eval_dev, cp)
     options                                                                          the module-level dict of the reference
 
 Like the reference, algorithm parameters come from `solvers.options` ('maxiters', 'abstol', 'reltol', 'feastol',
@@ -22,6 +25,7 @@ import numpy as np
 
 from . import base as _base
 from . import cone as _cone
+from . import cvx as _cvx
 from . import lp as _lp
 
 options = {}
@@ -64,6 +68,31 @@ def coneqp(P, q, G, h, dims=None, A=None, b=None, initvals=None, **kw):
             raise NotImplementedError("coneqp with 'q' / 's' cones runs misc.kkt_chol on the GPU; kktsolver is not selectable")
         return _cone.coneqp(P, q, G, h, dims, A=A, b=b, initvals=initvals, options=_opts(kw))
     return _lp.coneqp(P, q, G, h, _opts(kw), None, A=A, b=b, initvals=initvals, kktsolver=k)
+
+
+def _cvx_opts(kw):
+    o = dict(options)
+    o.update(kw.pop("options", None) or {})
+    if kw:
+        raise TypeError("unexpected arguments: %s" % ", ".join(sorted(kw)))
+    return o
+
+
+def cpl(c, F, G=None, h=None, dims=None, A=None, b=None, kktsolver=None, xnewcopy=None, xdot=None, xaxpy=None, xscal=None,
+        ynewcopy=None, ydot=None, yaxpy=None, yscal=None, **kw):
+    """solvers.cpl (cvxprog.py:35-1356): nonlinear convex program with a linear objective, 'l' rows only, on the GPU."""
+    return _cvx.cpl(c, F, G, h, dims, A, b, kktsolver, xnewcopy, xdot, xaxpy, xscal, ynewcopy, ydot, yaxpy, yscal, options=_cvx_opts(kw))
+
+
+def cp(F, G=None, h=None, dims=None, A=None, b=None, kktsolver=None, xnewcopy=None, xdot=None, xaxpy=None, xscal=None,
+       ynewcopy=None, ydot=None, yaxpy=None, yscal=None, **kw):
+    """solvers.cp (cvxprog.py:1359-1964): nonlinear convex program, through the epigraph form and cpl."""
+    return _cvx.cp(F, G, h, dims, A, b, kktsolver, xnewcopy, xdot, xaxpy, xscal, ynewcopy, ydot, yaxpy, yscal, options=_cvx_opts(kw))
+
+
+def gp(K, F, g, G=None, h=None, A=None, b=None, kktsolver=None, **kw):
+    """solvers.gp (cvxprog.py:1967-2155): geometric program in convex form; F stays in HBM (kvx_gp_eval_dev)."""
+    return _cvx.gp(K, F, g, G, h, A, b, kktsolver, options=_cvx_opts(kw))
 
 
 def lp(c, G, h, A=None, b=None, primalstart=None, dualstart=None, **kw):
