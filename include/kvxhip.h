@@ -184,6 +184,13 @@ int kvx_chol_prof_read(kvx_chol *F, double *total_ms, int64_t *launches);
 int kvx_dbg_tile_cover(int uonly, const int32_t *hm, const int32_t *hk, int count, int kb, int klen, int col_lim, int tmax,
                        int32_t *counts, int64_t *info);
 int kvx_dbg_syrk_counts(int64_t *out, int reset);
+/* kvx_dbg_lu_counts: launches enqueued by the sparse LU path of this process, one counter per routing outcome (out may be NULL;
+ * reset = 1 zeroes them); returns the number of counters, 30.  Order: k_lu_front_wp<T> at index T (T = 1, 2, 3, 4, 6, 7; 0 and 5
+ * unused), k_lu_front_tiled<T> at 8 + T, then from 16: LDS-resident legacy kernel, unblocked big fronts, k_lub_panel_reg<32,1>,
+ * <16,2>, <8,4>, k_lub_panel, k_lub_panel launches in which some front has more than 4096 rows left, k_lub_trsm, k_lub_trsm left
+ * out (refactorisation, block without interchanges), k_lub_gemm, forward sweep small / big, backward sweep small / big (per
+ * launcher call with fronts).  A graph replay enqueues nothing and is not counted. */
+int kvx_dbg_lu_counts(int64_t *out, int reset);
 /* ---- sharded mode: ONE system factored and solved by nranks processes, one GPU each ----------------------------
  * (the reference is single-process: the calls this stands in for are cholmod_l_factorize / cholmod_l_solve,
  * src/C/cholmod.c:362-364, 483.)  Every rank analyses the same matrix (the analysis is deterministic) and computes the

@@ -341,6 +341,12 @@ int enqueue_pass(kvx_lu_num *N, const double *Ax_dev, int reuse)
             else {
                 const uint8_t *sw = (reuse && (size_t)l < N->swap_steps.size() && !N->swap_steps[(size_t)l].empty()) ? N->swap_steps[(size_t)l].data() : nullptr;
                 launch_lu_big_level(d, N->d_lists + b + nl, (int)(e - b - nl), bm, bk, Ax_dev, N->tol, N->stol, reuse, N->st2, sw);
+                // diagnostics: the k_lub_panel launches of this level in which a front really has more than 4096 rows left
+                for (int jb = 0; jb < bk && bm - jb > 4096; jb += lu_big_block_width(bm - jb)) {
+                    bool work = false;
+                    for (int64_t qq = b + nl; qq < e && !work; qq++) { const LuFrontH &f = P.fr[P.levellist[qq]]; work = f.k > jb && f.m - jb > 4096; }
+                    if (work) lu_count(LU_CNT_PANEL_LDS_WORK);
+                }
             }
         }
         if (hasA) { HIPCHK(hipEventRecord(N->evA[l], N->st)); lastA = l; }

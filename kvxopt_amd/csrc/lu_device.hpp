@@ -33,6 +33,23 @@ struct LuDev {           // all device pointers
     int64_t arena_size;      // doubles in `arena` (k_lu_front_wp keeps 32-bit offsets into it)
 };
 
+// Host-side count of the launches enqueued by the launchers below, one counter per routing outcome (process-wide;
+// kvx_dbg_lu_counts reads them, in this order).  WP / TILED are indexed by the kernel's template argument T (1, 2, 3, 4, 6, 7).
+enum LuCount {
+    LU_CNT_WP = 0,                     // k_lu_front_wp<T>: LU_CNT_WP + T
+    LU_CNT_TILED = 8,                  // k_lu_front_tiled<T>: LU_CNT_TILED + T
+    LU_CNT_LDS_LEGACY = 16,            // k_lu_front<true, ...>
+    LU_CNT_UNBLOCKED,                  // k_lu_front<false, ...>
+    LU_CNT_PANEL_REG32, LU_CNT_PANEL_REG16, LU_CNT_PANEL_REG8,   // k_lub_panel_reg<32, 1>, <16, 2>, <8, 4>
+    LU_CNT_PANEL_LDS,                  // k_lub_panel
+    LU_CNT_PANEL_LDS_WORK,             // ... of which some front of the launch has more than 4096 rows left (lu_api.cpp counts these)
+    LU_CNT_TRSM, LU_CNT_TRSM_SKIPPED,  // k_lub_trsm launched / left out by the interchange flags of a refactorisation
+    LU_CNT_GEMM,
+    LU_CNT_FWD_SMALL, LU_CNT_FWD_BIG, LU_CNT_BWD_SMALL, LU_CNT_BWD_BIG,   // sweeps: one per launcher call that has fronts
+    LU_NCOUNT
+};
+void lu_count(LuCount c);
+
 // Factor the fronts list[0..cnt) (one workgroup each).  lds_m > 0: fronts of order <= lds_m held in LDS; 0: in HBM.
 void launch_lu_fronts(const LuDev &d, const int32_t *list, int cnt, int lds_m, int max_k, const double *Ax,
                       double tol, double stol, int reuse, hipStream_t st);

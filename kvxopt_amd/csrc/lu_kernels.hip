@@ -10,6 +10,7 @@
 // Latency-bound work: fronts of circuit / power-flow matrices are tens to hundreds of rows.
 #include "lu_device.hpp"
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 namespace kvx {
@@ -1792,6 +1793,9 @@ __global__ void k_lu_fterm(const int64_t cnt, const int32_t *__restrict__ poslis
 
 }  // namespace
 
+static std::atomic<long long> g_lu_counts[LU_NCOUNT];
+void lu_count(LuCount c) { g_lu_counts[c].fetch_add(1, std::memory_order_relaxed); }
+
 // gfx950: a workgroup may use all 160 KB of a CU's LDS; beyond 64 KB the kernel must be told so once.
 static void allow_large_lds()
 {
@@ -1815,6 +1819,7 @@ void launch_lu_fronts(const LuDev &d, const int32_t *list, int cnt, int lds_m, i
         const size_t sm = (size_t)lds_m * lds_m * sizeof(double) + 2 * (size_t)lds_m * sizeof(int32_t);
         static const bool legacy = getenv("KVX_LU_LDS_LEGACY") != nullptr;       // the LDS-resident elimination (debugging aid)
         if (legacy) {
+            lu_count(LU_CNT_LDS_LEGACY);
             hipLaunchKernelGGL((k_lu_front<true, LU_NT_LDS>), dim3(cnt), dim3(LU_NT_LDS), sm, st, d, list, Ax, tol, stol, reuse, lds_m);
             return;
         }
@@ -1823,7 +1828,9 @@ void launch_lu_fronts(const LuDev &d, const int32_t *list, int cnt, int lds_m, i
         // bound by how many workgroups a CU holds, and the round-3 kernel is the smaller one (KVX_LU_WP_MAXCNT, default 512)
         static const int wp_maxcnt = [] { const char *e = getenv("KVX_LU_WP_MAXCNT"); return e ? atoi(e) : 512; }();
         if (wp && cnt <= wp_maxcnt && d.arena_size < (int64_t)1 << 32) {      // (its work items hold 32-bit offsets into the arena)
-            switch ((lds_m + 15) / 16) {
+            const int T = (lds_m + 15) / 16;
+            lu_count((LuCount)(LU_CNT_WP + (T <= 4 ? std::max(T, 1) : (T <= 6 ? 6 : 7))));
+            switch (T) {
             case 1: hipLaunchKernelGGL((k_lu_front_wp<1>), dim3(cnt), dim3(256), wp_lds_bytes(1), st, d, list, Ax, tol, stol, reuse); break;
             case 2: hipLaunchKernelGGL((k_lu_front_wp<2>), dim3(cnt), dim3(256), wp_lds_bytes(2), st, d, list, Ax, tol, stol, reuse); break;
             case 3: hipLaunchKernelGGL((k_lu_front_wp<3>), dim3(cnt), dim3(256), wp_lds_bytes(3), st, d, list, Ax, tol, stol, reuse); break;
@@ -1833,7 +1840,9 @@ void launch_lu_fronts(const LuDev &d, const int32_t *list, int cnt, int lds_m, i
             }
             return;
         }
-        switch ((lds_m + 15) / 16) {
+        const int T = (lds_m + 15) / 16;
+        lu_count((LuCount)(LU_CNT_TILED + (T <= 4 ? std::max(T, 1) : (T <= 6 ? 6 : 7))));
+        switch (T) {
         case 1: hipLaunchKernelGGL((k_lu_front_tiled<1>), dim3(cnt), dim3(256), sm, st, d, list, Ax, tol, stol, reuse, lds_m); break;
         case 2: hipLaunchKernelGGL((k_lu_front_tiled<2>), dim3(cnt), dim3(256), sm, st, d, list, Ax, tol, stol, reuse, lds_m); break;
         case 3: hipLaunchKernelGGL((k_lu_front_tiled<3>), dim3(cnt), dim3(256), sm, st, d, list, Ax, tol, stol, reuse, lds_m); break;
@@ -1843,6 +1852,7 @@ void launch_lu_fronts(const LuDev &d, const int32_t *list, int cnt, int lds_m, i
         }
     } else {
         const size_t sm = 2 * (size_t)max_k * sizeof(int32_t) + 16;
+        lu_count(LU_CNT_UNBLOCKED);
         hipLaunchKernelGGL((k_lu_front<false, LU_NT_BIG>), dim3(cnt), dim3(LU_NT_BIG), sm, st, d, list, Ax, tol, stol, reuse, 0);
     }
 }
@@ -1861,22 +1871,31 @@ void launch_lu_big_level(const LuDev &d, const int32_t *list, int cnt, int max_m
         const int nth = std::min(1024, (rows + 63) / 64 * 64);
         int nbs = LU_NB;
         if (rows <= 1024) {
+            lu_count(LU_CNT_PANEL_REG32);
             if (reuse) hipLaunchKernelGGL((k_lub_panel_reg<32, 1, true>), dim3(cnt), dim3(nth), 0, st, d, list, jb, tol, stol);
             else hipLaunchKernelGGL((k_lub_panel_reg<32, 1, false>), dim3(cnt), dim3(nth), 0, st, d, list, jb, tol, stol);
         } else if (rows <= 2048) {
             nbs = 16;
+            lu_count(LU_CNT_PANEL_REG16);
             if (reuse) hipLaunchKernelGGL((k_lub_panel_reg<16, 2, true>), dim3(cnt), dim3(1024), 0, st, d, list, jb, tol, stol);
             else hipLaunchKernelGGL((k_lub_panel_reg<16, 2, false>), dim3(cnt), dim3(1024), 0, st, d, list, jb, tol, stol);
         } else {
             nbs = 8;
+            lu_count(LU_CNT_PANEL_REG8);
             if (reuse) hipLaunchKernelGGL((k_lub_panel_reg<8, 4, true>), dim3(cnt), dim3(1024), 0, st, d, list, jb, tol, stol);
             else hipLaunchKernelGGL((k_lub_panel_reg<8, 4, false>), dim3(cnt), dim3(1024), 0, st, d, list, jb, tol, stol);
-            if (rows > 4096)
+            if (rows > 4096) {
+                lu_count(LU_CNT_PANEL_LDS);
                 hipLaunchKernelGGL(k_lub_panel, dim3(cnt), dim3(LU_NT_LDS), (size_t)LU_PANEL_LDS_DOUBLES * sizeof(double), st, d, list, jb, nbs,
                                    tol, stol, reuse);
+            }
         }
         // (a refactorisation knows from the recorded sequence which blocks interchange rows at all: lu_api.cpp, refresh_swap_steps)
-        if (!swap_steps || swap_steps[step]) hipLaunchKernelGGL(k_lub_trsm, dim3(tiles, cnt), dim3(64), 0, st, d, list, jb, nbs);
+        if (!swap_steps || swap_steps[step]) {
+            lu_count(LU_CNT_TRSM);
+            hipLaunchKernelGGL(k_lub_trsm, dim3(tiles, cnt), dim3(64), 0, st, d, list, jb, nbs);
+        } else lu_count(LU_CNT_TRSM_SKIPPED);
+        lu_count(LU_CNT_GEMM);
         hipLaunchKernelGGL(k_lub_gemm, dim3(tiles, tiles, cnt), dim3(256), 0, st, d, list, jb, nbs);
         jb += nbs;
     }
@@ -1887,6 +1906,7 @@ void launch_lu_fwd(const LuDev &d, const int32_t *list, int cnt, int max_m, int 
                    double *W, int64_t wsize, hipStream_t st)
 {
     if (cnt <= 0 || nrhs <= 0) return;
+    lu_count(LU_CNT_FWD_SMALL);
     const size_t sm = (size_t)(max_m + max_k) * sizeof(double);
     if (unit) hipLaunchKernelGGL(k_lu_fwd<true>, dim3(cnt, nrhs), dim3(LU_NT_SOLVE), sm, st, d, list, X, ldx, W, wsize, max_m);
     else hipLaunchKernelGGL(k_lu_fwd<false>, dim3(cnt, nrhs), dim3(LU_NT_SOLVE), sm, st, d, list, X, ldx, W, wsize, max_m);
@@ -1896,6 +1916,7 @@ void launch_lu_bwd(const LuDev &d, const int32_t *list, int cnt, int max_m, int 
                    hipStream_t st)
 {
     if (cnt <= 0 || nrhs <= 0) return;
+    lu_count(LU_CNT_BWD_SMALL);
     const size_t sm = (size_t)(max_m + max_k) * sizeof(double);
     if (unit) hipLaunchKernelGGL(k_lu_bwd<true>, dim3(cnt, nrhs), dim3(LU_NT_SOLVE), sm, st, d, list, X, ldx, max_m);
     else hipLaunchKernelGGL(k_lu_bwd<false>, dim3(cnt, nrhs), dim3(LU_NT_SOLVE), sm, st, d, list, X, ldx, max_m);
@@ -1906,6 +1927,7 @@ void launch_lu_fwd_big(const LuDev &d, const int32_t *list, int cnt, int max_m, 
                        double *W, int64_t wsize, hipStream_t st)
 {
     if (cnt <= 0 || nrhs <= 0) return;
+    lu_count(LU_CNT_FWD_BIG);
     const int chunks = (max_m + LU_BIG_CHUNK - 1) / LU_BIG_CHUNK;
     if (unit) hipLaunchKernelGGL(k_lu_fwd_big_init<true>, dim3(cnt, nrhs), dim3(LU_NT_SOLVE), (size_t)max_k * sizeof(double), st, d, list, X, ldx, W, wsize);
     else hipLaunchKernelGGL(k_lu_fwd_big_init<false>, dim3(cnt, nrhs), dim3(LU_NT_SOLVE), 0, st, d, list, X, ldx, W, wsize);
@@ -1919,6 +1941,7 @@ void launch_lu_bwd_big(const LuDev &d, const int32_t *list, int cnt, int max_m, 
                        double *W, int64_t wsize, hipStream_t st)
 {
     if (cnt <= 0 || nrhs <= 0) return;
+    lu_count(LU_CNT_BWD_BIG);
     const int chunks = (max_k + LU_BIG_CHUNK - 1) / LU_BIG_CHUNK, colwg = (max_k + LU_NT_SOLVE / 64 - 1) / (LU_NT_SOLVE / 64);
     if (unit) hipLaunchKernelGGL(k_lu_bwd_big_init<true>, dim3(colwg, cnt, nrhs), dim3(LU_NT_SOLVE), 0, st, d, list, X, ldx, W, wsize);
     else hipLaunchKernelGGL(k_lu_bwd_big_init<false>, dim3(colwg, cnt, nrhs), dim3(LU_NT_SOLVE), 0, st, d, list, X, ldx, W, wsize);
@@ -1974,3 +1997,12 @@ void launch_lu_udiag(const LuDev &d, int nfront, double *out, hipStream_t st)
 }
 
 }  // namespace kvx
+
+extern "C" int kvx_dbg_lu_counts(int64_t *out, int reset)
+{
+    for (int c = 0; c < kvx::LU_NCOUNT; c++) {
+        const long long v = reset ? kvx::g_lu_counts[c].exchange(0) : kvx::g_lu_counts[c].load();
+        if (out) out[c] = (int64_t)v;
+    }
+    return kvx::LU_NCOUNT;
+}
