@@ -543,6 +543,15 @@ typedef struct kvx_lu_num kvx_lu_num;      /* replaces the "KLU NUM D FACTOR" ca
  * singular pattern is accepted here and reported by the numeric phase (KVX_ESINGULAR), as KLU does.
  * KVX_EINVAL: n < 1, malformed colptr/rowind. */
 int kvx_lu_analyze(int64_t n, const int64_t *colptr, const int64_t *rowind, const double *values, kvx_lu_sym **out);
+/* symbolic(A) of the general LU without block form -- replaces umfpack.c:240-290 (umfpack_*_symbolic): UMFPACK returns
+ * P R A Q = L U with no off-diagonal part, so the choice belongs to ONE analysis, never to the process.  flags:
+ *   KVX_LU_FLAG_NO_BTF       one block, an empty F and one block level, whatever the matrix and the environment say;
+ *   KVX_LU_FLAG_KEEP_VALUES  numeric objects of this analysis refresh their own copy of A's values in kvx_lu_factor_dev /
+ *                            kvx_lu_refactor_dev as well (the host entry points always have it): kvx_lu_solve_refine needs A.
+ * kvx_lu_analyze is flags = 0 (and still honours the process-wide KVX_LU_NO_BTF=1).  KVX_EINVAL also for unknown flag bits. */
+#define KVX_LU_FLAG_NO_BTF 1
+#define KVX_LU_FLAG_KEEP_VALUES 2
+int kvx_lu_analyze_opts(int64_t n, const int64_t *colptr, const int64_t *rowind, const double *values, int64_t flags, kvx_lu_sym **out);
 void kvx_lu_free_symbolic(kvx_lu_sym *S);
 /* info: n, nnz, base supernodes, merges learned so far, structurally singular (0/1), nnz(L) bound of the
  * symmetrised pattern, levels, largest base front */
@@ -585,6 +594,15 @@ int kvx_lu_num_graph_replays(kvx_lu_num *N, int64_t *replays);
  * B is n x nrhs column-major with leading dimension ldB >= max(1, n), overwritten by the solution. */
 int kvx_lu_solve(kvx_lu_num *N, int trans, double *B, int64_t nrhs, int64_t ldB);
 int kvx_lu_solve_dev(kvx_lu_num *N, int trans, double *B_dev, int64_t nrhs, int64_t ldB);
+/* solve with iterative refinement -- what umfpack.c:582-668 gets from umfpack_*_solve (UMFPACK_IRSTEP = 2).  Per column, with
+ * op(A) = A or A':  x = solve(b);  r = b - op(A) x;  omega = max_i |r_i| / (|op(A)| |x| + |b|)_i  (0 / 0 = 0);  then up to `steps`
+ * times  d = solve(r), x' = x + d, r', omega':  x' is kept ONLY IF omega' < omega, otherwise x stays and the column stops changing.
+ * The residual uses the caller's unscaled values (the factor's own device copy).  All of it runs on the device without a host
+ * read between the steps; no floating-point atomics: two calls give the same bytes.  steps >= 0; steps = 0 with berr_out = NULL
+ * is kvx_lu_solve itself (the same launches, the same bits).  berr_out: NULL or 2 nrhs doubles in HOST memory (both entry points):
+ * berr_out[2 j] = omega of column j before refinement, berr_out[2 j + 1] = omega of the returned column.  nrhs <= 65535. */
+int kvx_lu_solve_refine(kvx_lu_num *N, int trans, double *B, int64_t nrhs, int64_t ldB, int64_t steps, double *berr_out);
+int kvx_lu_solve_refine_dev(kvx_lu_num *N, int trans, double *B_dev, int64_t nrhs, int64_t ldB, int64_t steps, double *berr_out);
 
 /* get_numeric(A, Fs, Fn) -- klu.c:392-566 (klu_extract :444).  L, U, F come back as malloc'ed CCS triples
  * (free with kvx_free), sorted rows, no explicit zeros; P[k] = row of A that is pivot row k, Q[k] = column of A

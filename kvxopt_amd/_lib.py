@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("KVX_LIB_PATH") or os.path.join(_HERE, "libkvxhip.so")
 
 KVX_OK, KVX_EINVAL, KVX_ENOMEM, KVX_ENOTPOSDEF, KVX_ESYMBOLIC, KVX_ESINGULAR, KVX_EDEVICE, KVX_EPERM, KVX_ECOMM = range(9)
 KVX_DIST_BCAST, KVX_DIST_ALLREDUCE, KVX_DIST_ALLREDUCE_MIN = 1, 2, 3
+KVX_LU_FLAG_NO_BTF, KVX_LU_FLAG_KEEP_VALUES = 1, 2
 
 i64 = ctypes.c_int64
 f64 = ctypes.c_double
@@ -181,6 +182,7 @@ _SIGS = {
     "kvx_vec_xmy_dev": (ctypes.c_int, [i64, f64, vp, vp, f64, vp]),
     "kvx_spmv_dev": (ctypes.c_int, [ctypes.c_int, i64, i64, vp, vp, vp, f64, vp, f64, vp]),
     "kvx_lu_analyze": (ctypes.c_int, [i64, i64p, i64p, f64p, ctypes.POINTER(vp)]),
+    "kvx_lu_analyze_opts": (ctypes.c_int, [i64, i64p, i64p, f64p, i64, ctypes.POINTER(vp)]),
     "kvx_lu_free_symbolic": (None, [vp]),
     "kvx_lu_sym_info": (ctypes.c_int, [vp, i64p]),
     "kvx_lu_sym_matching": (ctypes.c_int, [vp, i64p]),
@@ -195,6 +197,8 @@ _SIGS = {
     "kvx_lu_num_graph_replays": (ctypes.c_int, [vp, i64p]),
     "kvx_lu_solve": (ctypes.c_int, [vp, ctypes.c_int, f64p, i64, i64]),
     "kvx_lu_solve_dev": (ctypes.c_int, [vp, ctypes.c_int, vp, i64, i64]),
+    "kvx_lu_solve_refine": (ctypes.c_int, [vp, ctypes.c_int, f64p, i64, i64, i64, f64p]),
+    "kvx_lu_solve_refine_dev": (ctypes.c_int, [vp, ctypes.c_int, vp, i64, i64, i64, f64p]),
     "kvx_lu_extract": (ctypes.c_int, [vp, i64p, ctypes.POINTER(i64p), ctypes.POINTER(i64p), ctypes.POINTER(f64p),
                                       i64p, ctypes.POINTER(i64p), ctypes.POINTER(i64p), ctypes.POINTER(f64p),
                                       i64p, ctypes.POINTER(i64p), ctypes.POINTER(i64p), ctypes.POINTER(f64p),

@@ -72,11 +72,22 @@ struct kvx_lu_num {
         uint64_t seen_version = 0;
         void drop() { if (exec) (void)hipGraphExecDestroy(exec); exec = nullptr; }
     };
-    Graph g_pass, g_solve[2];
+    Graph g_pass, g_solve[2], g_refine[2];
     uint64_t version = 1, swap_version = 0;                   // (swap_version: the interchange flags -- the passes depend on them, the solves do not)
     bool graphs_on = [] { const char *e = std::getenv("KVX_LU_GRAPH"); return !e || e[0] != '0'; }();
     int64_t graph_replays = 0;
     bool unblocked = std::getenv("KVX_LU_UNBLOCKED") != nullptr;   // debugging aid: big fronts by one workgroup each
+    // Refined solves (kvx_lu_solve_refine, lu_refine.hip).  The residual needs the caller's unscaled A: d_Ax -- the block the host
+    // entry points upload the values into anyway -- is this factor's own copy; the device entry points refresh it when the analysis
+    // carries KVX_LU_FLAG_KEEP_VALUES.  Everything else is allocated at the first refined solve, never for a plain one.
+    bool have_vals = false;                                       // d_Ax holds the values of the current factorisation
+    void *d_rmap = nullptr, *d_rwork = nullptr;                   // one device block each: the row-wise views / the work vectors
+    int64_t *d_ap = nullptr, *d_csrp = nullptr;                   // column pointers of A (the rows of A'), row pointers of A
+    int32_t *d_csrc = nullptr, *d_csrs = nullptr;                 // columns of the rows of A, their index in the caller's value order
+    double *d_rx = nullptr, *d_rd[2] = {nullptr, nullptr}, *d_ratio = nullptr, *d_part = nullptr;   // x; residual / correction (by step parity)
+    double *d_om[2] = {nullptr, nullptr}, *d_omc = nullptr, *d_berr = nullptr;                        // omega (by step parity), the candidate's, [before, after] pairs
+    int32_t *d_act[2] = {nullptr, nullptr};                       // per column: still improving (by step parity)
+    int64_t cap_ref = 0;
 };
 
 namespace {
@@ -502,13 +513,15 @@ int ensure_rhs(kvx_lu_num *N, int64_t nrhs)
     return KVX_OK;
 }
 
-int enqueue_solve(kvx_lu_num *N, int trans, double *B_dev, int64_t nrhs, int64_t ldB);
+int enqueue_solve(kvx_lu_num *N, int trans, double *B_dev, int64_t nrhs, int64_t ldB, double *Out_dev = nullptr, int64_t ldOut = 0);
 int solve_on_device(kvx_lu_num *N, int trans, double *B_dev, int64_t nrhs, int64_t ldB)
 {
     return run_graphed(N, N->g_solve[trans ? 1 : 0], B_dev, nrhs, ldB, [&] { return enqueue_solve(N, trans, B_dev, nrhs, ldB); });
 }
-int enqueue_solve(kvx_lu_num *N, int trans, double *B_dev, int64_t nrhs, int64_t ldB)
+// The solution overwrites B, or goes to Out (B is then only read).
+int enqueue_solve(kvx_lu_num *N, int trans, double *B_dev, int64_t nrhs, int64_t ldB, double *Out_dev, int64_t ldOut)
 {
+    if (!Out_dev) { Out_dev = B_dev; ldOut = ldB; }
     const LuPlan &P = N->P;
     const LuDev d = dev_view(N);
     const int64_t n = N->n;
@@ -541,9 +554,98 @@ int enqueue_solve(kvx_lu_num *N, int trans, double *B_dev, int64_t nrhs, int64_t
         for (int32_t t = P.levstage[l + 1] - 1; t >= P.levstage[l]; t--) sweep(t, true, trans ? 0 : 1);
         for (int32_t t = P.levstage[l]; t < P.levstage[l + 1]; t++) sweep(t, false, trans ? 1 : 0);
     }
-    if (!trans) launch_lu_scatter(n, (int)nrhs, N->d_qcol, nullptr, N->d_X, n, B_dev, ldB, N->st);
-    else launch_lu_scatter(n, (int)nrhs, N->d_prow, N->d_rinv, N->d_X, n, B_dev, ldB, N->st);
+    if (!trans) launch_lu_scatter(n, (int)nrhs, N->d_qcol, nullptr, N->d_X, n, Out_dev, ldOut, N->st);
+    else launch_lu_scatter(n, (int)nrhs, N->d_prow, N->d_rinv, N->d_X, n, Out_dev, ldOut, N->st);
     HIPCHK(hipGetLastError());
+    return KVX_OK;
+}
+
+// The values of a factorisation made from device memory: kept in d_Ax when the analysis asks for it.
+int keep_values(kvx_lu_num *N, const double *values_dev)
+{
+    N->have_vals = values_dev == N->d_Ax;
+    if (N->have_vals || !(N->sym->Y.flags & KVX_LU_FLAG_KEEP_VALUES)) return KVX_OK;
+    HIPCHK(hipMemcpyAsync(N->d_Ax, values_dev, (size_t)N->nnz * sizeof(double), hipMemcpyDeviceToDevice, N->st));
+    N->have_vals = true;
+    return KVX_OK;
+}
+
+int ensure_refine(kvx_lu_num *N, int64_t nrhs)
+{
+    const LuSymbolic &Y = N->sym->Y;
+    if (!N->d_rmap) {
+        Arena A;
+        A.up(&N->d_ap, Y.Ap);
+        A.up(&N->d_csrp, Y.csr_ptr);
+        A.up(&N->d_csrc, Y.csr_col);
+        A.up(&N->d_csrs, Y.csr_src);
+        if (int rc = A.commit(&N->d_rmap)) return rc;
+    }
+    if (nrhs <= N->cap_ref) return KVX_OK;
+    if (N->d_rwork) (void)pool_free(N->d_rwork);
+    N->d_rwork = nullptr;
+    N->cap_ref = 0;
+    const int64_t n = N->n;
+    Arena A;
+    A.alloc(&N->d_rx, n * nrhs);
+    A.alloc(&N->d_rd[0], n * nrhs);
+    A.alloc(&N->d_rd[1], n * nrhs);
+    A.alloc(&N->d_ratio, n * nrhs);
+    A.alloc(&N->d_part, lu_berr_parts(n) * nrhs);
+    A.alloc(&N->d_om[0], nrhs);
+    A.alloc(&N->d_om[1], nrhs);
+    A.alloc(&N->d_omc, nrhs);
+    A.alloc(&N->d_berr, 2 * nrhs);
+    A.alloc(&N->d_act[0], nrhs);
+    A.alloc(&N->d_act[1], nrhs);
+    if (int rc = A.commit(&N->d_rwork)) return rc;
+    N->cap_ref = nrhs;
+    N->version++;                                                 // (new work buffers)
+    return KVX_OK;
+}
+
+// x <- solve(b), then up to `steps` corrections, each kept only if it lowers the componentwise backward error of its column
+// (lu_refine.hip).  b stays in B until the last launch writes the result there; nothing is read back between the steps.
+int enqueue_refine(kvx_lu_num *N, int trans, double *B_dev, int64_t nrhs, int64_t ldB, int64_t steps)
+{
+    const int64_t n = N->n;
+    const int nr = (int)nrhs;
+    const int64_t *rp = trans ? N->d_ap : N->d_csrp;              // the CCS is the row-wise view of A'
+    const int32_t *ci = trans ? N->d_ai32 : N->d_csrc, *src = trans ? nullptr : N->d_csrs;
+    int rc = enqueue_solve(N, trans, B_dev, nrhs, ldB, N->d_rx, n);
+    if (rc) return rc;
+    launch_lu_resid(n, nr, rp, ci, src, N->d_Ax, B_dev, ldB, N->d_rx, n, nullptr, 0, N->d_rd[0], n, N->d_ratio, N->st);
+    launch_lu_berr(n, nr, N->d_ratio, N->d_part, N->d_om[0], 1, N->d_berr, 2, N->d_act[0], N->st);
+    if (steps == 0)                                               // (only the backward error was asked for)
+        launch_lu_accept(n, nr, N->d_rx, n, nullptr, 0, B_dev, ldB, N->d_om[0], N->d_act[0], nullptr, nullptr, nullptr, N->d_berr + 1, 2, N->st);
+    for (int64_t s = 0; s < steps; s++) {
+        double *d = N->d_rd[s & 1], *rnext = N->d_rd[(s + 1) & 1];
+        const bool last = s == steps - 1;
+        if ((rc = enqueue_solve(N, trans, d, nrhs, n))) return rc;
+        launch_lu_resid(n, nr, rp, ci, src, N->d_Ax, B_dev, ldB, N->d_rx, n, d, n, rnext, n, N->d_ratio, N->st);
+        launch_lu_berr(n, nr, N->d_ratio, N->d_part, N->d_omc, 1, nullptr, 0, nullptr, N->st);
+        launch_lu_accept(n, nr, N->d_rx, n, d, n, last ? B_dev : N->d_rx, last ? ldB : n, N->d_om[s & 1], N->d_act[s & 1], N->d_omc,
+                         N->d_om[(s + 1) & 1], N->d_act[(s + 1) & 1], last ? N->d_berr + 1 : nullptr, 2, N->st);
+    }
+    HIPCHK(hipGetLastError());
+    return KVX_OK;
+}
+
+int refine_on_device(kvx_lu_num *N, int trans, double *B_dev, int64_t nrhs, int64_t ldB, int64_t steps)
+{
+    return run_graphed(N, N->g_refine[trans ? 1 : 0], B_dev, nrhs | (steps << 32), ldB, [&] { return enqueue_refine(N, trans, B_dev, nrhs, ldB, steps); });
+}
+
+int refine_args(kvx_lu_num *N, int trans, int64_t nrhs, int64_t ldB, int64_t steps)
+{
+    if (!N || (trans != 0 && trans != 1) || nrhs < 0 || steps < 0 || steps >= ((int64_t)1 << 20) || ldB < std::max<int64_t>(1, N->n)) return KVX_EINVAL;
+    if (!N->factored) { set_last_error("singular matrix"); return KVX_ESINGULAR; }
+    if (nrhs > 65535) { set_last_error("a refined solve takes at most 65535 right-hand sides at a time"); return KVX_EINVAL; }
+    if (!N->have_vals) {
+        set_last_error("refined solve: this factor was made from device values and its analysis has no KVX_LU_FLAG_KEEP_VALUES");
+        return KVX_EINVAL;
+    }
+    if (N->sym->Y.csr_ptr.empty()) { set_last_error("refined solve: more than 2^31-1 entries"); return KVX_EINVAL; }
     return KVX_OK;
 }
 
@@ -577,12 +679,18 @@ extern "C" {
 
 int kvx_lu_analyze(int64_t n, const int64_t *colptr, const int64_t *rowind, const double *values, kvx_lu_sym **out)
 {
-    if (!out || !colptr || (!rowind && n > 0 && colptr[n] > 0)) return KVX_EINVAL;
+    return kvx_lu_analyze_opts(n, colptr, rowind, values, 0, out);
+}
+
+int kvx_lu_analyze_opts(int64_t n, const int64_t *colptr, const int64_t *rowind, const double *values, int64_t flags, kvx_lu_sym **out)
+{
+    if (!out || !colptr || (!rowind && n > 0 && colptr[n] > 0) || (flags & ~(int64_t)(KVX_LU_FLAG_NO_BTF | KVX_LU_FLAG_KEEP_VALUES))) return KVX_EINVAL;
     *out = nullptr;
     kvx_lu_sym *S = new (std::nothrow) kvx_lu_sym();
     if (!S) return KVX_ENOMEM;
     try {
-        lu_analyze(n, colptr, rowind, values, S->Y);
+        lu_analyze(n, colptr, rowind, values, S->Y, (flags & KVX_LU_FLAG_NO_BTF) != 0);
+        S->Y.flags = flags;
     } catch (const std::bad_alloc &) {
         delete S;
         return KVX_ENOMEM;
@@ -604,7 +712,11 @@ void kvx_lu_free_numeric(kvx_lu_num *N)
     N->g_pass.drop();
     N->g_solve[0].drop();
     N->g_solve[1].drop();
+    N->g_refine[0].drop();
+    N->g_refine[1].drop();
     free_structure(N);
+    if (N->d_rmap) (void)pool_free(N->d_rmap);
+    if (N->d_rwork) (void)pool_free(N->d_rwork);
     if (N->d_base) (void)pool_free(N->d_base);    // d_ai32, d_rinv, d_rmax, d_Ax
     for (hipEvent_t e : N->evA) pool_event_put(e, false);
     for (hipEvent_t e : N->evB) pool_event_put(e, false);
@@ -663,7 +775,7 @@ static int kvx_lu_factor_dev_impl(kvx_lu_sym *S, int64_t nnz, const double *valu
     int rc = new_numeric(S, nnz, out);
     if (rc) return rc;
     kvx_lu_num *N = *out;
-    if ((rc = ensure_device(N)) || (rc = lu_wait_for_caller(N)) || (rc = factor_loop(N, values_dev, 0))) { kvx_lu_free_numeric(N); *out = nullptr; return rc; }
+    if ((rc = ensure_device(N)) || (rc = lu_wait_for_caller(N)) || (rc = keep_values(N, values_dev)) || (rc = factor_loop(N, values_dev, 0))) { kvx_lu_free_numeric(N); *out = nullptr; return rc; }
     return KVX_OK;
 }
 
@@ -679,6 +791,7 @@ static int kvx_lu_factor_impl(kvx_lu_sym *S, int64_t nnz, const double *values, 
     kvx_lu_num *N = *out;
     if ((rc = ensure_device(N))) { kvx_lu_free_numeric(N); *out = nullptr; return rc; }
     if (hipMemcpy(N->d_Ax, values, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = KVX_EDEVICE;
+    N->have_vals = !rc;
     if (!rc) rc = factor_loop(N, N->d_Ax, 0);
     if (rc) { kvx_lu_free_numeric(N); *out = nullptr; return rc; }
     return KVX_OK;
@@ -693,6 +806,7 @@ static int kvx_lu_refactor_dev_impl(kvx_lu_num *N, int64_t nnz, const double *va
 {
     if (!N || nnz != N->nnz) return KVX_EINVAL;
     if (int rc = lu_wait_for_caller(N)) return rc;
+    if (int rc = keep_values(N, values_dev)) return rc;
     if (!N->factored) return factor_loop(N, values_dev, 0);
     return factor_loop(N, values_dev, 1);
 }
@@ -752,6 +866,49 @@ static int kvx_lu_solve_impl(kvx_lu_num *N, int trans, double *B, int64_t nrhs, 
 int kvx_lu_solve(kvx_lu_num *N, int trans, double *B, int64_t nrhs, int64_t ldB)
 {
     return guarded([&] { return kvx_lu_solve_impl(N, trans, B, nrhs, ldB); });
+}
+
+static int kvx_lu_solve_refine_dev_impl(kvx_lu_num *N, int trans, double *B_dev, int64_t nrhs, int64_t ldB, int64_t steps, double *berr_out)
+{
+    if (steps == 0 && !berr_out) return kvx_lu_solve_dev_impl(N, trans, B_dev, nrhs, ldB);      // the plain solve: the same launches, the same bits
+    int rc = refine_args(N, trans, nrhs, ldB, steps);
+    if (rc) return rc;
+    if (!B_dev) return KVX_EINVAL;
+    if (nrhs == 0) return KVX_OK;
+    if ((rc = ensure_rhs(N, nrhs)) || (rc = ensure_refine(N, nrhs)) || (rc = lu_wait_for_caller(N))) return rc;
+    if ((rc = refine_on_device(N, trans, B_dev, nrhs, ldB, steps))) return rc;
+    if (berr_out) HIPCHK(hipMemcpyAsync(berr_out, N->d_berr, (size_t)(2 * nrhs) * sizeof(double), hipMemcpyDeviceToHost, N->st));
+    HIPCHK(hipStreamSynchronize(N->st));
+    return KVX_OK;
+}
+
+int kvx_lu_solve_refine_dev(kvx_lu_num *N, int trans, double *B_dev, int64_t nrhs, int64_t ldB, int64_t steps, double *berr_out)
+{
+    return guarded([&] { return kvx_lu_solve_refine_dev_impl(N, trans, B_dev, nrhs, ldB, steps, berr_out); });
+}
+
+static int kvx_lu_solve_refine_impl(kvx_lu_num *N, int trans, double *B, int64_t nrhs, int64_t ldB, int64_t steps, double *berr_out)
+{
+    if (steps == 0 && !berr_out) return kvx_lu_solve_impl(N, trans, B, nrhs, ldB);
+    int rc = refine_args(N, trans, nrhs, ldB, steps);
+    if (rc) return rc;
+    if (!B) return KVX_EINVAL;
+    if (nrhs == 0) return KVX_OK;
+    if ((rc = ensure_rhs(N, nrhs)) || (rc = ensure_refine(N, nrhs))) return rc;
+    const int64_t n = N->n;
+    HIPCHK(hipMemcpy2DAsync(N->d_B, (size_t)n * sizeof(double), B, (size_t)ldB * sizeof(double), (size_t)n * sizeof(double),
+                            (size_t)nrhs, hipMemcpyHostToDevice, N->st));
+    if ((rc = refine_on_device(N, trans, N->d_B, nrhs, n, steps))) return rc;
+    HIPCHK(hipMemcpy2DAsync(B, (size_t)ldB * sizeof(double), N->d_B, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
+                            (size_t)nrhs, hipMemcpyDeviceToHost, N->st));
+    if (berr_out) HIPCHK(hipMemcpyAsync(berr_out, N->d_berr, (size_t)(2 * nrhs) * sizeof(double), hipMemcpyDeviceToHost, N->st));
+    HIPCHK(hipStreamSynchronize(N->st));
+    return KVX_OK;
+}
+
+int kvx_lu_solve_refine(kvx_lu_num *N, int trans, double *B, int64_t nrhs, int64_t ldB, int64_t steps, double *berr_out)
+{
+    return guarded([&] { return kvx_lu_solve_refine_impl(N, trans, B, nrhs, ldB, steps, berr_out); });
 }
 
 int kvx_lu_num_info(kvx_lu_num *N, int64_t info[8])

@@ -84,4 +84,17 @@ void launch_lu_scatter(int64_t n, int nrhs, const int64_t *idx, const double *sc
 // d[p0 + t] = U(p0+t, p0+t) for every front
 void launch_lu_udiag(const LuDev &d, int nfront, double *out, hipStream_t st);
 
+// Refined solves (lu_refine.hip).  rp / ci / src: row-wise view of op(A) with an index map into the caller's value order (src ==
+// nullptr: identity).  R = B - op(A) (X [+ D]), ratio[i + j n] = |R_i| / (|op(A)| |X [+ D]| + |B|)_i with 0 / 0 = 0.
+void launch_lu_resid(int64_t n, int nrhs, const int64_t *rp, const int32_t *ci, const int32_t *src, const double *Ax, const double *B,
+                     int64_t ldb, const double *X, int64_t ldx, const double *D, int64_t ldd, double *R, int64_t ldr, double *ratio,
+                     hipStream_t st);
+constexpr int64_t LU_BERR_CHUNK = 8192;                 // ratios per workgroup of the first pass of the column maximum
+int64_t lu_berr_parts(int64_t n);                        // doubles of `part` per column
+void launch_lu_berr(int64_t n, int nrhs, const double *ratio, double *part, double *om, int64_t om_stride, double *om2, int64_t om2_stride,
+                    int32_t *act, hipStream_t st);
+void launch_lu_accept(int64_t n, int nrhs, const double *X, int64_t ldx, const double *D, int64_t ldd, double *out, int64_t ldo,
+                      const double *om_in, const int32_t *act_in, const double *om_cand, double *om_out, int32_t *act_out, double *om_final,
+                      int64_t final_stride, hipStream_t st);
+
 }  // namespace kvx

@@ -104,7 +104,7 @@ int64_t lu_matching(int64_t n, const int64_t *Ap, const int64_t *Ai, const doubl
     return matched;
 }
 
-void lu_analyze(int64_t n, const int64_t *Ap, const int64_t *Ai, const double *Ax, LuSymbolic &Y)
+void lu_analyze(int64_t n, const int64_t *Ap, const int64_t *Ai, const double *Ax, LuSymbolic &Y, bool no_btf)
 {
     if (n < 1) throw std::runtime_error("A must have at least one row and column");
     if (n >= (int64_t)1 << 31) throw std::runtime_error("order exceeds 2^31-1");
@@ -119,6 +119,20 @@ void lu_analyze(int64_t n, const int64_t *Ap, const int64_t *Ai, const double *A
     Y.nnz = Ap[n];
     Y.Ap.assign(Ap, Ap + n + 1);
     Y.Ai.assign(Ai, Ai + Y.nnz);
+    if (Y.nnz < ((int64_t)1 << 31)) {                                  // row-wise index map of A (the residual of a refined solve)
+        Y.csr_ptr.assign((size_t)n + 1, 0);
+        for (int64_t p = 0; p < Y.nnz; p++) Y.csr_ptr[(size_t)Ai[p] + 1]++;
+        for (int64_t i = 0; i < n; i++) Y.csr_ptr[(size_t)i + 1] += Y.csr_ptr[(size_t)i];
+        Y.csr_col.resize((size_t)Y.nnz);
+        Y.csr_src.resize((size_t)Y.nnz);
+        std::vector<int64_t> cur(Y.csr_ptr.begin(), Y.csr_ptr.end() - 1);
+        for (int64_t j = 0; j < n; j++)
+            for (int64_t p = Ap[j]; p < Ap[j + 1]; p++) {
+                const int64_t e = cur[(size_t)Ai[p]]++;
+                Y.csr_col[(size_t)e] = (int32_t)j;
+                Y.csr_src[(size_t)e] = (int32_t)p;
+            }
+    }
     std::vector<double> rinv((size_t)n, 1.0);
     if (Ax) {
         std::vector<double> rmax((size_t)n, 0.0);
@@ -178,7 +192,7 @@ void lu_analyze(int64_t n, const int64_t *Ap, const int64_t *Ai, const double *A
             }
         }
         const char *env = std::getenv("KVX_LU_NO_BTF");
-        if (ncomp > 1 && !(env && env[0] == '1') && !Y.structurally_singular) {
+        if (ncomp > 1 && !no_btf && !(env && env[0] == '1') && !Y.structurally_singular) {
             std::vector<int32_t> blk((size_t)n);
             for (int64_t v = 0; v < n; v++) blk[v] = ncomp - 1 - comp[v];
             // block levels for the back substitution: block k waits for the later blocks its rows touch

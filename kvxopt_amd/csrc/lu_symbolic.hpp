@@ -34,6 +34,12 @@ struct LuSymbolic {
     std::vector<int32_t> blev;            // [nblocks] solve level: 1 + max level of the later blocks this one's rows touch (0: none)
     std::vector<int32_t> uf;              // union-find over S's supernodes: learned merges (uf[s] = representative link)
     int64_t nmerges = 0;
+    int64_t flags = 0;                    // KVX_LU_FLAG_* of kvx_lu_analyze_opts: they belong to this analysis, never to the process
+    // row-wise view of the caller's matrix for the residual of a refined solve (lu_refine.hip): row i holds the entries
+    // csr_ptr[i] .. csr_ptr[i+1], column csr_col[e], value Ax[csr_src[e]] (an index map into the caller's value order,
+    // columns ascending inside a row).  The CCS itself is the row-wise view of A'.  Empty when nnz >= 2^31.
+    std::vector<int64_t> csr_ptr;
+    std::vector<int32_t> csr_col, csr_src;
 };
 
 // One front of the LU plan (positions = indices in the final pivotal order).
@@ -90,7 +96,9 @@ constexpr int KVX_LU_SOLVE_BIG_M = 384;   // fronts of order > this are swept by
 constexpr int KVX_LU_LDS_M = 112;        // fronts of order <= this are assembled in LDS and eliminated in registers (7 x 7 tile per thread)
 
 // values may be nullptr (pattern-only: plain maximum transversal).  Throws std::runtime_error on invalid input.
-void lu_analyze(int64_t n, const int64_t *Ap, const int64_t *Ai, const double *Ax, LuSymbolic &Y);
+// no_btf: one block, empty F, one block level whatever the matrix and the environment say (umfpack.c:240-290, umfpack_*_symbolic:
+// UMFPACK's P R A Q = L U has no off-diagonal part).
+void lu_analyze(int64_t n, const int64_t *Ap, const int64_t *Ai, const double *Ax, LuSymbolic &Y, bool no_btf = false);
 
 // Builds the plan for the current merge state of Y.
 void lu_build_plan(const LuSymbolic &Y, LuPlan &P);

@@ -133,6 +133,22 @@ def _rhs_args(n, B, trans, nrhs, ldB, offsetB, tc="d"):
     return buf, nrhs, ldB
 
 
+def _solve_packed(num_solve, n, buf, nrhs, ldB, offsetB, trans, cplx):
+    """Run num_solve(buffer, trans=, nrhs=, ldB=, offset=) -- a LuNumeric solve -- on the block of `buf` that _rhs_args checked;
+    a complex block goes through as [Re; Im] columns of the real embedding and comes back in place.  Returns num_solve's result."""
+    if not cplx:
+        return num_solve(buf, trans="N" if trans == "N" else "T", nrhs=nrhs, ldB=ldB, offset=offsetB)
+    # complex: [Re; Im] through the embedding.  'C': A^H = transpose of the embedding; 'T': A^T x = b  <=>  A^H conj(x) = conj(b)
+    cols = [buf[offsetB + j * ldB: offsetB + j * ldB + n] for j in range(nrhs)]
+    R = np.empty((2 * n, nrhs), order="F")
+    for j, c in enumerate(cols):
+        R[:n, j], R[n:, j] = c.real, (-c.imag if trans == "T" else c.imag)
+    out = num_solve(R.reshape(-1, order="F"), trans="N" if trans == "N" else "T", nrhs=nrhs, ldB=2 * n, offset=0)
+    for j, c in enumerate(cols):
+        c[:] = R[:n, j] + 1j * (-R[n:, j] if trans == "T" else R[n:, j])
+    return out
+
+
 def solve(A, Fs, F, B, trans="N", nrhs=-1, ldB=0, offsetB=0):
     n, cp, ri, v = _sp(A, msg="A must a square sparse matrix")
     if not isinstance(F, _Fn):
@@ -145,17 +161,7 @@ def solve(A, Fs, F, B, trans="N", nrhs=-1, ldB=0, offsetB=0):
     buf, nrhs, ldB = _rhs_args(n, B, trans, nrhs, ldB, offsetB, "z" if cplx else "d")
     if nrhs == 0:
         return
-    if not cplx:
-        F.num.solve(buf, trans="N" if trans == "N" else "T", nrhs=nrhs, ldB=ldB, offset=offsetB)
-        return
-    # complex: [Re; Im] through the embedding.  'C': A^H = transpose of the embedding; 'T': A^T x = b  <=>  A^H conj(x) = conj(b)
-    cols = [buf[offsetB + j * ldB: offsetB + j * ldB + n] for j in range(nrhs)]
-    R = np.empty((2 * n, nrhs), order="F")
-    for j, c in enumerate(cols):
-        R[:n, j], R[n:, j] = c.real, (-c.imag if trans == "T" else c.imag)
-    F.num.solve(R.reshape(-1, order="F"), trans="N" if trans == "N" else "T", nrhs=nrhs, ldB=2 * n, offset=0)
-    for j, c in enumerate(cols):
-        c[:] = R[:n, j] + 1j * (-R[n:, j] if trans == "T" else R[n:, j])
+    _solve_packed(F.num.solve, n, buf, nrhs, ldB, offsetB, trans, cplx)
 
 
 # linsolve re-analyses and re-factors at every call in the reference (klu.c:142-198).  Here the symbolic and numeric factors of the

@@ -7,7 +7,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import lib, raise_for, pi, pd, as_i64, as_f64, i64, i64p, f64p, vp
+from ._lib import lib, raise_for, pi, pd, as_i64, as_f64, i64, i64p, f64p, vp, KVX_LU_FLAG_NO_BTF, KVX_LU_FLAG_KEEP_VALUES
 
 
 def _take(ptr, count, dtype):
@@ -20,13 +20,17 @@ def _take(ptr, count, dtype):
 
 
 class LuSymbolic:
-    def __init__(self, n, colptr, rowind, values=None):
+    """btf=False: this analysis has one block, an empty F and one block level (KVX_LU_FLAG_NO_BTF: what `kvxopt_amd.umfpack`
+    factors); keep_values=True: its numeric objects keep A's values through refactor_dev too (KVX_LU_FLAG_KEEP_VALUES)."""
+
+    def __init__(self, n, colptr, rowind, values=None, btf=True, keep_values=False):
         self.n = int(n)
         self.colptr = as_i64(colptr)
         self.rowind = as_i64(rowind)
         v = None if values is None else as_f64(values)
         h = vp()
-        rc = lib().kvx_lu_analyze(self.n, pi(self.colptr), pi(self.rowind), None if v is None else pd(v), ctypes.byref(h))
+        flags = (0 if btf else KVX_LU_FLAG_NO_BTF) | (KVX_LU_FLAG_KEEP_VALUES if keep_values else 0)
+        rc = lib().kvx_lu_analyze_opts(self.n, pi(self.colptr), pi(self.rowind), None if v is None else pd(v), flags, ctypes.byref(h))
         raise_for(rc, "symbolic factorization failed")
         self._h = h
 
@@ -107,6 +111,26 @@ class LuNumeric:
 
     def solve_dev(self, B_ptr, trans="N", nrhs=1, ldB=None):
         raise_for(lib().kvx_lu_solve_dev(self._h, 0 if trans == "N" else 1, B_ptr, nrhs, ldB or max(1, self.n)))
+
+    def solve_refine(self, B, trans="N", nrhs=None, ldB=None, offset=0, steps=2, berr=True):
+        """solve() followed by up to `steps` refinement steps on the device (kvx_lu_solve_refine): a step is kept only if it lowers
+        the componentwise backward error omega of its column.  Returns an (nrhs, 2) array [omega before, omega after] (None with
+        berr=False); steps=0, berr=False is solve() itself."""
+        n = self.n
+        if nrhs is None:
+            nrhs = B.size // max(n, 1)
+        if ldB is None:
+            ldB = max(1, n)
+        w = np.zeros((max(nrhs, 0), 2)) if berr else None
+        ptr = ctypes.cast(B.ctypes.data + 8 * offset, f64p)
+        raise_for(lib().kvx_lu_solve_refine(self._h, 0 if trans == "N" else 1, ptr, nrhs, ldB, int(steps), None if w is None else pd(w)))
+        return w
+
+    def solve_refine_dev(self, B_ptr, trans="N", nrhs=1, ldB=None, steps=2, berr=True):
+        w = np.zeros((max(nrhs, 0), 2)) if berr else None
+        raise_for(lib().kvx_lu_solve_refine_dev(self._h, 0 if trans == "N" else 1, B_ptr, nrhs, ldB or max(1, self.n), int(steps),
+                                                None if w is None else pd(w)))
+        return w
 
     def extract(self):
         n = self.n
