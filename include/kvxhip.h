@@ -191,6 +191,18 @@ int kvx_dbg_syrk_counts(int64_t *out, int reset);
  * out (refactorisation, block without interchanges), k_lub_gemm, forward sweep small / big, backward sweep small / big (per
  * launcher call with fronts).  A graph replay enqueues nothing and is not counted. */
 int kvx_dbg_lu_counts(int64_t *out, int reset);
+/* kvx_dbg_lu_schedule: the factor-side launch schedule of a numeric pass over the plan that the analysis S gives in its current
+ * merge state (no device needed).  Returns the number of entries of the record, -1 for bad arguments or a plan that cannot be
+ * built; the record is written only if cap entries hold it (call with cap = 0 for the length).  Record: nlevels, then per level
+ * (0 = roots)
+ *   nfront, nfront pairs (m, k): the fronts in list order;
+ *   nlaunch, nlaunch quadruples (first, count, class, side): the launches of LDS fronts in launch order -- list entries
+ *     [first, first + count) of the level, LDS class 16 / 32 / 48 / 64 / 88 / 112, side 0 = the main stream, 1 = the second one;
+ *   first, count, bm, bk: the blocked part (fronts of order > 112) and the largest order / pivot count in it;
+ *   nstep, nstep triples (jb, width, lds_work): its pivot blocks [jb, jb + width) and whether some front has pivots from jb on
+ *     and more than 4096 rows left there. */
+struct kvx_lu_sym;
+int64_t kvx_dbg_lu_schedule(struct kvx_lu_sym *S, int64_t *out, int64_t cap);
 /* ---- sharded mode: ONE system factored and solved by nranks processes, one GPU each ----------------------------
  * (the reference is single-process: the calls this stands in for are cholmod_l_factorize / cholmod_l_solve,
  * src/C/cholmod.c:362-364, 483.)  Every rank analyses the same matrix (the analysis is deterministic) and computes the

@@ -108,6 +108,7 @@ _SIGS = {
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), i64p]),
     "kvx_dbg_syrk_counts": (ctypes.c_int, [i64p, ctypes.c_int]),
     "kvx_dbg_lu_counts": (ctypes.c_int, [i64p, ctypes.c_int]),
+    "kvx_dbg_lu_schedule": (i64, [vp, i64p, i64]),
     "kvx_chol_dist_map": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8), f64p, f64p, f64p]),
     "kvx_chol_dist_setup": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64p]),

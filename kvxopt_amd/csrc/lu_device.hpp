@@ -1,6 +1,7 @@
 // Device-side records and launchers of the sparse LU path (lu_kernels.hip); host plan in lu_symbolic.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "lu_symbolic.hpp"
 #include <cstdint>
 #include <string>
 
@@ -42,7 +43,7 @@ enum LuCount {
     LU_CNT_UNBLOCKED,                  // k_lu_front<false, ...>
     LU_CNT_PANEL_REG32, LU_CNT_PANEL_REG16, LU_CNT_PANEL_REG8,   // k_lub_panel_reg<32, 1>, <16, 2>, <8, 4>
     LU_CNT_PANEL_LDS,                  // k_lub_panel
-    LU_CNT_PANEL_LDS_WORK,             // ... of which some front of the launch has more than 4096 rows left (lu_api.cpp counts these)
+    LU_CNT_PANEL_LDS_WORK,             // ... of which some front of the launch has more than 4096 rows left (from the plan's schedule)
     LU_CNT_TRSM, LU_CNT_TRSM_SKIPPED,  // k_lub_trsm launched / left out by the interchange flags of a refactorisation
     LU_CNT_GEMM,
     LU_CNT_FWD_SMALL, LU_CNT_FWD_BIG, LU_CNT_BWD_SMALL, LU_CNT_BWD_BIG,   // sweeps: one per launcher call that has fronts
@@ -50,14 +51,16 @@ enum LuCount {
 };
 void lu_count(LuCount c);
 
-// Factor the fronts list[0..cnt) (one workgroup each).  lds_m > 0: fronts of order <= lds_m held in LDS; 0: in HBM.
-void launch_lu_fronts(const LuDev &d, const int32_t *list, int cnt, int lds_m, int max_k, const double *Ax,
+// Which kernel factors a launch of LDS fronts (chosen on the host: lu_internal.hpp lu_front_kernel).
+enum LuFrontKernel { LU_FRONT_LEGACY, LU_FRONT_WP, LU_FRONT_TILED };
+// Factor the fronts list[0..cnt) (one workgroup each).  lds_m > 0: fronts of order <= lds_m held in LDS, by kernel `kern`;
+// 0: in HBM (`kern` is not looked at).
+void launch_lu_fronts(const LuDev &d, const int32_t *list, int cnt, int lds_m, LuFrontKernel kern, int max_k, const double *Ax,
                       double tol, double stol, int reuse, hipStream_t st);
-// All fronts of a level that do not fit in LDS (blocked: lu_kernels.hip k_lub_*).
-void launch_lu_big_level(const LuDev &d, const int32_t *list, int cnt, int max_m, int max_k, const double *Ax, double tol,
-                         double stol, int reuse, hipStream_t st, const uint8_t *swap_steps = nullptr);
-// pivots per block while `rows` rows of the level's tallest front remain (the register budget of the panel's workgroup)
-inline int lu_big_block_width(int rows) { return rows <= 1024 ? 32 : (rows <= 2048 ? 16 : 8); }
+// The blocked part of a level, list = its L.big_count fronts (lu_kernels.hip k_lub_*): one panel / interchange / update round per
+// step of L.steps.  swap_steps (one flag per step, or nullptr): the interchange launch of a step whose flag is 0 is left out.
+void launch_lu_big_level(const LuDev &d, const int32_t *list, const LuLevelSched &L, const double *Ax, double tol, double stol,
+                         int reuse, hipStream_t st, const uint8_t *swap_steps = nullptr);
 // Triangular sweeps over one level.  unit = 1: the L panels (unit diagonal, in-front row permutation);
 // unit = 0: the U' panels.  W: update vectors, wsize doubles per right-hand side.
 void launch_lu_fwd(const LuDev &d, const int32_t *list, int cnt, int max_m, int max_k, int unit, double *X, int64_t ldx,

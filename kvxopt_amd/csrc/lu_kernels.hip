@@ -1810,94 +1810,78 @@ static void allow_large_lds()
     (void)hipGetLastError();
 }
 
-void launch_lu_fronts(const LuDev &d, const int32_t *list, int cnt, int lds_m, int max_k, const double *Ax, double tol,
-                      double stol, int reuse, hipStream_t st)
+void launch_lu_fronts(const LuDev &d, const int32_t *list, int cnt, int lds_m, LuFrontKernel kern, int max_k, const double *Ax,
+                      double tol, double stol, int reuse, hipStream_t st)
 {
     if (cnt <= 0) return;
     allow_large_lds();
-    if (lds_m > 0) {
-        const size_t sm = (size_t)lds_m * lds_m * sizeof(double) + 2 * (size_t)lds_m * sizeof(int32_t);
-        static const bool legacy = getenv("KVX_LU_LDS_LEGACY") != nullptr;       // the LDS-resident elimination (debugging aid)
-        if (legacy) {
-            lu_count(LU_CNT_LDS_LEGACY);
-            hipLaunchKernelGGL((k_lu_front<true, LU_NT_LDS>), dim3(cnt), dim3(LU_NT_LDS), sm, st, d, list, Ax, tol, stol, reuse, lds_m);
-            return;
-        }
-        static const bool wp = [] { const char *e = getenv("KVX_LU_WP"); return !e || e[0] != '0'; }();   // 0: the round-3 kernel (two barriers per pivot)
-        // ... where a launch is a level's few dozen fronts (its time is that of its slowest front); thousands of fronts per launch are
-        // bound by how many workgroups a CU holds, and the round-3 kernel is the smaller one (KVX_LU_WP_MAXCNT, default 512)
-        static const int wp_maxcnt = [] { const char *e = getenv("KVX_LU_WP_MAXCNT"); return e ? atoi(e) : 512; }();
-        if (wp && cnt <= wp_maxcnt && d.arena_size < (int64_t)1 << 32) {      // (its work items hold 32-bit offsets into the arena)
-            const int T = (lds_m + 15) / 16;
-            lu_count((LuCount)(LU_CNT_WP + (T <= 4 ? std::max(T, 1) : (T <= 6 ? 6 : 7))));
-            switch (T) {
-            case 1: hipLaunchKernelGGL((k_lu_front_wp<1>), dim3(cnt), dim3(256), wp_lds_bytes(1), st, d, list, Ax, tol, stol, reuse); break;
-            case 2: hipLaunchKernelGGL((k_lu_front_wp<2>), dim3(cnt), dim3(256), wp_lds_bytes(2), st, d, list, Ax, tol, stol, reuse); break;
-            case 3: hipLaunchKernelGGL((k_lu_front_wp<3>), dim3(cnt), dim3(256), wp_lds_bytes(3), st, d, list, Ax, tol, stol, reuse); break;
-            case 4: hipLaunchKernelGGL((k_lu_front_wp<4>), dim3(cnt), dim3(256), wp_lds_bytes(4), st, d, list, Ax, tol, stol, reuse); break;
-            case 5: case 6: hipLaunchKernelGGL((k_lu_front_wp<6>), dim3(cnt), dim3(256), wp_lds_bytes(6), st, d, list, Ax, tol, stol, reuse); break;
-            default: hipLaunchKernelGGL((k_lu_front_wp<7>), dim3(cnt), dim3(256), wp_lds_bytes(7), st, d, list, Ax, tol, stol, reuse); break;
-            }
-            return;
-        }
-        const int T = (lds_m + 15) / 16;
-        lu_count((LuCount)(LU_CNT_TILED + (T <= 4 ? std::max(T, 1) : (T <= 6 ? 6 : 7))));
-        switch (T) {
-        case 1: hipLaunchKernelGGL((k_lu_front_tiled<1>), dim3(cnt), dim3(256), sm, st, d, list, Ax, tol, stol, reuse, lds_m); break;
-        case 2: hipLaunchKernelGGL((k_lu_front_tiled<2>), dim3(cnt), dim3(256), sm, st, d, list, Ax, tol, stol, reuse, lds_m); break;
-        case 3: hipLaunchKernelGGL((k_lu_front_tiled<3>), dim3(cnt), dim3(256), sm, st, d, list, Ax, tol, stol, reuse, lds_m); break;
-        case 4: hipLaunchKernelGGL((k_lu_front_tiled<4>), dim3(cnt), dim3(256), sm, st, d, list, Ax, tol, stol, reuse, lds_m); break;
-        case 5: case 6: hipLaunchKernelGGL((k_lu_front_tiled<6>), dim3(cnt), dim3(256), sm, st, d, list, Ax, tol, stol, reuse, lds_m); break;
-        default: hipLaunchKernelGGL((k_lu_front_tiled<7>), dim3(cnt), dim3(256), sm, st, d, list, Ax, tol, stol, reuse, lds_m); break;
-        }
-    } else {
+    if (lds_m <= 0) {
         const size_t sm = 2 * (size_t)max_k * sizeof(int32_t) + 16;
         lu_count(LU_CNT_UNBLOCKED);
         hipLaunchKernelGGL((k_lu_front<false, LU_NT_BIG>), dim3(cnt), dim3(LU_NT_BIG), sm, st, d, list, Ax, tol, stol, reuse, 0);
+        return;
+    }
+    const size_t sm = (size_t)lds_m * lds_m * sizeof(double) + 2 * (size_t)lds_m * sizeof(int32_t);
+    if (kern == LU_FRONT_LEGACY) {                              // the LDS-resident elimination (debugging aid)
+        lu_count(LU_CNT_LDS_LEGACY);
+        hipLaunchKernelGGL((k_lu_front<true, LU_NT_LDS>), dim3(cnt), dim3(LU_NT_LDS), sm, st, d, list, Ax, tol, stol, reuse, lds_m);
+        return;
+    }
+    // LU_FRONT_WP: one barrier per pivot; LU_FRONT_TILED: the round-3 kernel (two barriers per pivot), the smaller one
+    const bool wp = kern == LU_FRONT_WP;
+    auto go = [&](auto tc) {
+        constexpr int T = decltype(tc)::value;
+        lu_count((LuCount)((wp ? LU_CNT_WP : LU_CNT_TILED) + T));
+        if (wp) hipLaunchKernelGGL((k_lu_front_wp<T>), dim3(cnt), dim3(256), wp_lds_bytes(T), st, d, list, Ax, tol, stol, reuse);
+        else hipLaunchKernelGGL((k_lu_front_tiled<T>), dim3(cnt), dim3(256), sm, st, d, list, Ax, tol, stol, reuse, lds_m);
+    };
+    switch ((lds_m + 15) / 16) {
+    case 1: go(std::integral_constant<int, 1>()); break;
+    case 2: go(std::integral_constant<int, 2>()); break;
+    case 3: go(std::integral_constant<int, 3>()); break;
+    case 4: go(std::integral_constant<int, 4>()); break;
+    case 5: case 6: go(std::integral_constant<int, 6>()); break;
+    default: go(std::integral_constant<int, 7>()); break;
     }
 }
 
-
-void launch_lu_big_level(const LuDev &d, const int32_t *list, int cnt, int max_m, int max_k, const double *Ax, double tol,
-                         double stol, int reuse, hipStream_t st, const uint8_t *swap_steps)
+template <int NB, int RPT>
+static void launch_panel_reg(LuCount c, int cnt, int nth, hipStream_t st, const LuDev &d, const int32_t *list, int jb, double tol, double stol, int reuse)
 {
+    lu_count(c);
+    if (reuse) hipLaunchKernelGGL((k_lub_panel_reg<NB, RPT, true>), dim3(cnt), dim3(nth), 0, st, d, list, jb, tol, stol);
+    else hipLaunchKernelGGL((k_lub_panel_reg<NB, RPT, false>), dim3(cnt), dim3(nth), 0, st, d, list, jb, tol, stol);
+}
+
+void launch_lu_big_level(const LuDev &d, const int32_t *list, const LuLevelSched &L, const double *Ax, double tol, double stol,
+                         int reuse, hipStream_t st, const uint8_t *swap_steps)
+{
+    const int cnt = L.big_count, max_m = L.bm, max_k = L.bk;
     if (cnt <= 0) return;
     allow_large_lds();
     hipLaunchKernelGGL(k_lub_assemble, dim3((max_m + LU_ASM_COLS - 1) / LU_ASM_COLS, cnt, (max_m + LU_ASM_ROWS - 1) / LU_ASM_ROWS), dim3(256), 0, st,
                        d, list, Ax);
     const int tiles = (max_m + 63) / 64;
-    for (int jb = 0, step = 0; jb < max_k; step++) {
+    for (size_t step = 0; step < L.steps.size(); step++) {
+        const int jb = L.steps[step].jb, nbs = L.steps[step].width;
         const int rows = max_m - jb;                          // tallest panel of this step
-        const int nth = std::min(1024, (rows + 63) / 64 * 64);
-        int nbs = LU_NB;
-        if (rows <= 1024) {
-            lu_count(LU_CNT_PANEL_REG32);
-            if (reuse) hipLaunchKernelGGL((k_lub_panel_reg<32, 1, true>), dim3(cnt), dim3(nth), 0, st, d, list, jb, tol, stol);
-            else hipLaunchKernelGGL((k_lub_panel_reg<32, 1, false>), dim3(cnt), dim3(nth), 0, st, d, list, jb, tol, stol);
-        } else if (rows <= 2048) {
-            nbs = 16;
-            lu_count(LU_CNT_PANEL_REG16);
-            if (reuse) hipLaunchKernelGGL((k_lub_panel_reg<16, 2, true>), dim3(cnt), dim3(1024), 0, st, d, list, jb, tol, stol);
-            else hipLaunchKernelGGL((k_lub_panel_reg<16, 2, false>), dim3(cnt), dim3(1024), 0, st, d, list, jb, tol, stol);
-        } else {
-            nbs = 8;
-            lu_count(LU_CNT_PANEL_REG8);
-            if (reuse) hipLaunchKernelGGL((k_lub_panel_reg<8, 4, true>), dim3(cnt), dim3(1024), 0, st, d, list, jb, tol, stol);
-            else hipLaunchKernelGGL((k_lub_panel_reg<8, 4, false>), dim3(cnt), dim3(1024), 0, st, d, list, jb, tol, stol);
-            if (rows > 4096) {
-                lu_count(LU_CNT_PANEL_LDS);
-                hipLaunchKernelGGL(k_lub_panel, dim3(cnt), dim3(LU_NT_LDS), (size_t)LU_PANEL_LDS_DOUBLES * sizeof(double), st, d, list, jb, nbs,
-                                   tol, stol, reuse);
-            }
+        switch (nbs) {
+        case 32: launch_panel_reg<32, 1>(LU_CNT_PANEL_REG32, cnt, std::min(1024, (rows + 63) / 64 * 64), st, d, list, jb, tol, stol, reuse); break;
+        case 16: launch_panel_reg<16, 2>(LU_CNT_PANEL_REG16, cnt, 1024, st, d, list, jb, tol, stol, reuse); break;
+        default: launch_panel_reg<8, 4>(LU_CNT_PANEL_REG8, cnt, 1024, st, d, list, jb, tol, stol, reuse); break;
         }
-        // (a refactorisation knows from the recorded sequence which blocks interchange rows at all: lu_api.cpp, refresh_swap_steps)
+        if (rows > 4096) {
+            lu_count(LU_CNT_PANEL_LDS);
+            hipLaunchKernelGGL(k_lub_panel, dim3(cnt), dim3(LU_NT_LDS), (size_t)LU_PANEL_LDS_DOUBLES * sizeof(double), st, d, list, jb, nbs,
+                               tol, stol, reuse);
+        }
+        // (a refactorisation knows from the recorded sequence which blocks interchange rows at all: lu_factor.cpp, refresh_swap_steps)
         if (!swap_steps || swap_steps[step]) {
             lu_count(LU_CNT_TRSM);
             hipLaunchKernelGGL(k_lub_trsm, dim3(tiles, cnt), dim3(64), 0, st, d, list, jb, nbs);
         } else lu_count(LU_CNT_TRSM_SKIPPED);
         lu_count(LU_CNT_GEMM);
         hipLaunchKernelGGL(k_lub_gemm, dim3(tiles, tiles, cnt), dim3(256), 0, st, d, list, jb, nbs);
-        jb += nbs;
     }
     hipLaunchKernelGGL(k_lub_store, dim3(tiles, cnt, (max_m + 255) / 256), dim3(256), 2 * (size_t)max_k * sizeof(int32_t) + 16, st, d, list, max_m);
 }

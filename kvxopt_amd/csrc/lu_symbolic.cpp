@@ -256,6 +256,40 @@ static int32_t uf_find(const std::vector<int32_t> &uf, int32_t a)
     return a;
 }
 
+static int lds_class(int m)
+{
+    for (int c : {16, 32, 48, 64, 88}) if (m <= c) return c;
+    return KVX_LU_LDS_M;
+}
+
+// The factor-side schedule of every level (LuLevelSched) from the sorted level lists.
+static void build_level_schedule(LuPlan &P)
+{
+    P.sched.assign((size_t)P.nlevels, {});
+    for (int32_t l = 0; l < P.nlevels; l++) {
+        LuLevelSched &L = P.sched[(size_t)l];
+        const int64_t b = P.levelptr[l], nl = P.nlds[l], e = P.levelptr[l + 1];
+        auto front = [&](int64_t q) -> const LuFrontH & { return P.fr[P.levellist[(size_t)q]]; };
+        for (int64_t q = b; q < b + nl;) {
+            const int c = lds_class(front(q).m);
+            int64_t q2 = q;
+            while (q2 < b + nl && (nl <= 256 || lds_class(front(q2).m) == c)) q2++;
+            L.lds.push_back({q, (int32_t)(q2 - q), c, (int32_t)(L.lds.size() & 1)});
+            q = q2;
+        }
+        L.big_first = b + nl;
+        L.big_count = (int32_t)(e - b - nl);
+        for (int64_t q = b + nl; q < e; q++) { L.bm = std::max(L.bm, front(q).m); L.bk = std::max(L.bk, front(q).k); }
+        for (int jb = 0; jb < L.bk;) {
+            const int w = lu_big_block_width(L.bm - jb);
+            int32_t work = 0;
+            for (int64_t q = b + nl; q < e && !work; q++) work = front(q).k > jb && front(q).m - jb > 4096;
+            L.steps.push_back({jb, w, work});
+            jb += w;
+        }
+    }
+}
+
 void lu_build_plan(const LuSymbolic &Y, LuPlan &P)
 {
     const Symbolic &S = Y.S;
@@ -418,7 +452,6 @@ void lu_build_plan(const LuSymbolic &Y, LuPlan &P)
         for (int64_t f = 0; f < nf; f++) P.levellist[(size_t)cur[P.fr[f].depth]++] = (int32_t)f;
     }
     P.nlds.assign((size_t)P.nlevels, 0);
-    P.nsbig.assign((size_t)P.nlevels, 0);
     for (int32_t l = 0; l < P.nlevels; l++) {
         std::stable_sort(P.levellist.begin() + P.levelptr[l], P.levellist.begin() + P.levelptr[l + 1],
                          [&](int32_t a, int32_t b) {
@@ -426,10 +459,7 @@ void lu_build_plan(const LuSymbolic &Y, LuPlan &P)
                              if (la != lb) return la;
                              return la ? P.fr[a].m > P.fr[b].m : P.fr[a].m < P.fr[b].m;
                          });
-        for (int64_t q = P.levelptr[l]; q < P.levelptr[l + 1]; q++) {
-            P.nlds[l] += P.fr[P.levellist[q]].m <= KVX_LU_LDS_M;
-            P.nsbig[l] += P.fr[P.levellist[q]].m > KVX_LU_SOLVE_BIG_M;
-        }
+        for (int64_t q = P.levelptr[l]; q < P.levelptr[l + 1]; q++) P.nlds[l] += P.fr[P.levellist[q]].m <= KVX_LU_LDS_M;
     }
     // ---- position blocks, solve stages ----------------------------------------------------------------------
     std::vector<int32_t> pblk((size_t)n);
@@ -540,6 +570,21 @@ void lu_build_plan(const LuSymbolic &Y, LuPlan &P)
             std::sort(tmp.begin(), tmp.end());
             for (int64_t q = a; q < b; q++) { P.a_dst[(size_t)q] = tmp[(size_t)(q - a)].first; P.a_src[(size_t)q] = tmp[(size_t)(q - a)].second; }
         }
+    }
+    build_level_schedule(P);
+}
+
+void lu_dump_levels(const LuPlan &P, FILE *out)
+{
+    for (int32_t l = P.nlevels - 1; l >= 0; l--) {
+        int mm = 0, mk = 0, mc = 0; int64_t nc = 0, mku = 0;
+        for (int64_t q = P.levelptr[l]; q < P.levelptr[l + 1]; q++) {
+            const LuFrontH &f = P.fr[P.levellist[q]];
+            mm = std::max(mm, f.m); mk = std::max(mk, f.k); mc = std::max(mc, f.nchild); nc += f.nchild;
+            mku = std::max<int64_t>(mku, (int64_t)f.k * f.m);
+        }
+        fprintf(out, "  lu level %2d: %6lld fronts (%lld in LDS)  max m %4d  max k %4d  max children %3d  children %lld  max k*m %lld\n", (int)l,
+                (long long)(P.levelptr[l + 1] - P.levelptr[l]), (long long)P.nlds[l], mm, mk, mc, (long long)nc, (long long)mku);
     }
 }
 

@@ -17,6 +17,7 @@
 #pragma once
 #include "symbolic.hpp"
 #include <cstdint>
+#include <cstdio>
 #include <vector>
 
 namespace kvx {
@@ -49,6 +50,28 @@ struct LuFrontH {
     int32_t depth;
 };
 
+constexpr int KVX_LU_SOLVE_BIG_M = 384;   // fronts of order > this are swept by many workgroups (one launch per 32 pivots); their solve
+                                          // work vector holds all m entries (the update part at offset k)
+constexpr int KVX_LU_LDS_M = 112;        // fronts of order <= this are assembled in LDS and eliminated in registers (7 x 7 tile per thread)
+
+// pivots per block while `rows` rows of the level's tallest front remain (the register budget of the panel's workgroup)
+inline int lu_big_block_width(int rows) { return rows <= 1024 ? 32 : (rows <= 2048 ? 16 : 8); }
+
+// Factor-side schedule of one level, built with the plan (lu_build_plan): what a numeric pass launches, in launch order.  The
+// level loop (lu_factor.cpp), the interchange flags, the plan dump and the launcher read it; none of them derives a width or a
+// maximum itself.
+struct LuLdsLaunch { int64_t first; int32_t count, cls, side; };   // levellist[first .. first + count): one launch of LDS class
+                                                                    // cls (16, 32, 48, 64, 88, 112) on side 0 (st) / 1 (st3)
+struct LuBigStep { int32_t jb, width, lds_work; };                  // pivot block [jb, jb + width); lds_work: some front of the level
+                                                                    // has k > jb and more than 4096 rows left (k_lub_panel has work)
+struct LuLevelSched {
+    std::vector<LuLdsLaunch> lds;         // runs of one class (the list is sorted by m descending); a level of at most 256 LDS
+                                          // fronts is ONE launch sized for its largest front; sides alternate 0, 1, 0, ...
+    int64_t big_first = 0;                // the blocked part: levellist[big_first .. big_first + big_count), the fronts of m > KVX_LU_LDS_M
+    int32_t big_count = 0, bm = 0, bk = 0;   // largest order / pivot count among them
+    std::vector<LuBigStep> steps;         // their pivot blocks: widths lu_big_block_width(bm - jb) from jb = 0 while jb < bk
+};
+
 struct LuPlan {
     int64_t n = 0, nfront = 0;
     std::vector<int64_t> qcol;            // [n] column of A at position j
@@ -71,7 +94,7 @@ struct LuPlan {
     std::vector<int64_t> levelptr;        // level L = fronts at depth L (roots: 0)
     std::vector<int32_t> levellist;       // inside a level: LDS-resident fronts first (largest first), then the big ones (smallest first)
     std::vector<int32_t> nlds;            // [nlevels] how many fronts of the level are LDS resident (m <= lds_m)
-    std::vector<int32_t> nsbig;           // [nlevels] how many fronts (the LAST of the level's list) take the multi-workgroup solve path
+    std::vector<LuLevelSched> sched;      // [nlevels] the launches of a numeric pass over the level
     // triangular solves: stages = (block level, tree depth) pairs; without BTF one block level, stages = tree levels
     int32_t nblev = 1, nstage = 0;
     std::vector<int32_t> levstage;        // [nblev+1] stage range of every block level (stage = levstage[l] + depth)
@@ -91,10 +114,6 @@ struct LuPlan {
     int64_t lnz_bound = 0, unz_bound = 0;
 };
 
-constexpr int KVX_LU_SOLVE_BIG_M = 384;   // fronts of order > this are swept by many workgroups (one launch per 32 pivots); their solve
-                                          // work vector holds all m entries (the update part at offset k)
-constexpr int KVX_LU_LDS_M = 112;        // fronts of order <= this are assembled in LDS and eliminated in registers (7 x 7 tile per thread)
-
 // values may be nullptr (pattern-only: plain maximum transversal).  Throws std::runtime_error on invalid input.
 // no_btf: one block, empty F, one block level whatever the matrix and the environment say (umfpack.c:240-290, umfpack_*_symbolic:
 // UMFPACK's P R A Q = L U has no off-diagonal part).
@@ -102,6 +121,9 @@ void lu_analyze(int64_t n, const int64_t *Ap, const int64_t *Ai, const double *A
 
 // Builds the plan for the current merge state of Y.
 void lu_build_plan(const LuSymbolic &Y, LuPlan &P);
+
+// One line per level, deepest first (KVX_LU_DUMP_PLAN): fronts, LDS-resident, largest m / k / child count, children of the level.
+void lu_dump_levels(const LuPlan &P, FILE *out);
 
 // Merge the base-supernode groups whose fronts are listed (front indices of `P`) into their parents.
 // Returns false when one of them is a root (nothing to merge into: singular).

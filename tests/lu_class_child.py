@@ -1,7 +1,7 @@
 """Child process and shared helpers of the sparse-LU kernel-class tests (test_lu_classes_gpu.py, test_lu_bounds.py).
 
-The routing knobs of the LU path (KVX_LU_WP, KVX_LU_WP_MAXCNT, KVX_LU_LDS_LEGACY: statics of launch_lu_fronts; KVX_LU_UNBLOCKED,
-KVX_LU_GRAPH: member initialisers of kvx_lu_num; KVX_LU_NO_BTF: read by the analysis) are read once per process or per factor, so
+The routing knobs of the LU path (KVX_LU_WP, KVX_LU_WP_MAXCNT, KVX_LU_LDS_LEGACY, KVX_LU_UNBLOCKED, KVX_LU_GRAPH: lu_internal.hpp
+LuKnobs, read when a numeric object is created; KVX_LU_NO_BTF: read by the analysis) hold for the life of a factor, so
 every setting runs in a process of its own.  For each case named on the command line the child factors (klu.numeric), refactors
 with values perturbed by +-5 % (the REUSE kernels), refactors twice more from the same buffers (capture, then replay of the launch
 graph), and after every step checks the factor, the solves, the pivot rule and the structure against bounds that come from the
@@ -18,7 +18,7 @@ Bounds (u = 2^-53, gamma_k = k u / (1 - k u); L, U, P, Q, R, F of klu.get_numeri
   factor  |R P A Q - (L U + F)| <= gamma_{n+2} |L| |U| entrywise (Higham, Accuracy and Stability, Thm 9.3, for any elimination order
           and any pivot choice; 2 more for the row scaling), dense for n <= 2100 (on 256 seeded columns above), sparse otherwise;
   solve   |R P b - (L U + F) Q'x| <= gamma_{3n+4} (|L| |U| + |F|) |Q'x| (Thm 9.4 with the scalings), mirrored for A'x = b;
-  pivots  max |L_ij| <= (1 + 4u) / stol, stol = 1e-3 (lu_api.cpp)."""
+  pivots  max |L_ij| <= (1 + 4u) / stol, stol = 1e-3 (lu_internal.hpp)."""
 import hashlib
 import json
 import os
@@ -58,7 +58,7 @@ def lds_T(m):
 
 
 def block_width(rows):
-    """lu_device.hpp lu_big_block_width"""
+    """lu_symbolic.hpp lu_big_block_width"""
     return 32 if rows <= 1024 else (16 if rows <= 2048 else 8)
 
 

@@ -160,3 +160,33 @@ def test_graphs_off_gives_the_same_bits():
 def test_no_btf():
     res = child.run_setting({"KVX_LU_NO_BTF": 1}, ["bp_800", "mixeda", "mixedb", "mixedc"])
     assert res["bp_800"]["info"]["factored"] == 1
+
+
+def test_knobs_are_read_per_factor(monkeypatch):
+    """LuKnobs is filled when a numeric object is created: a knob changed inside a process holds for the factors made after it and
+    leaves the ones that exist alone"""
+    from kvxopt_amd import klu
+    from kvxopt_amd.base import spmatrix
+    for k in child.KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    n, cp, ri, v = child.case_matrix("d48a")
+    A, As = spmatrix.from_ccs(n, n, cp, ri, v), child.to_csc(n, cp, ri, v)
+    Fs = klu.symbolic(A)
+    child.counts(reset=True)
+    F1 = klu.numeric(A, Fs)
+    c1 = child.counts(reset=True)
+    monkeypatch.setenv("KVX_LU_WP", "0")
+    F2 = klu.numeric(A, Fs)
+    c2 = child.counts(reset=True)
+    assert klu.numeric(A, Fs, F1) is F1
+    c3 = child.counts(reset=True)
+    wp = lambda c: sum(c["wp%d" % t] for t in range(8))
+    tiled = lambda c: sum(c["tiled%d" % t] for t in range(8))
+    assert c1["wp3"] == 1 and wp(c1) == 1 and tiled(c1) == 0 and c1["lds_legacy"] == 0, c1
+    assert c2["tiled3"] == 1 and tiled(c2) == 1 and wp(c2) == 0 and c2["lds_legacy"] == 0, c2
+    assert c3["tiled3"] == 0 and tiled(c3) == 0 and wp(c3) == c3["wp3"] <= 1, c3          # still wp (or a replay: nothing counted)
+    for F in (F1, F2):
+        fa, _ = child.factors_from_get_numeric(n, klu.get_numeric(A, Fs, F))
+        r = child.factor_ratio(As, fa)
+        print("factor ratio %.3e" % r)
+        assert r <= 1.0, r
