@@ -511,6 +511,47 @@ int kvx_gp_eval_dev(kvx_gp *P, const double *Fx_dev, const double *g_dev, const 
                     double *Dfx_dev, double *Hx_dev);
 void kvx_gp_free(kvx_gp *P);
 
+/* ---- ADMM for quadratic programs on one kept Cholesky factor: what kvxopt.osqp (src/C/osqp.c:192-368) gets from the external
+ * OSQP library (osqp_setup / osqp_solve), as the published algorithm (Stellato et al., "OSQP: an operator splitting solver for
+ * quadratic programs", 2020).  minimise 1/2 x'Px + q'x subject to l <= Ax <= u; A is m x n CCS, P n x n CCS of which the lower
+ * triangle is read (Pp == NULL: P = 0); |bound| >= 1e26 is infinite.
+ * kvx_admm_plan (host only): `scaling` Ruiz passes on [[P, A'], [A, 0]] (column infinity norms, below 1e-4 -> 1, above 1e4 ->
+ * 1e4, delta = 1 / sqrt(norm)) each followed by the cost scaling gamma = 1 / max(mean column norm of P, |q|_inf) with the same
+ * limits; returns D (n), E (m), c and nnz of the lower pattern of S = P + sigma I + A' diag(rho) A = tril(P) U I U tril(A'A),
+ * which is analysed once.  The scaled data are c D P D, c D q, E A D, E l, E u; the state below is the scaled one.
+ * kvx_admm_setup_dev(sigma, rho, alpha): uploads, builds the rho vector (1e3 rho on rows with u - l < 1e-4, 1e-6 on rows without
+ * a finite bound, rho elsewhere; rho clipped to [1e-6, 1e6]), assembles S (kvx_atda_assemble_dev) and factors it;
+ * KVX_ENOTPOSDEF: S is not positive definite, the problem is not convex.  x = z = y = 0.
+ * kvx_admm_iterate(k, out): k iterations
+ *     xt = S^-1 (sigma x - q + A'(rho o z - y)),  x+ = alpha xt + (1 - alpha) x,  v = alpha A xt + (1 - alpha) z,
+ *     z+ = clip(v + y / rho, l, u),  y+ = y + rho o (v - z+),  dx = x+ - x,  dy = y+ - y
+ * issued back to back without a host synchronisation, then the residuals of the state in one host read, out[24]:
+ *     [0] |Ax - z|  [1] |Ax|  [2] |z|  [3] |Px + q + A'y|  [4] |Px|  [5] |A'y|  [6] |q|      infinity norms, scaled problem
+ *     [7] .. [13]   the same seven of the unscaled problem (x = D x, z = E^-1 z, y = E y / c)
+ *     [14] |dy|  [15] u'(dy)+ + l'(dy)-  [16] |A'dy|       unscaled, dy without the parts that push against an infinite bound
+ *     [17] |dx|  [18] q'dx  [19] |P dx|  [20] max (A dx)_i over rows with finite u  [21] max -(A dx)_i over rows with finite l
+ *     [22] x'Px  [23] q'x  (scaled; the objective is ([22] / 2 + [23]) / c).  A maximum over no rows is -DBL_MAX.
+ * kvx_admm_set_rho: new rho vector, S reassembled on the same pattern and refactored (no new analysis).
+ * kvx_admm_state: the scaled x (n), z, y (m), dx (n), dy (m) to the host; any pointer may be NULL.
+ * kvx_admm_solution: kind 0: x = D x, y = E y / c;  1: y = the certificate of primal infeasibility ([14]-[16]'s dy), x not
+ * written;  2: x = D dx, the certificate of dual infeasibility, y not written.
+ * kvx_admm_info: m, n, nnz(S), factorisations, iterations, rows summed by 16 lanes, rows summed by a wavefront, set up (0/1).
+ * Fixed summation order, no floating-point atomics: two runs give the same bytes.  Device entry points return KVX_EDEVICE
+ * without a GPU (no CPU fallback).  Null stream. */
+typedef struct kvx_admm kvx_admm;
+int kvx_admm_plan(int64_t m, int64_t n, const int64_t *Ap, const int64_t *Ai, const double *Ax, const int64_t *Pp, const int64_t *Pi,
+                  const double *Px, const double *q, const double *l, const double *u, int64_t scaling, double *D, double *E,
+                  double *c, int64_t *snz, kvx_admm **out);
+int kvx_admm_pattern(kvx_admm *S, int64_t *snz, int64_t *Sp, int64_t *Si);      /* lower CCS pattern of S; pointers may be NULL */
+int kvx_admm_rho_vector(kvx_admm *S, double rho, double *rho_host);             /* host only: the m entries for this rho */
+int kvx_admm_setup_dev(kvx_admm *S, double sigma, double rho, double alpha);
+int kvx_admm_iterate(kvx_admm *S, int64_t k, double *out_host);
+int kvx_admm_set_rho(kvx_admm *S, double rho);
+int kvx_admm_state(kvx_admm *S, double *x, double *z, double *y, double *dx, double *dy);
+int kvx_admm_solution(kvx_admm *S, int kind, double *x, double *y);
+int kvx_admm_info(kvx_admm *S, int64_t info[8]);
+void kvx_admm_free(kvx_admm *S);
+
 /* ---- dense helpers of the equality-constrained KKT solve with a general S (misc.py:1476-1487, 1545): K = A S^-1 A' formed
  * as a dense p x p matrix from X = S^-1 A' (kvx_chol_solve_dev with nrhs = p) when p is moderate ------------------------- */
 /* Y(j, c) = sum_i A(i, j) X(i, c) for the CCS matrix A with n columns and every column c < ncols of the dense X */

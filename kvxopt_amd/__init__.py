@@ -6,4 +6,4 @@ C-ABI HIP library (libkvxhip.so, include/kvxhip.h).  No CPU fallback.
 __version__ = "0.1.0"
 
 # the reference's solver modules mirrored here (`from kvxopt_amd import *` imports them; none of them needs a GPU to import)
-__all__ = ["base", "amd", "cholmod", "klu", "umfpack", "misc", "solvers"]
+__all__ = ["base", "amd", "cholmod", "klu", "umfpack", "osqp", "misc", "solvers"]

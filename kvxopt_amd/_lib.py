@@ -215,6 +215,17 @@ _SIGS = {
     "kvx_gp_pattern": (ctypes.c_int, [vp, i64p, i64p, i64p, i64p, i64p, i64p]),
     "kvx_gp_eval_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "kvx_gp_free": (None, [vp]),
+    "kvx_admm_plan": (ctypes.c_int, [i64, i64, i64p, i64p, f64p, i64p, i64p, f64p, f64p, f64p, f64p, i64, f64p, f64p, f64p, i64p,
+                                     ctypes.POINTER(vp)]),
+    "kvx_admm_pattern": (ctypes.c_int, [vp, i64p, i64p, i64p]),
+    "kvx_admm_rho_vector": (ctypes.c_int, [vp, f64, f64p]),
+    "kvx_admm_setup_dev": (ctypes.c_int, [vp, f64, f64, f64]),
+    "kvx_admm_iterate": (ctypes.c_int, [vp, i64, f64p]),
+    "kvx_admm_set_rho": (ctypes.c_int, [vp, f64]),
+    "kvx_admm_state": (ctypes.c_int, [vp, f64p, f64p, f64p, f64p, f64p]),
+    "kvx_admm_solution": (ctypes.c_int, [vp, ctypes.c_int, f64p, f64p]),
+    "kvx_admm_info": (ctypes.c_int, [vp, i64p]),
+    "kvx_admm_free": (None, [vp]),
     "kvx_vec_scatter_dev": (ctypes.c_int, [i64, vp, vp, vp]),
     "kvx_nts_colscale_dev": (ctypes.c_int, [i64, vp, vp, vp, vp]),
     "kvx_spmm_t_dev": (ctypes.c_int, [i64, i64, vp, vp, vp, vp, i64, vp, i64]),

@@ -1,0 +1,319 @@
+"""`kvxopt.osqp` on the GPU (src/C/osqp.c): quadratic programs by ADMM on one kept Cholesky factor.
+
+    solve(q, A, l, u, P=None, options=None) -> (status, x, y)        minimise 1/2 x'Px + q'x  s.t.  l <= Ax <= u    osqp.c:374-432
+    qp(q, G, h, A=None, b=None, P=None, options=None) -> (status, x, z, y)         ... s.t. Gx <= h, Ax = b        osqp.c:442-572
+    options                                                          the module-level dict of the reference
+
+The reference binds the external OSQP library; here the published algorithm (Stellato et al. 2020) runs in HBM through the
+kvx_admm_* entry points of include/kvxhip.h: the plan equilibrates the data on the host, S = P + sigma I + A' diag(rho) A is
+assembled on a fixed pattern and factored once (again only when rho adapts), and an iteration is two short kernels around one
+triangular solve; a termination check reads 24 doubles.  DESIGN section 11 fixes every rule (scaling, rho classes, termination,
+certificates, adaptive rho).  The answers follow the algorithm, not libosqp bit for bit.
+
+A, G, P are sparse 'd' matrices (ours or kvxopt's), q, l, u, h, b dense 'd' vectors; of P the lower triangle is read.  Results are
+numpy arrays, as everywhere in this package.  For a status other than solved / infeasible, x and y are zero vectors, as the
+reference's freshly allocated matrices are.  'linsys_solver', 'time_limit', 'delta', 'polish_refine_iter', 'adaptive_rho_fraction'
+and 'warm_start' are accepted without effect (every call starts from zero); 'polish' is not built and raises.
+"""
+import ctypes
+import math
+import warnings
+
+import numpy as np
+
+from . import _lib
+from . import base as _base
+from ._lib import pd, pi
+
+options = {}
+
+INFTY = 1e30
+_NEG_MAX = -1.7976931348623157e308
+
+_INT_OPTS = ("scaling", "adaptive_rho", "adaptive_rho_interval", "max_iter", "linsys_solver", "polish", "polish_refine_iter", "verbose",
+             "scaled_termination", "check_termination", "warm_start")
+_FLOAT_OPTS = ("adaptive_rho_tolerance", "adaptive_rho_fraction", "rho", "sigma", "eps_abs", "eps_rel", "eps_prim_inf", "eps_dual_inf",
+               "alpha", "delta", "time_limit")
+_DEFAULTS = {"scaling": 10, "adaptive_rho": 1, "adaptive_rho_interval": 0, "adaptive_rho_tolerance": 5.0, "adaptive_rho_fraction": 0.4,
+             "rho": 0.1, "sigma": 1e-6, "max_iter": 4000, "eps_abs": 1e-3, "eps_rel": 1e-3, "eps_prim_inf": 1e-4, "eps_dual_inf": 1e-4,
+             "alpha": 1.6, "delta": 1e-6, "linsys_solver": 0, "polish": 0, "polish_refine_iter": 3, "verbose": 1, "scaled_termination": 0,
+             "check_termination": 25, "warm_start": 1, "time_limit": 0.0}
+
+
+def _settings(opts):
+    """The settings of one call: the defaults overridden by `opts` (osqp.c:225-269)."""
+    if not isinstance(opts, dict):
+        opts = options
+    if not isinstance(opts, dict):
+        raise AttributeError("missing osqp.options dictionary")
+    o = dict(_DEFAULTS)
+    for key, value in opts.items():
+        if not isinstance(key, str):
+            continue
+        if key in _INT_OPTS:
+            o[key] = int(value)
+        elif key in _FLOAT_OPTS:
+            o[key] = float(value)
+        else:
+            warnings.warn("Invalid parameter name: " + key, RuntimeWarning, stacklevel=4)
+    if o["polish"]:
+        raise NotImplementedError("kvxopt_amd.osqp: 'polish' is not built (the ADMM iterates are returned as they are)")
+    return o
+
+
+def _is_sparse_d(A):
+    if isinstance(A, _base.spmatrix):
+        return A.typecode == "d"
+    return hasattr(A, "CCS") and getattr(A, "typecode", None) == "d"
+
+
+def _vector(v, name, rows):
+    """A dense 'd' vector of `rows` entries as a float64 array (the checks of osqp.c:393-409)."""
+    if isinstance(v, _base.matrix) or (hasattr(v, "typecode") and hasattr(v, "size") and not hasattr(v, "CCS")):
+        if v.typecode != "d":
+            raise TypeError("%s must be a matrix with typecode 'd'" % name)
+        size = tuple(v.size)
+    elif isinstance(v, np.ndarray) and v.dtype == np.float64 and v.ndim in (1, 2):
+        size = (v.shape[0], 1 if v.ndim == 1 else v.shape[1])
+    else:
+        raise TypeError("%s must be a matrix with typecode 'd'" % name)
+    if size[0] != rows or size[1] != 1:
+        raise ValueError("incompatible dimensions")
+    return _base.flat(v).copy()
+
+
+class _Solver:
+    """One problem on the device: the handle of kvx_admm_plan / kvx_admm_setup_dev.  D, E, c are the plan's scaling."""
+
+    def __init__(self, q, Acc, l, u, Pcc=None, scaling=10):
+        m, n, Ap, Ai, Ax = Acc
+        self.m, self.n = int(m), int(n)
+        self._h = None
+        L = _lib.lib()
+        q, l, u = _lib.as_f64(q), _lib.as_f64(l), _lib.as_f64(u)
+        Ap, Ai, Ax = _lib.as_i64(Ap), _lib.as_i64(Ai), _lib.as_f64(Ax)
+        self.D, self.E = np.empty(self.n), np.empty(self.m)
+        c, snz, h = ctypes.c_double(), ctypes.c_int64(), ctypes.c_void_p()
+        if Pcc is None:
+            Pa = (None, None, None)
+        else:
+            keep = [_lib.as_i64(Pcc[0]), _lib.as_i64(Pcc[1]), _lib.as_f64(Pcc[2])]
+            Pa = (pi(keep[0]), pi(keep[1]), pd(keep[2]))
+        _lib.raise_for(L.kvx_admm_plan(self.m, self.n, pi(Ap), pi(Ai), pd(Ax), Pa[0], Pa[1], Pa[2], pd(q), pd(l), pd(u), int(scaling),
+                                       pd(self.D), pd(self.E), ctypes.byref(c), ctypes.byref(snz), ctypes.byref(h)), "kvx_admm_plan")
+        self._h, self.c, self.snz = h, c.value, snz.value
+        self.rho = None
+
+    def pattern(self):
+        Sp, Si = np.empty(self.n + 1, dtype=np.int64), np.empty(self.snz, dtype=np.int64)
+        _lib.raise_for(_lib.lib().kvx_admm_pattern(self._h, None, pi(Sp), pi(Si)))
+        return Sp, Si
+
+    def rho_vector(self, rho):
+        out = np.empty(self.m)
+        _lib.raise_for(_lib.lib().kvx_admm_rho_vector(self._h, float(rho), pd(out)))
+        return out
+
+    def setup(self, sigma=1e-6, rho=0.1, alpha=1.6):
+        rc = _lib.lib().kvx_admm_setup_dev(self._h, float(sigma), float(rho), float(alpha))
+        if rc == _lib.KVX_ENOTPOSDEF:
+            raise ArithmeticError(_lib.last_error() or "the problem is not convex")
+        _lib.raise_for(rc, "kvx_admm_setup_dev")
+        self.rho = min(max(float(rho), 1e-6), 1e6)
+        return self
+
+    def iterate(self, k):
+        """k iterations without a host synchronisation, then the 24 residual numbers of kvx_admm_iterate."""
+        out = np.empty(24)
+        _lib.raise_for(_lib.lib().kvx_admm_iterate(self._h, int(k), pd(out)), "kvx_admm_iterate")
+        return out
+
+    def set_rho(self, rho):
+        _lib.raise_for(_lib.lib().kvx_admm_set_rho(self._h, float(rho)), "kvx_admm_set_rho")
+        self.rho = min(max(float(rho), 1e-6), 1e6)
+
+    def state(self):
+        """The scaled x, z, y, dx, dy."""
+        x, z, y, dx, dy = np.empty(self.n), np.empty(self.m), np.empty(self.m), np.empty(self.n), np.empty(self.m)
+        _lib.raise_for(_lib.lib().kvx_admm_state(self._h, pd(x), pd(z), pd(y), pd(dx), pd(dy)), "kvx_admm_state")
+        return x, z, y, dx, dy
+
+    def solution(self, kind=0):
+        """kind 0: the unscaled (x, y); 1: the certificate of primal infeasibility as y; 2: of dual infeasibility as x."""
+        x, y = np.zeros(self.n), np.zeros(self.m)
+        _lib.raise_for(_lib.lib().kvx_admm_solution(self._h, int(kind), pd(x) if kind != 1 else None, pd(y) if kind != 2 else None),
+                       "kvx_admm_solution")
+        return x, y
+
+    def info(self):
+        out = np.zeros(8, dtype=np.int64)
+        _lib.raise_for(_lib.lib().kvx_admm_info(self._h, pi(out)))
+        return dict(zip(("m", "n", "snz", "factorisations", "iterations", "short_rows", "long_rows", "on_device"), (int(v) for v in out)))
+
+    def close(self):
+        if self._h is not None:
+            _lib.lib().kvx_admm_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _judge(res, o, mult):
+    """The status the residual vector `res` gives at tolerances times `mult`, or None (termination, certificates)."""
+    ea, er, epi, edi = o["eps_abs"] * mult, o["eps_rel"] * mult, o["eps_prim_inf"] * mult, o["eps_dual_inf"] * mult
+    b = 0 if o["scaled_termination"] else 7
+    prim = res[b] <= ea + er * max(res[b + 1], res[b + 2])
+    dual = res[b + 3] <= ea + er * max(res[b + 4], res[b + 5], res[b + 6])
+    if prim and dual:
+        return "solved"
+    ndy, ndx = res[14], res[17]
+    if not prim and ndy > epi and res[15] < -epi * ndy and res[16] < epi * ndy:
+        return "primal infeasible"
+    if not dual and ndx > edi and res[18] < -edi * ndx and res[19] < edi * ndx and res[20] <= edi * ndx and res[21] <= edi * ndx:
+        return "dual infeasible"
+    return None
+
+
+def _new_rho(res, rho):
+    """The rho the scaled residuals ask for (adaptive rho)."""
+    pr = res[0] / (max(res[1], res[2]) + 1e-10)
+    du = res[3] / (max(res[4], res[5], res[6]) + 1e-10)
+    return min(max(rho * math.sqrt(pr / (du + 1e-10)), 1e-6), 1e6)
+
+
+def _run(S, o):
+    """The ADMM loop on a solver that is set up: (status, iterations).  One host read per check."""
+    check, max_iter = o["check_termination"], o["max_iter"]
+    adaptive = bool(o["adaptive_rho"])
+    interval = (o["adaptive_rho_interval"] or 100) if adaptive else 0
+    it = 0
+    if o["verbose"]:
+        print("iter   objective    pri res    dua res    rho")
+    while True:
+        nxt = max_iter
+        if check > 0:
+            nxt = min(nxt, (it // check + 1) * check)
+        if adaptive:
+            nxt = min(nxt, (it // interval + 1) * interval)
+        res = S.iterate(max(nxt - it, 0))
+        it = max(nxt, it)
+        checked = check > 0 and it % check == 0
+        if checked or it >= max_iter:
+            if o["verbose"]:
+                b = 0 if o["scaled_termination"] else 7
+                print("%4d %12.4e  %9.2e  %9.2e  %8.2e" % (it, (0.5 * res[22] + res[23]) / S.c, res[b], res[b + 3], S.rho))
+            status = _judge(res, o, 1.0) if checked else None
+            if status is None and it >= max_iter:
+                status = _judge(res, o, 10.0)
+                status = status + " inaccurate" if status else "maximum iterations reached"
+            if status is not None:
+                return status, it
+        if adaptive and it % interval == 0:
+            rho = _new_rho(res, S.rho)
+            if rho > o["adaptive_rho_tolerance"] * S.rho or rho < S.rho / o["adaptive_rho_tolerance"]:
+                S.set_rho(rho)
+
+
+def _solve(q, Acc, l, u, Pcc, opts, stats=None):
+    o = _settings(opts)
+    _lib.require_device()
+    S = _Solver(q, Acc, l, u, Pcc, o["scaling"])
+    try:
+        S.setup(o["sigma"], o["rho"], o["alpha"])
+        status, it = _run(S, o)
+        if status.startswith("solved"):
+            x, y = S.solution(0)
+        elif status.startswith("primal infeasible"):
+            x, y = S.solution(1)
+        elif status.startswith("dual infeasible"):
+            x, y = S.solution(2)
+        else:
+            x, y = np.zeros(S.n), np.zeros(S.m)
+        if stats is not None:
+            stats.update(S.info())
+            stats["rho"] = S.rho
+        if o["verbose"]:
+            print("status: %s, %d iterations, %d factorisations" % (status, it, S.info()["factorisations"]))
+        return status, x, y
+    finally:
+        S.close()
+
+
+def _sparse_arg(M, name, exc):
+    if not _is_sparse_d(M):
+        raise exc("%s must be a sparse 'd' matrix" % name)
+    return _base.ccs(M)
+
+
+def _lower(P, n, text):
+    Pm, Pn, Pp, Pi, Px = _sparse_arg(P, "P", ValueError)
+    if Pm != n or Pn != n:
+        raise ValueError(text)
+    cols = np.repeat(np.arange(n, dtype=np.int64), np.diff(Pp))
+    keep = Pi >= cols
+    lp_ = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cols[keep], minlength=n), out=lp_[1:])
+    return lp_, Pi[keep].copy(), Px[keep].copy()
+
+
+def solve(q, A, l, u, P=None, options=None, _stats=None):
+    """minimize 0.5 x' P x + q' x  subject to  l <= A x <= u  (osqp.c:374-432): (status, x, y)."""
+    Acc = _sparse_arg(A, "A", TypeError)
+    m, n = Acc[0], Acc[1]
+    if m <= 0:
+        raise ValueError("m must be a positive integer")
+    if n <= 0:
+        raise ValueError("n must be a positive integer")
+    q = _vector(q, "q", n)
+    u = _vector(u, "u", m)
+    l = _vector(l, "l", m)
+    Pcc = _lower(P, n, "incompatible dimensions") if P is not None else None
+    return _solve(q, Acc, l, u, Pcc, options, _stats)
+
+
+def resize_problem(G, h, A, b):
+    """[G; A] with l = (-INFTY, b), u = (h, b) as CCS arrays and vectors (osqp.c:104-190): ((m + p, n, colptr, rowind, values), l, u)."""
+    m, n, Gp, Gi, Gx = G
+    if A is None:
+        return G, np.full(m, -INFTY), h.copy()
+    p, _, Ap, Ai, Ax = A
+    colptr = Gp + Ap
+    rowind, values = np.empty(colptr[-1], dtype=np.int64), np.empty(colptr[-1])
+    gc, ac = np.diff(Gp), np.diff(Ap)
+    gpos = np.repeat(colptr[:-1] - Gp[:-1], gc) + np.arange(Gp[-1])                    # column j: G's entries, then A's
+    apos = np.repeat(colptr[:-1] + gc - Ap[:-1], ac) + np.arange(Ap[-1])
+    rowind[gpos], values[gpos] = Gi, Gx
+    rowind[apos], values[apos] = Ai + m, Ax
+    return (m + p, n, colptr, rowind, values), np.concatenate([np.full(m, -INFTY), b]), np.concatenate([h, b])
+
+
+def qp(q, G, h, A=None, b=None, P=None, options=None, _stats=None):
+    """minimize (1/2) x'Px + q'x  subject to  Gx <= h, Ax = b  (osqp.c:442-572): (status, x, z, y)."""
+    Gcc = _sparse_arg(G, "G", TypeError)
+    m, n = Gcc[0], Gcc[1]
+    if m <= 0:
+        raise ValueError("m must be a positive integer")
+    if n <= 0:
+        raise ValueError("n must be a positive integer")
+    h = _vector(h, "h", m)
+    q = _vector(q, "q", n)
+    Acc, p = None, 0
+    if A is not None:
+        Acc = _sparse_arg(A, "A", ValueError)
+        p = Acc[0]
+        if Acc[1] != n:
+            raise ValueError("incompatible dimensions")
+    if b is not None:
+        b = _vector(b, "b", p)
+    elif p:
+        raise ValueError("incompatible dimensions")
+    Pcc = _lower(P, n, "P must be square matrix of n x n") if P is not None else None
+    if p == 0:
+        Acc = None
+    Anew, l, u = resize_problem(Gcc, h, Acc, b)
+    status, x, w = _solve(q, Anew, l, u, Pcc, options, _stats)
+    return status, x, w[:m].copy(), w[m:].copy()

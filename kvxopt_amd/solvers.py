@@ -19,7 +19,8 @@ Like the reference, algorithm parameters come from `solvers.options` ('maxiters'
 take the reference's plug-in, a function `W -> g(x, y, z)` (coneprog.py:323-344, 1969-1981; host round trips per factorisation
 and solve, lp.KKTUserHost) on the orthant; with 'q' / 's' cones the KKT system is misc.kkt_chol on the GPU (for coneqp with H = P)
 and any `kktsolver` raises.  The named solvers ('ldl', 'ldl2', 'qr', 'chol', 'chol2') and `solver=` (external codes) are not part
-of this path and raise.  coneqp reads 'use_correction' as well.
+of this path and raise -- except `lp / qp (..., solver='osqp')` (coneprog.py:2818-2906, 4391-4603), which run kvxopt_amd.osqp (ADMM on
+one kept Cholesky factor) with the options of `options['osqp']`.  coneqp reads 'use_correction' as well.
 """
 import numpy as np
 
@@ -27,6 +28,7 @@ from . import base as _base
 from . import cone as _cone
 from . import cvx as _cvx
 from . import lp as _lp
+from . import osqp as _osqp
 
 options = {}
 
@@ -95,14 +97,112 @@ def gp(K, F, g, G=None, h=None, A=None, b=None, kktsolver=None, **kw):
     return _cvx.gp(K, F, g, G, h, A, b, kktsolver, options=_cvx_opts(kw))
 
 
+def _osqp_args(kw):
+    """The arguments of a `solver='osqp'` call: options['osqp'] of the keyword `options` or of the module's dict."""
+    kw.pop("solver")
+    kw.pop("kktsolver", None)                            # the reference ignores it on this path
+    o = dict(options)
+    o.update(kw.pop("options", None) or {})
+    if kw:
+        raise TypeError("unexpected arguments: %s" % ", ".join(sorted(kw)))
+    return o.get("osqp", None)
+
+
+def _sp(M):
+    """A dense matrix as a sparse one with every entry stored (coneprog.py:2824-2827, 4398-4403); sparse and None unchanged."""
+    if isinstance(M, np.ndarray):
+        M = _base.matrix(np.asarray(M, dtype=np.float64).reshape(M.shape[0], -1))
+    return _base._full_pattern(M)
+
+
+def _mv(M, x, trans=False):
+    """M x (or M'x) of a CCS matrix in numpy."""
+    m, n, cp, ri, v = _base.ccs(M)
+    cols = np.repeat(np.arange(n, dtype=np.int64), np.diff(cp))
+    if trans:
+        return np.bincount(cols, weights=v * x[ri], minlength=n)
+    return np.bincount(ri, weights=v * x[cols], minlength=m)
+
+
+def _osqp_result(status, x, s, y, z, pcost, dcost, gap, relgap, pres, dres, pslack, dslack):
+    return {"status": status, "x": x, "s": s, "y": y, "z": z, "primal objective": pcost, "dual objective": dcost, "gap": gap,
+            "relative gap": relgap, "primal infeasibility": pres, "dual infeasibility": dres, "primal slack": pslack,
+            "dual slack": dslack, "residual as primal infeasibility certificate": None,
+            "residual as dual infeasibility certificate": None}
+
+
+def _nrm2(v):
+    return float(np.sqrt(np.dot(v, v)))
+
+
+def _relgap(gap, pcost, dcost):
+    return gap / -pcost if pcost < 0.0 else (gap / dcost if dcost > 0.0 else None)
+
+
+def _lp_osqp(c, G, h, A, b, opts):
+    """solvers.lp(..., solver='osqp') (coneprog.py:2818-2906): osqp.qp, then the reference's dictionary from x, z, y."""
+    G, A = _sp(G), _sp(A)
+    status, x, z, y = _osqp.qp(c, G, h, A, b, options=opts)
+    if status == "solved":
+        status = "optimal"
+    if status != "optimal":
+        return _osqp_result(status, x, None, y, z, None, None, None, None, None, None, None, None)
+    c, h = _flat(c), _flat(h)
+    b = _flat(b) if A is not None and b is not None else np.zeros(0)
+    pcost = float(np.dot(c, x))
+    dcost = -float(np.dot(h, z)) - float(np.dot(b, y))
+    s = h - _mv(G, x)
+    gap = float(np.dot(s, z))
+    rx = c + _mv(G, z, True) + (_mv(A, y, True) if b.size else 0.0)
+    ry = b - _mv(A, x) if b.size else np.zeros(0)
+    rz = _mv(G, x) + s - h
+    pres = max(_nrm2(ry) / max(1.0, _nrm2(b)), _nrm2(rz) / max(1.0, _nrm2(h)))
+    return _osqp_result(status, x, s, y, z, pcost, dcost, gap, _relgap(gap, pcost, dcost), pres, _nrm2(rx) / max(1.0, _nrm2(c)),
+                        float(s.min()), float(z.min()))
+
+
+def _qp_osqp(P, q, G, h, A, b, opts):
+    """solvers.qp(..., solver='osqp') (coneprog.py:4391-4408, 4542-4603)."""
+    if G is None:
+        raise NotImplementedError("solvers.qp(..., solver='osqp') needs inequality constraints G x <= h (osqp.qp, osqp.c:455-460)")
+    G, A, P = _sp(G), _sp(A), _sp(P)
+    solsta, x, z, y = _osqp.qp(q, G, h, A, b, P, options=opts)
+    if solsta != "solved":
+        return _osqp_result("unknown", None, None, None, None, None, None, None, None, None, None, None, None)
+    q, h = _flat(q), _flat(h)
+    b = _flat(b) if A is not None and b is not None else np.zeros(0)
+    s = h - _mv(G, x)
+    n = q.size
+    Pp, Pi, Px = _base.lower_ccs(P, n)                  # base.symv reads the lower triangle
+    cols = np.repeat(np.arange(n, dtype=np.int64), np.diff(Pp))
+    off = Pi != cols
+    rx = q + np.bincount(Pi, weights=Px * x[cols], minlength=n) + np.bincount(cols[off], weights=Px[off] * x[Pi[off]], minlength=n)
+    pcost = 0.5 * (float(np.dot(x, rx)) + float(np.dot(x, q)))
+    if b.size:
+        rx = rx + _mv(A, y, True)
+    rx = rx + _mv(G, z, True)
+    ry = _mv(A, x) - b if b.size else np.zeros(0)
+    rz = _mv(G, x) + s - h
+    gap = float(np.dot(s, z))
+    dcost = pcost + float(np.dot(y, ry)) + float(np.dot(z, rz)) - gap
+    pres = max(_nrm2(ry) / max(1.0, _nrm2(b)), _nrm2(rz) / max(1.0, _nrm2(h)))
+    return _osqp_result("optimal", x, s, y, z, pcost, dcost, gap, _relgap(gap, pcost, dcost), pres, _nrm2(rx) / max(1.0, _nrm2(q)),
+                        float(s.min()), float(z.min()))
+
+
 def lp(c, G, h, A=None, b=None, primalstart=None, dualstart=None, **kw):
-    """solvers.lp (coneprog.py:2551-2790): conelp on the orthant, result keys as the reference returns them."""
+    """solvers.lp (coneprog.py:2551-2790): conelp on the orthant, result keys as the reference returns them;
+    solver='osqp': kvxopt_amd.osqp.qp with P = 0 (coneprog.py:2818-2906)."""
+    if kw.get("solver", None) == "osqp":
+        return _lp_osqp(c, G, h, A, b, _osqp_args(kw))
     sol = conelp(c, G, h, None, A, b, primalstart, dualstart, **kw)
     return sol
 
 
 def qp(P, q, G, h, A=None, b=None, initvals=None, **kw):
-    """solvers.qp (coneprog.py:4120-4330): coneqp on the orthant."""
+    """solvers.qp (coneprog.py:4120-4330): coneqp on the orthant; solver='osqp': kvxopt_amd.osqp.qp (coneprog.py:4391-4603)."""
+    if kw.get("solver", None) == "osqp":
+        return _qp_osqp(P, q, G, h, A, b, _osqp_args(kw))
     return coneqp(P, q, G, h, None, A, b, initvals, **kw)
 
 
