@@ -534,7 +534,8 @@ void kvx_gp_free(kvx_gp *P);
  * kvx_admm_set_rho: new rho vector, S reassembled on the same pattern and refactored (no new analysis).
  * kvx_admm_state: the scaled x (n), z, y (m), dx (n), dy (m) to the host; any pointer may be NULL.
  * kvx_admm_solution: kind 0: x = D x, y = E y / c;  1: y = the certificate of primal infeasibility ([14]-[16]'s dy), x not
- * written;  2: x = D dx, the certificate of dual infeasibility, y not written.
+ * written;  2: x = D dx, the certificate of dual infeasibility, y not written;  3: the polished x = D xh, y = E yh / c
+ * (KVX_EINVAL unless the last kvx_admm_polish factored and no kvx_admm_update came after it).
  * kvx_admm_info: m, n, nnz(S), factorisations, iterations, rows summed by 16 lanes, rows summed by a wavefront, set up (0/1).
  * Fixed summation order, no floating-point atomics: two runs give the same bytes.  Device entry points return KVX_EDEVICE
  * without a GPU (no CPU fallback).  Null stream. */
@@ -551,6 +552,40 @@ int kvx_admm_state(kvx_admm *S, double *x, double *z, double *y, double *dx, dou
 int kvx_admm_solution(kvx_admm *S, int kind, double *x, double *y);
 int kvx_admm_info(kvx_admm *S, int64_t info[8]);
 void kvx_admm_free(kvx_admm *S);
+
+/* ---- a problem kept on the device across solves: same pattern, same analysis, same factor.  All after kvx_admm_setup_dev.
+ * kvx_admm_update(q, l, u): host pointers to unscaled data, any of them NULL (kept).  Rescaled on the device with the plan's
+ * D, E, c, which are not recomputed: q := (c D) o q, l := E o l, u := E o u; l <= -1e26 stays -1e30 and u >= 1e26 stays 1e30.  The
+ * rho classes of the rows (equality, free, other) are derived again: if none changed nothing is assembled or factored, else
+ * the rho vector at the current rho is issued, S reassembled on its pattern and factored once (counted by kvx_admm_info).
+ * l_i > u_i: KVX_EINVAL, nothing changed (checked before a device is asked for).  The values of P and A cannot be replaced.
+ * kvx_admm_warm_start(x, y): unscaled host vectors, either NULL (kept): x := D^-1 x and z := A x;  y := (c E^-1) o y;  dx = dy = 0.
+ * kvx_admm_cold_start: x = z = y = dx = dy = 0; rho and the factor are kept.
+ * kvx_admm_polish(delta, refine_iter, out): OSQP's polish in the scaled problem, in the eliminated form of its regularised
+ * system [[P + delta I, A_act'], [A_act, -delta I]]; enqueued without a host synchronisation until the one read of out.
+ *     active set from the state: lower z_i - l_i < -y_i, upper u_i - z_i < y_i;  w_i = 1 / delta on active rows, 0 elsewhere;
+ *     b_i = l_i or u_i;  S_pol = P + delta I + A' diag(w) A assembled on the kept pattern and factored (no analysis);
+ *     first solve   xh = S_pol^-1 (-q + A'(w o b)),  yh = w o (A xh - b);
+ *     refine_iter x e1 = -q - (P xh + A' yh),  e2 = b - A xh on active rows and 0 elsewhere,
+ *                   dx = S_pol^-1 (e1 + A'(w o e2)),  dy = w o (A dx - e2),  xh += dx,  yh += dy;
+ *     zh = clip(A xh, l, u).
+ *   out[16]:  [0] 1: factored, -1: S_pol is not positive definite (the call still returns 0; only [1], [2] are then set)
+ *     [1] rows active at l  [2] rows active at u  [3] |A xh - zh|  [4] |P xh + q + A' yh|  (scaled, as [0], [3] of kvx_admm_iterate)
+ *     [5] [6] the same two of the unscaled problem (as [7], [10] there)  [7] xh'P xh  [8] q'xh  (scaled; objective ([7] / 2 + [8]) / c)
+ *     [9] |e1|  [10] |e2| of the last pass before its correction (refine_iter = 0: of the first solve, |q| and |b|)  [11]-[15] 0.
+ *   The polished vectors live in buffers of their own: the ADMM state is not touched.  The kept numeric factor is now that of
+ *   S_pol and the handle marks the ADMM factor stale: the next kvx_admm_iterate with k > 0 rebuilds it at the current rho first
+ *   (one counted numeric factorisation, no analysis); kvx_admm_set_rho and a class-changing kvx_admm_update rebuild it anyway.
+ *   The polish's own factorisation is counted too.
+ * kvx_admm_polish_state: the scaled xh (n), zh, yh (m) and the flags -1 (at l) / 0 / +1 (at u) to the host; any pointer may be NULL.
+ * kvx_admm_polish_accept: x, z, y := xh, zh, yh and dx = dy = 0, so that the next warm start begins at the polished point.
+ * Whether to accept is the caller's decision.  Fixed summation order, no floating-point atomics; KVX_EDEVICE without a GPU. */
+int kvx_admm_update(kvx_admm *S, const double *q, const double *l, const double *u);
+int kvx_admm_warm_start(kvx_admm *S, const double *x, const double *y);
+int kvx_admm_cold_start(kvx_admm *S);
+int kvx_admm_polish(kvx_admm *S, double delta, int64_t refine_iter, double *out_host);
+int kvx_admm_polish_state(kvx_admm *S, double *x, double *z, double *y, int64_t *act);
+int kvx_admm_polish_accept(kvx_admm *S);
 
 /* ---- dense helpers of the equality-constrained KKT solve with a general S (misc.py:1476-1487, 1545): K = A S^-1 A' formed
  * as a dense p x p matrix from X = S^-1 A' (kvx_chol_solve_dev with nrhs = p) when p is moderate ------------------------- */

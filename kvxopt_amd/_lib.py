@@ -226,6 +226,12 @@ _SIGS = {
     "kvx_admm_solution": (ctypes.c_int, [vp, ctypes.c_int, f64p, f64p]),
     "kvx_admm_info": (ctypes.c_int, [vp, i64p]),
     "kvx_admm_free": (None, [vp]),
+    "kvx_admm_update": (ctypes.c_int, [vp, f64p, f64p, f64p]),
+    "kvx_admm_warm_start": (ctypes.c_int, [vp, f64p, f64p]),
+    "kvx_admm_cold_start": (ctypes.c_int, [vp]),
+    "kvx_admm_polish": (ctypes.c_int, [vp, f64, i64, f64p]),
+    "kvx_admm_polish_state": (ctypes.c_int, [vp, f64p, f64p, f64p, i64p]),
+    "kvx_admm_polish_accept": (ctypes.c_int, [vp]),
     "kvx_vec_scatter_dev": (ctypes.c_int, [i64, vp, vp, vp]),
     "kvx_nts_colscale_dev": (ctypes.c_int, [i64, vp, vp, vp, vp]),
     "kvx_spmm_t_dev": (ctypes.c_int, [i64, i64, vp, vp, vp, vp, i64, vp, i64]),

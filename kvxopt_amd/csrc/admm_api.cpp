@@ -8,9 +8,15 @@
 // A with the pattern tril(P) U I -- sigma has a slot in every column -- and analyses that pattern once.  Everything after the
 // plan runs in HBM: kvx_admm_iterate issues k x {k_admm_rhs, kvx_chol_solve_async_dev, k_admm_update} back to back, then the
 // residual kernels, and reads 24 doubles.  No CPU fallback: without a HIP device the device entry points return KVX_EDEVICE.
+//
+// A handle can be kept across solves: kvx_admm_update replaces q, l, u (rescaled with the kept D, E, c; one refactorisation only
+// when a row changes its rho class), kvx_admm_warm_start / kvx_admm_cold_start set the state, and kvx_admm_polish solves the
+// equality-constrained QP of the guessed active set on S_pol = P + delta I + A' diag(w) A -- the analysed pattern, the same
+// kvx_chol, whose numeric factor it takes over: the handle marks the ADMM factor stale and the next iteration rebuilds it.
 #include "../../include/kvxhip.h"
 #include "abi_guard.hpp"
 #include "admm.hpp"
+#include "admm_polish.hpp"
 #include "devpool.hpp"
 
 #include <algorithm>
@@ -44,6 +50,12 @@ struct kvx_admm {
     AdmmDev d{};
     double *d_Lxs = nullptr, *d_Sx = nullptr, *d_part = nullptr, *d_res = nullptr;
     std::vector<void *> owned;
+    // the kept problem (admm_polish.hip): staging for raw q | x (n), l | y (m), u (m); the polish buffers, allocated at first use
+    bool stale = false;                 // the kept numeric factor is that of S_pol, not of S
+    bool polished = false;              // xh, zh, yh hold the result of a polish that factored
+    PolishDev p{};
+    double *d_stage = nullptr, *d_ppart = nullptr, *d_pres = nullptr, *d_Lxd = nullptr;
+    double lxd_delta = 0.0;
 };
 
 namespace {
@@ -255,6 +267,7 @@ int refactor(kvx_admm *S, double rho)
     if (rc == KVX_ENOTPOSDEF) set_last_error("kvx_admm: P + sigma I + A' diag(rho) A is not positive definite: the problem is not convex");
     if (rc) return rc;
     S->nfact++;
+    S->stale = false;
     return KVX_OK;
 }
 
@@ -297,6 +310,10 @@ int iterate_impl(kvx_admm *S, int64_t k, double *out)
     if (!have_device("kvx_admm_iterate")) return KVX_EDEVICE;
     if (!S->dev) { set_last_error("kvx_admm_iterate: kvx_admm_setup_dev has not run"); return KVX_EINVAL; }
     const int64_t ld = std::max<int64_t>(1, S->n);
+    if (S->stale && k > 0) {                                            // a polish took the factor over: S at the current rho again
+        const int rc = refactor(S, S->rho0);
+        if (rc) return rc;
+    }
     for (int64_t it = 0; it < k; it++) {
         launch_admm_rhs(nullptr, S->d);
         const int rc = kvx_chol_solve_async_dev(S->F, 0, S->d.xt, 1, ld);
@@ -313,6 +330,186 @@ int iterate_impl(kvx_admm *S, int64_t k, double *out)
 int fetch(double *dst, const double *src_dev, int64_t count)
 {
     if (dst && count > 0) HIPCHK(hipMemcpy(dst, src_dev, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    return KVX_OK;
+}
+
+// ---- the kept problem: update, warm start, polish ---------------------------------------------------------------------------
+inline int rho_class(double l, double u)                                 // the three classes of rho_vector: free, equality, other
+{
+    if (l <= -OSQP_INFTY * MIN_SCALING && u >= OSQP_INFTY * MIN_SCALING) return 0;
+    return u - l < RHO_TOL ? 1 : 2;
+}
+
+int need_setup(kvx_admm *S, const char *who)
+{
+    if (!have_device(who)) return KVX_EDEVICE;
+    if (!S->dev) { set_last_error(std::string(who) + ": kvx_admm_setup_dev has not run"); return KVX_EINVAL; }
+    return KVX_OK;
+}
+
+int stage_buffer(kvx_admm *S)
+{
+    if (S->d_stage) return KVX_OK;
+    return zeros(S, &S->d_stage, S->n + 2 * S->m);
+}
+
+int update_impl(kvx_admm *S, const double *q, const double *l, const double *u)
+{
+    if (!S) return KVX_EINVAL;
+    const int64_t m = S->m, n = S->n;
+    std::vector<double> ln, un;
+    bool changed = false;
+    if (l || u) {                                                       // the scaled bounds on the host too: they give the rho classes
+        ln = S->l; un = S->u;
+        for (int64_t i = 0; i < m; i++) {
+            if (l) ln[i] = l[i] <= -OSQP_INFTY * MIN_SCALING ? -OSQP_INFTY : S->E[i] * l[i];
+            if (u) un[i] = u[i] >= OSQP_INFTY * MIN_SCALING ? OSQP_INFTY : S->E[i] * u[i];
+            if (!(ln[i] <= un[i])) { set_last_error("kvx_admm_update: l <= u does not hold"); return KVX_EINVAL; }
+            changed = changed || rho_class(ln[i], un[i]) != rho_class(S->l[i], S->u[i]);
+        }
+    }
+    int rc = need_setup(S, "kvx_admm_update");
+    if (rc || (rc = stage_buffer(S))) return rc;
+    double *sq = S->d_stage, *sl = S->d_stage + n, *su = S->d_stage + n + m;
+    if (q) {
+        HIPCHK(hipMemcpy(sq, q, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        launch_admm_scale_q(nullptr, S->d, S->c, sq, const_cast<double *>(S->d.q));
+        for (int64_t j = 0; j < n; j++) S->q[j] = (S->c * S->D[j]) * q[j];
+    }
+    if (l) {
+        HIPCHK(hipMemcpy(sl, l, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+        launch_admm_scale_bound(nullptr, S->d, false, sl, const_cast<double *>(S->d.l));
+        S->l.swap(ln);
+    }
+    if (u) {
+        HIPCHK(hipMemcpy(su, u, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+        launch_admm_scale_bound(nullptr, S->d, true, su, const_cast<double *>(S->d.u));
+        S->u.swap(un);
+    }
+    HIPCHK(hipGetLastError());
+    S->polished = false;
+    return changed ? refactor(S, S->rho0) : (int)KVX_OK;               // same pattern, same analysis
+}
+
+int warm_start_impl(kvx_admm *S, const double *x, const double *y)
+{
+    if (!S) return KVX_EINVAL;
+    int rc = need_setup(S, "kvx_admm_warm_start");
+    if (rc || (rc = stage_buffer(S))) return rc;
+    const int64_t m = S->m, n = S->n;
+    if (x) {
+        HIPCHK(hipMemcpy(S->d_stage, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        launch_admm_warm_x(nullptr, S->d, S->d_stage);
+    }
+    if (y) {
+        HIPCHK(hipMemcpy(S->d_stage + n, y, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+        launch_admm_warm_y(nullptr, S->d, S->c, S->d_stage + n);
+    }
+    HIPCHK(hipMemsetAsync(S->d.dx, 0, (size_t)n * sizeof(double), nullptr));
+    HIPCHK(hipMemsetAsync(S->d.dy, 0, (size_t)m * sizeof(double), nullptr));
+    HIPCHK(hipGetLastError());
+    return KVX_OK;
+}
+
+int cold_start_impl(kvx_admm *S)
+{
+    if (!S) return KVX_EINVAL;
+    const int rc = need_setup(S, "kvx_admm_cold_start");
+    if (rc) return rc;
+    const size_t nb = (size_t)S->n * sizeof(double), mb = (size_t)S->m * sizeof(double);
+    HIPCHK(hipMemsetAsync(S->d.x, 0, nb, nullptr));
+    HIPCHK(hipMemsetAsync(S->d.dx, 0, nb, nullptr));
+    HIPCHK(hipMemsetAsync(S->d.z, 0, mb, nullptr));
+    HIPCHK(hipMemsetAsync(S->d.y, 0, mb, nullptr));
+    HIPCHK(hipMemsetAsync(S->d.dy, 0, mb, nullptr));
+    return KVX_OK;
+}
+
+// the buffers of the polish, and tril(P) + delta I on the pattern the plan was given
+int polish_buffers(kvx_admm *S, double delta)
+{
+    PolishDev &p = S->p;
+    int rc = 0;
+    if (!p.act) {
+        double *act = nullptr;                                          // m int64 flags in a buffer of the same width
+        if ((rc = zeros(S, &p.w, S->m)) || (rc = zeros(S, &p.b, S->m)) || (rc = zeros(S, &p.xh, S->n)) || (rc = zeros(S, &p.zh, S->m)) ||
+            (rc = zeros(S, &p.yh, S->m)) || (rc = zeros(S, &p.e2, S->m)) || (rc = zeros(S, &p.we2, S->m)) || (rc = zeros(S, &p.rhs, S->n)) ||
+            (rc = zeros(S, &S->d_ppart, POLISH_NRES * polish_part_stride(S->d))) || (rc = zeros(S, &S->d_pres, POLISH_NRES)) ||
+            (rc = zeros(S, &S->d_Lxd, (int64_t)S->Lx.size())) || (rc = zeros(S, &act, S->m)))
+            return rc;
+        static_assert(sizeof(int64_t) == sizeof(double), "the flags share the allocator of the vectors");
+        p.act = reinterpret_cast<int64_t *>(act);
+    }
+    if (S->lxd_delta != delta) {
+        std::vector<double> lxd(S->Lx);
+        for (int64_t j = 0; j < S->n; j++) lxd[S->Lp[j]] += delta;
+        HIPCHK(hipMemcpy(S->d_Lxd, lxd.data(), lxd.size() * sizeof(double), hipMemcpyHostToDevice));
+        S->lxd_delta = delta;
+    }
+    return KVX_OK;
+}
+
+int polish_impl(kvx_admm *S, double delta, int64_t refine_iter, double *out)
+{
+    if (!S || !out || refine_iter < 0 || !(delta > 0.0)) { set_last_error("kvx_admm_polish: delta > 0 and refine_iter >= 0 are required"); return KVX_EINVAL; }
+    int rc = need_setup(S, "kvx_admm_polish");
+    if (rc || (rc = polish_buffers(S, delta))) return rc;
+    PolishDev &p = S->p;
+    p.a = S->d;
+    p.delta = delta;
+    S->polished = false;
+    const int64_t ld = std::max<int64_t>(1, S->n);
+    HIPCHK(hipMemsetAsync(p.xh, 0, (size_t)S->n * sizeof(double), nullptr));
+    HIPCHK(hipMemsetAsync(p.yh, 0, (size_t)S->m * sizeof(double), nullptr));
+    launch_polish_active(nullptr, p, S->d_ppart);
+    if ((rc = kvx_atda_assemble_dev(S->plan, S->d.Ax, p.w, S->d_Lxd, S->d_Sx))) return rc;
+    S->stale = true;                                                    // from here on the kept factor is not that of S
+    if ((rc = kvx_chol_factorize_async_dev(S->F, S->d_Sx))) return rc;
+    S->nfact++;
+    for (int64_t pass = 0; pass <= refine_iter; pass++) {               // the first solve, then the refinement passes
+        launch_polish_residual(nullptr, p, S->d_ppart);
+        if ((rc = kvx_chol_solve_async_dev(S->F, 0, p.rhs, 1, ld))) return rc;
+        launch_polish_correct(nullptr, p);
+    }
+    launch_polish_finish(nullptr, p, S->d_ppart, S->d_pres);
+    HIPCHK(hipGetLastError());
+    double res[POLISH_NRES];
+    HIPCHK(hipMemcpy(res, S->d_pres, sizeof(res), hipMemcpyDeviceToHost));      // the one host synchronisation
+    std::fill(out, out + 16, 0.0);
+    out[1] = res[0]; out[2] = res[1];
+    int64_t minor = 0;
+    rc = kvx_chol_status(S->F, &minor);
+    if (rc == KVX_ENOTPOSDEF) { out[0] = -1.0; return KVX_OK; }         // not an error: the caller keeps the ADMM solution
+    if (rc) return rc;
+    out[0] = 1.0;
+    std::copy(res, res + POLISH_NRES, out + 1);
+    S->polished = true;
+    return KVX_OK;
+}
+
+int polish_state_impl(kvx_admm *S, double *x, double *z, double *y, int64_t *act)
+{
+    if (!S) return KVX_EINVAL;
+    int rc = need_setup(S, "kvx_admm_polish_state");
+    if (rc) return rc;
+    if (!S->p.act) { set_last_error("kvx_admm_polish_state: kvx_admm_polish has not run"); return KVX_EINVAL; }
+    if ((rc = fetch(x, S->p.xh, S->n)) || (rc = fetch(z, S->p.zh, S->m)) || (rc = fetch(y, S->p.yh, S->m))) return rc;
+    if (act) HIPCHK(hipMemcpy(act, S->p.act, (size_t)S->m * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return KVX_OK;
+}
+
+int polish_accept_impl(kvx_admm *S)
+{
+    if (!S) return KVX_EINVAL;
+    const int rc = need_setup(S, "kvx_admm_polish_accept");
+    if (rc) return rc;
+    if (!S->polished) { set_last_error("kvx_admm_polish_accept: no polished solution is held"); return KVX_EINVAL; }
+    const size_t nb = (size_t)S->n * sizeof(double), mb = (size_t)S->m * sizeof(double);
+    HIPCHK(hipMemcpyAsync(S->d.x, S->p.xh, nb, hipMemcpyDeviceToDevice, nullptr));
+    HIPCHK(hipMemcpyAsync(S->d.z, S->p.zh, mb, hipMemcpyDeviceToDevice, nullptr));
+    HIPCHK(hipMemcpyAsync(S->d.y, S->p.yh, mb, hipMemcpyDeviceToDevice, nullptr));
+    HIPCHK(hipMemsetAsync(S->d.dx, 0, nb, nullptr));
+    HIPCHK(hipMemsetAsync(S->d.dy, 0, mb, nullptr));
     return KVX_OK;
 }
 
@@ -359,7 +556,7 @@ int kvx_admm_set_rho(kvx_admm *S, double rho)
         if (!S || !(rho > 0.0)) return (int)KVX_EINVAL;
         if (!have_device("kvx_admm_set_rho")) return (int)KVX_EDEVICE;
         if (!S->dev) { set_last_error("kvx_admm_set_rho: kvx_admm_setup_dev has not run"); return (int)KVX_EINVAL; }
-        return refactor(S, rho);
+        return refactor(S, rho);                                        // also what restores a factor a polish took over
     });
 }
 
@@ -378,17 +575,18 @@ int kvx_admm_state(kvx_admm *S, double *x, double *z, double *y, double *dx, dou
 int kvx_admm_solution(kvx_admm *S, int kind, double *x, double *y)
 {
     return guarded([&] {
-        if (!S || kind < 0 || kind > 2 || (kind != 1 && !x) || (kind != 2 && !y)) return (int)KVX_EINVAL;
+        if (!S || kind < 0 || kind > 3 || (kind != 1 && !x) || (kind != 2 && !y)) return (int)KVX_EINVAL;
+        if (kind == 3 && !S->polished) { set_last_error("kvx_admm_solution: no polished solution is held"); return (int)KVX_EINVAL; }
         if (!have_device("kvx_admm_solution")) return (int)KVX_EDEVICE;
         if (!S->dev) { set_last_error("kvx_admm_solution: kvx_admm_setup_dev has not run"); return (int)KVX_EINVAL; }
         int rc;
         const double cinv = 1.0 / S->c;
-        if (kind != 1) {                                                // x = D x (kind 0), the certificate D dx (kind 2)
-            if ((rc = fetch(x, kind == 0 ? S->d.x : S->d.dx, S->n))) return rc;
+        if (kind != 1) {                                                // x = D x (kind 0), D xh (kind 3), the certificate D dx (kind 2)
+            if ((rc = fetch(x, kind == 0 ? S->d.x : (kind == 3 ? S->p.xh : S->d.dx), S->n))) return rc;
             for (int64_t j = 0; j < S->n; j++) x[j] *= S->D[j];
         }
-        if (kind != 2) {                                                // y = E y / c (kind 0), the certificate E dy / c (kind 1)
-            if ((rc = fetch(y, kind == 0 ? S->d.y : S->d.dy, S->m))) return rc;
+        if (kind != 2) {                                                // y = E y / c (kind 0), E yh / c (kind 3), the certificate E dy / c (kind 1)
+            if ((rc = fetch(y, kind == 0 ? S->d.y : (kind == 3 ? S->p.yh : S->d.dy), S->m))) return rc;
             for (int64_t i = 0; i < S->m; i++) {
                 double v = y[i];
                 if (kind == 1) {                                        // without the parts that push against an infinite bound
@@ -400,6 +598,36 @@ int kvx_admm_solution(kvx_admm *S, int kind, double *x, double *y)
         }
         return (int)KVX_OK;
     });
+}
+
+int kvx_admm_update(kvx_admm *S, const double *q, const double *l, const double *u)
+{
+    return guarded([&] { return update_impl(S, q, l, u); });
+}
+
+int kvx_admm_warm_start(kvx_admm *S, const double *x, const double *y)
+{
+    return guarded([&] { return warm_start_impl(S, x, y); });
+}
+
+int kvx_admm_cold_start(kvx_admm *S)
+{
+    return guarded([&] { return cold_start_impl(S); });
+}
+
+int kvx_admm_polish(kvx_admm *S, double delta, int64_t refine_iter, double *out_host)
+{
+    return guarded([&] { return polish_impl(S, delta, refine_iter, out_host); });
+}
+
+int kvx_admm_polish_state(kvx_admm *S, double *x, double *z, double *y, int64_t *act)
+{
+    return guarded([&] { return polish_state_impl(S, x, z, y, act); });
+}
+
+int kvx_admm_polish_accept(kvx_admm *S)
+{
+    return guarded([&] { return polish_accept_impl(S); });
 }
 
 int kvx_admm_info(kvx_admm *S, int64_t info[8])

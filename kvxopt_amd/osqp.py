@@ -3,6 +3,8 @@
     solve(q, A, l, u, P=None, options=None) -> (status, x, y)        minimise 1/2 x'Px + q'x  s.t.  l <= Ax <= u    osqp.c:374-432
     qp(q, G, h, A=None, b=None, P=None, options=None) -> (status, x, z, y)         ... s.t. Gx <= h, Ax = b        osqp.c:442-572
     options                                                          the module-level dict of the reference
+    Problem(q, A, l, u, P=None, options=None)                        the same problem kept on the device (not in the reference):
+        .update(q, l, u)  .warm_start(x, y)  .solve() -> (status, x, y)  .info  .close()
 
 The reference binds the external OSQP library; here the published algorithm (Stellato et al. 2020) runs in HBM through the
 kvx_admm_* entry points of include/kvxhip.h: the plan equilibrates the data on the host, S = P + sigma I + A' diag(rho) A is
@@ -12,8 +14,14 @@ certificates, adaptive rho).  The answers follow the algorithm, not libosqp bit 
 
 A, G, P are sparse 'd' matrices (ours or kvxopt's), q, l, u, h, b dense 'd' vectors; of P the lower triangle is read.  Results are
 numpy arrays, as everywhere in this package.  For a status other than solved / infeasible, x and y are zero vectors, as the
-reference's freshly allocated matrices are.  'linsys_solver', 'time_limit', 'delta', 'polish_refine_iter', 'adaptive_rho_fraction'
-and 'warm_start' are accepted without effect (every call starts from zero); 'polish' is not built and raises.
+reference's freshly allocated matrices are.  In solve and qp 'linsys_solver', 'time_limit', 'delta', 'polish_refine_iter',
+'adaptive_rho_fraction' and 'warm_start' are accepted without effect (every call starts from zero) and 'polish' raises.
+
+A Problem plans, analyses and factors once and stays in HBM: update() replaces q, l, u (rescaled with the kept scaling; one
+numeric refactorisation only when a row changes its rho class), every solve() continues from the state the last one left
+(warm_start = 0: from zero), rho persists, and 'polish', 'delta', 'polish_refine_iter' take effect: after 'solved' the active
+set is guessed, one equality-constrained QP is solved on the analysed pattern and refined, and the result is taken when its
+residuals are smaller ("A kept problem").
 """
 import ctypes
 import math
@@ -40,8 +48,8 @@ _DEFAULTS = {"scaling": 10, "adaptive_rho": 1, "adaptive_rho_interval": 0, "adap
              "check_termination": 25, "warm_start": 1, "time_limit": 0.0}
 
 
-def _settings(opts):
-    """The settings of one call: the defaults overridden by `opts` (osqp.c:225-269)."""
+def _read_options(opts, stacklevel):
+    """The defaults overridden by `opts` (osqp.c:225-269); a warning for an unknown key is attributed `stacklevel` frames up."""
     if not isinstance(opts, dict):
         opts = options
     if not isinstance(opts, dict):
@@ -55,9 +63,16 @@ def _settings(opts):
         elif key in _FLOAT_OPTS:
             o[key] = float(value)
         else:
-            warnings.warn("Invalid parameter name: " + key, RuntimeWarning, stacklevel=4)
+            warnings.warn("Invalid parameter name: " + key, RuntimeWarning, stacklevel=stacklevel)
+    return o
+
+
+def _settings(opts):
+    """The settings of one call of solve / qp: these return the ADMM iterates as they are."""
+    o = _read_options(opts, 5)
     if o["polish"]:
-        raise NotImplementedError("kvxopt_amd.osqp: 'polish' is not built (the ADMM iterates are returned as they are)")
+        raise NotImplementedError("kvxopt_amd.osqp: 'polish' is not built into solve and qp (the ADMM iterates are returned as they are); "
+                                  "osqp.Problem polishes")
     return o
 
 
@@ -103,6 +118,7 @@ class _Solver:
                                        pd(self.D), pd(self.E), ctypes.byref(c), ctypes.byref(snz), ctypes.byref(h)), "kvx_admm_plan")
         self._h, self.c, self.snz = h, c.value, snz.value
         self.rho = None
+        self.last_res = None
 
     def pattern(self):
         Sp, Si = np.empty(self.n + 1, dtype=np.int64), np.empty(self.snz, dtype=np.int64)
@@ -126,6 +142,7 @@ class _Solver:
         """k iterations without a host synchronisation, then the 24 residual numbers of kvx_admm_iterate."""
         out = np.empty(24)
         _lib.raise_for(_lib.lib().kvx_admm_iterate(self._h, int(k), pd(out)), "kvx_admm_iterate")
+        self.last_res = out
         return out
 
     def set_rho(self, rho):
@@ -138,8 +155,40 @@ class _Solver:
         _lib.raise_for(_lib.lib().kvx_admm_state(self._h, pd(x), pd(z), pd(y), pd(dx), pd(dy)), "kvx_admm_state")
         return x, z, y, dx, dy
 
+    def update(self, q=None, l=None, u=None):
+        """New unscaled q, l, u (None: kept), rescaled on the device with the kept D, E, c."""
+        keep = [None if v is None else _lib.as_f64(v) for v in (q, l, u)]
+        rc = _lib.lib().kvx_admm_update(self._h, *(None if v is None else pd(v) for v in keep))
+        if rc == _lib.KVX_ENOTPOSDEF:
+            raise ArithmeticError(_lib.last_error() or "the problem is not convex")
+        _lib.raise_for(rc, "kvx_admm_update")
+
+    def warm_start(self, x=None, y=None):
+        """The state from unscaled x (then z = Ax) and y (None: kept); dx = dy = 0."""
+        keep = [None if v is None else _lib.as_f64(v) for v in (x, y)]
+        _lib.raise_for(_lib.lib().kvx_admm_warm_start(self._h, *(None if v is None else pd(v) for v in keep)), "kvx_admm_warm_start")
+
+    def cold_start(self):
+        _lib.raise_for(_lib.lib().kvx_admm_cold_start(self._h), "kvx_admm_cold_start")
+
+    def polish(self, delta=1e-6, refine_iter=3):
+        """The 16 numbers of kvx_admm_polish; out[0] = -1: S_pol did not factor."""
+        out = np.empty(16)
+        _lib.raise_for(_lib.lib().kvx_admm_polish(self._h, float(delta), int(refine_iter), pd(out)), "kvx_admm_polish")
+        return out
+
+    def polish_state(self):
+        """The scaled polished x, z, y and the flags -1 (active at l) / 0 / +1 (active at u)."""
+        x, z, y, act = np.empty(self.n), np.empty(self.m), np.empty(self.m), np.empty(self.m, dtype=np.int64)
+        _lib.raise_for(_lib.lib().kvx_admm_polish_state(self._h, pd(x), pd(z), pd(y), pi(act)), "kvx_admm_polish_state")
+        return x, z, y, act
+
+    def polish_accept(self):
+        _lib.raise_for(_lib.lib().kvx_admm_polish_accept(self._h), "kvx_admm_polish_accept")
+
     def solution(self, kind=0):
-        """kind 0: the unscaled (x, y); 1: the certificate of primal infeasibility as y; 2: of dual infeasibility as x."""
+        """kind 0: the unscaled (x, y); 1: the certificate of primal infeasibility as y; 2: of dual infeasibility as x; 3: the
+        polished (x, y)."""
         x, y = np.zeros(self.n), np.zeros(self.m)
         _lib.raise_for(_lib.lib().kvx_admm_solution(self._h, int(kind), pd(x) if kind != 1 else None, pd(y) if kind != 2 else None),
                        "kvx_admm_solution")
@@ -273,6 +322,102 @@ def solve(q, A, l, u, P=None, options=None, _stats=None):
     l = _vector(l, "l", m)
     Pcc = _lower(P, n, "incompatible dimensions") if P is not None else None
     return _solve(q, Acc, l, u, Pcc, options, _stats)
+
+
+def _polish_accepted(rp, rd, hp, hd):
+    """(rp, rd): the loop's last residuals, (hp, hd): the polished ones (a kept problem)."""
+    return (hp < rp and hd < rd) or (hp < rp and rd < 1e-10) or (hd < rd and rp < 1e-10)
+
+
+class Problem:
+    """minimize 0.5 x' P x + q' x  subject to  l <= A x <= u, kept on the device: planned, analysed and factored once.
+
+    The arguments, their checks and the option keys are those of solve(); here 'polish', 'delta', 'polish_refine_iter' and
+    'warm_start' take effect.  After every solve() `info` holds: status, iterations (of this solve), factorisations (so far),
+    rho, status_polish (1 accepted, -1 rejected or not factorable, 0 not run), pri_res / dua_res (the loop's last residuals in the
+    measure 'scaled_termination' selects), pri_res_polish / dua_res_polish (None when no polish factored), obj_val and
+    active_lower / active_upper (None when no polish ran)."""
+
+    def __init__(self, q, A, l, u, P=None, options=None):
+        Acc = _sparse_arg(A, "A", TypeError)
+        m, n = Acc[0], Acc[1]
+        if m <= 0:
+            raise ValueError("m must be a positive integer")
+        if n <= 0:
+            raise ValueError("n must be a positive integer")
+        q = _vector(q, "q", n)
+        u = _vector(u, "u", m)
+        l = _vector(l, "l", m)
+        Pcc = _lower(P, n, "incompatible dimensions") if P is not None else None
+        self._o = _read_options(options, 3)
+        self.info = None
+        self._S = None
+        _lib.require_device()
+        S = _Solver(q, Acc, l, u, Pcc, self._o["scaling"])
+        try:
+            S.setup(self._o["sigma"], self._o["rho"], self._o["alpha"])
+        except Exception:
+            S.close()
+            raise
+        self._S = S
+
+    def _solver(self):
+        if self._S is None:
+            raise ValueError("the problem is closed")
+        return self._S
+
+    def update(self, q=None, l=None, u=None):
+        """Replace q, l, u (None: kept).  The scaling is kept; a row that changes between equality, free and the other rows
+        costs one numeric refactorisation."""
+        S = self._solver()
+        S.update(None if q is None else _vector(q, "q", S.n), None if l is None else _vector(l, "l", S.m),
+                 None if u is None else _vector(u, "u", S.m))
+
+    def warm_start(self, x=None, y=None):
+        """The state the next solve() continues from: x (with z = Ax) and y (None: kept).  With 'warm_start' = 0 every solve()
+        starts from zero and this has no effect."""
+        S = self._solver()
+        S.warm_start(None if x is None else _vector(x, "x", S.n), None if y is None else _vector(y, "y", S.m))
+
+    def solve(self):
+        """(status, x, y) with the conventions of solve()."""
+        S, o = self._solver(), self._o
+        if not o["warm_start"]:
+            S.cold_start()
+        status, it = _run(S, o)
+        res = S.last_res
+        b = 0 if o["scaled_termination"] else 7
+        info = {"status": status, "iterations": it, "status_polish": 0, "pri_res": float(res[b]), "dua_res": float(res[b + 3]),
+                "pri_res_polish": None, "dua_res_polish": None, "obj_val": (0.5 * res[22] + res[23]) / S.c, "active_lower": None,
+                "active_upper": None}
+        kind = 0 if status.startswith("solved") else 1 if status.startswith("primal infeasible") else 2 if status.startswith("dual infeasible") else None
+        if o["polish"] and status == "solved":
+            out = S.polish(o["delta"], o["polish_refine_iter"])
+            info["active_lower"], info["active_upper"], info["status_polish"] = int(out[1]), int(out[2]), -1
+            if out[0] > 0:
+                hp, hd = (out[3], out[4]) if o["scaled_termination"] else (out[5], out[6])
+                info["pri_res_polish"], info["dua_res_polish"] = float(hp), float(hd)
+                if _polish_accepted(res[b], res[b + 3], hp, hd):
+                    S.polish_accept()
+                    info["status_polish"], info["obj_val"], kind = 1, (0.5 * out[7] + out[8]) / S.c, 3
+        x, y = S.solution(kind) if kind is not None else (np.zeros(S.n), np.zeros(S.m))
+        info["factorisations"], info["rho"] = S.info()["factorisations"], S.rho
+        self.info = info
+        if o["verbose"]:
+            print("status: %s, %d iterations, %d factorisations, polish: %s" % (status, it, info["factorisations"],
+                                                                              {1: "accepted", -1: "rejected", 0: "not run"}[info["status_polish"]]))
+        return status, x, y
+
+    def close(self):
+        if self._S is not None:
+            self._S.close()
+            self._S = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def resize_problem(G, h, A, b):
