@@ -10,6 +10,8 @@ import numpy as np
 from . import base
 
 _INT, _NUM = (int, np.integer), (float, int, np.floating, np.integer)
+EXPON = 3          # coneprog.py:423
+STEP = 0.99        # coneprog.py:424
 
 
 def options(user, dims, qp=False):
@@ -158,6 +160,16 @@ def f4(no_ir, res, nref, w, w2):
             for t, u in zip((bx, by, bz, bs), w2):
                 t.axpy(u)
     return f
+
+
+def relgap(gap, pcost, dcost):
+    """The relative gap of the reference's drivers (coneprog.py:898-903), None when neither objective has the sign it needs."""
+    return gap / -pcost if pcost < 0.0 else (gap / dcost if dcost > 0.0 else None)
+
+
+def step_length(t, i):
+    """The step of direction i (0: predictor, 1: corrector) from the distance t to the boundary (coneprog.py:1322-1328)."""
+    return 1.0 if t == 0.0 else (min(1.0, 1.0 / t) if i == 0 else min(1.0, STEP / t))
 
 
 def progress(iters, pcost, dcost, gap, pres, dres, kt=None):

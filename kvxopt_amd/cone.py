@@ -29,9 +29,6 @@ from .coneops import (Dims, WDev, compute_scaling as _compute_scaling, max_step,
 from .devvec import DVec, SpMatDev, SymSpMatDev
 from .lp import dense_schur
 
-EXPON = 3          # coneprog.py:423
-STEP = 0.99        # coneprog.py:424
-
 
 
 class ConePlan:
@@ -300,7 +297,7 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
         gap = sdot(D, s.ptr, z.ptr)
         pcost = cv.dot(x)
         dcost = -bv.dot(y) - sdot(D, hv.ptr, z.ptr)
-        relgap = gap / -pcost if pcost < 0.0 else (gap / dcost if dcost > 0.0 else None)
+        relgap = _ipm.relgap(gap, pcost, dcost)
         if ts <= 0 and tz <= 0 and (gap <= ABSTOL or (relgap is not None and relgap <= RELTOL)):
             tri(D, s.ptr, 0); tri(D, z.ptr, 0)
             rx = vec(n, c_h)
@@ -368,7 +365,7 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
         cx, by, hz = cv.dot(x), bv.dot(y), sdot(D, hv.ptr, z.ptr)
         rt = kappa + cx + by + hz
         pcost, dcost = cx / tau, -(by + hz) / tau
-        relgap = gap / -pcost if pcost < 0.0 else (gap / dcost if dcost > 0.0 else None)
+        relgap = _ipm.relgap(gap, pcost, dcost)
         pres = max(resy / resy0, resz / resz0)
         dres = resx / resx0
         pinfres = hresx / resx0 / (-hz - by) if hz + by < 0.0 else None
@@ -471,12 +468,9 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
             tt = -dtau[0] / lmbda_g
             tk = -dkappa[0] / lmbda_g
             t = max([0.0, ts, tz, tt, tk])
-            if t == 0.0:
-                step = 1.0
-            else:
-                step = min(1.0, 1.0 / t) if i == 0 else min(1.0, STEP / t)
+            step = _ipm.step_length(t, i)
             if i == 0:
-                sigma = (1.0 - step) ** EXPON
+                sigma = (1.0 - step) ** _ipm.EXPON
 
         # update (coneprog.py:1336-1436)
         x.axpy(dx, step)
@@ -635,7 +629,7 @@ def coneqp(P, q, G, h, dims, A=None, b=None, initvals=None, options=None, chol_o
         resz = snrm2(D, rz.ptr)
         pcost = f0
         dcost = f0 + (y.dot(ry) if p else 0.0) + sdot(D, z.ptr, rz.ptr) - gap
-        relgap = gap / -pcost if pcost < 0.0 else (gap / dcost if dcost > 0.0 else None)
+        relgap = _ipm.relgap(gap, pcost, dcost)
         pres = max(resy / resy0, resz / resz0)
         dres = resx / resx0
         if show:
@@ -686,12 +680,9 @@ def coneqp(P, q, G, h, dims, A=None, b=None, initvals=None, options=None, chol_o
             else:
                 ts, tz = max_step(D, ds.ptr, sigma=sigs), max_step(D, dz.ptr, sigma=sigz)
             t = max([0.0, ts, tz])
-            if t == 0:
-                step = 1.0
-            else:
-                step = min(1.0, 1.0 / t) if i == 0 else min(1.0, STEP / t)
+            step = _ipm.step_length(t, i)
             if i == 0:
-                sigma = min(1.0, max(0.0, 1.0 - step + dsdz / gap * step ** 2)) ** EXPON
+                sigma = min(1.0, max(0.0, 1.0 - step + dsdz / gap * step ** 2)) ** _ipm.EXPON
                 eta = 0.0
 
         # update (coneprog.py:2459-2547)

@@ -27,7 +27,7 @@ from .cone import KKTConeDev
 from .coneops import (Dims, WDev, compute_scaling, max_step, scale, scale2, sdot, sinv, sprod, ssqr, step_and_update_scaling)
 from .devvec import DVec, SpMatDev
 
-STEP, BETA, ALPHA, EXPON, MAX_RELAXED_ITERS = 0.99, 0.5, 0.01, 3, 8          # cvxprog.py:384-388
+BETA, ALPHA, MAX_RELAXED_ITERS = 0.5, 0.01, 8          # cvxprog.py:384-388
 RANK_MSG = "Rank(A) < p or Rank([H(x); A; Df(x); G]) < n"
 
 
@@ -390,7 +390,7 @@ def _cpl(c_h, ev, ml, G, h_h, p, A, b_h, opt):
         reszl = math.sqrt(_dot(ml, lo(rz).ptr, lo(rz).ptr))
         pcost = cv.dot(x)
         dcost = pcost + (y.dot(ry) if p else 0.0) + _dot(mnl, z.ptr, rz.ptr) + _dot(ml, lo(z).ptr, lo(rz).ptr) - gap
-        relgap = gap / -pcost if pcost < 0.0 else (gap / dcost if dcost > 0.0 else None)
+        relgap = _ipm.relgap(gap, pcost, dcost)
         pres = math.sqrt(resy ** 2 + resznl ** 2 + reszl ** 2)
         dres = resx
         if iters == 0:
@@ -465,7 +465,7 @@ def _cpl(c_h, ev, ml, G, h_h, p, A, b_h, opt):
             scale2(D, lmbda.ptr, dz.ptr)
             tz = max_step(D, dz.ptr)
             t = max([0.0, ts, tz])
-            step = 1.0 if t == 0 else min(1.0, STEP / t)
+            step = _ipm.step_length(t, 1)
 
             while True:                                               # backtrack until newx is in the domain of f
                 newx.copy_from(x).axpy(dx, step)
@@ -503,7 +503,7 @@ def _cpl(c_h, ev, ml, G, h_h, p, A, b_h, opt):
                     if newgap <= (1.0 - ALPHA * step) * gap and (0 <= relaxed_iters < MAX_RELAXED_ITERS or
                                                                    newphi <= phi + ALPHA * step * dphi):
                         backtrack = False
-                        sigma = min(newgap / gap, (newgap / gap) ** EXPON)
+                        sigma = min(newgap / gap, (newgap / gap) ** _ipm.EXPON)
                         eta = 0.0
                     else:
                         step *= BETA

@@ -1,17 +1,20 @@
-"""Device-resident cone-LP interior-point driver for the orthant cone (inequality form, p = 0):
+"""Device-resident cone-LP and cone-QP interior-point drivers for the orthant cone:
 
-    minimize c'x  subject to  G x + s = h,  s >= 0          (G sparse, ml x n)
+    minimize c'x [+ (1/2) x'Px]  subject to  G x + s = h,  A x = b,  s >= 0          (G sparse, ml x n; A sparse, p x n, p >= 0)
 
-A restatement of the reference's `coneprog.conelp` (src/python/coneprog.py:31-1436) specialised to
-dims = {'l': ml, 'q': [], 's': []} and no equality constraints, with the default KKT solver
-`misc.kkt_chol2` (src/python/misc.py:1352-1567).  Every vector lives in HBM for the whole solve; per
-iteration the host sees only scalars (gap, residual norms, step lengths).  Per iteration, as in the
-reference: 1 numeric refactorisation of S = G' diag(di^2) G on a fixed symbolic analysis,
-3 KKT solves, 2 products with G and 2 with G', the NT-scaling update -- all HIP kernels of
-libkvxhip.so.  No CPU fallback.
+A restatement of the reference's `coneprog.conelp` / `coneqp` (src/python/coneprog.py:31-2547) specialised to dims = {'l': ml, 'q': [],
+'s': []}, with the default KKT solver `misc.kkt_chol2` (src/python/misc.py:1352-1567) or a caller's `kktsolver`.  Every vector lives in
+HBM for the whole solve; per iteration the host sees only scalars (gap, residual norms, step lengths).  Per iteration, as in the
+reference: 1 numeric refactorisation of S = G' diag(di^2) G on a fixed symbolic analysis, 3 KKT solves, 2 products with G
+and 2 with G', the NT-scaling update -- all HIP kernels of libkvxhip.so.  No CPU fallback.  KKT objects: KKTChol2Dev (p = 0), KKTDiagEqDev
+(p > 0, diagonal S, sparse K = A S^{-1} A' on a fixed pattern), KKTGenEqDev (p > 0, general S, dense K in HBM); `misc.kkt_chol2` is built
+on the same classes.
 
-Equality constraints (p > 0, K = A S^{-1} A') are device-resident too: KKTDiagEqDev (diagonal S, sparse K on a fixed
-pattern) and KKTGenEqDev (general S, dense K in HBM, any p).  `kvxopt_amd.misc.kkt_chol2` is built on the same classes.
+conelp's loop is written once, on host scalars (`_iterate`); the launches of an iteration belong to one of four engines, all with the
+same arithmetic and roundings (tests/test_kkt_gpu.py compares them bit for bit): `_CIssued`, the default for p = 0 (fused kernels, an
+iteration in four C calls); `_PythonIssued`, KVX_LP_PYCALLS=1 (the same launches, one ctypes call each); `_PerOperation`, KVX_LP_UNFUSED=1,
+p > 0 or a user's kktsolver (one launch per BLAS-1-sized operation); `_Refined`, options['refinement'] > 0 (iterative refinement of
+the Newton systems).  tests/test_lp_loop_cpu.py runs the loop on a numpy engine.
 """
 import collections
 import ctypes
@@ -27,15 +30,9 @@ from ._lib import DeviceBuffer, lib, raise_for
 from .chol import Factor
 from .devvec import DVec, SpMatDev, SymSpMatDev, reduce_multi      # noqa: F401  (lp.DVec, lp.SpMatDev, ... are public names)
 
-_lower_ccs = base.lower_ccs
-EXPON = 3          # coneprog.py:423
-STEP = 0.99        # coneprog.py:424
-# KVX_LP_UNFUSED=1: one launch per BLAS-1-sized operation, as in rounds 1-2 (the library reads the same variable); the fused launches
-# of round 3 do the same arithmetic with the same roundings -- tests/test_kkt_gpu.py compares the two bit for bit
+# the schedule of conelp's iteration (module docstring); the library reads KVX_LP_UNFUSED too
 _UNFUSED = os.environ.get("KVX_LP_UNFUSED", "0") not in ("", "0")
 _TRACE = os.environ.get("KVX_LP_TRACE", "0") not in ("", "0")      # per-iteration wall times of conelp on stderr
-# KVX_LP_PYCALLS=1: the fused launches of an iteration issued one by one from Python (round 3) instead of through the four calls
-# kvx_lp_iter_* (round 4: same kernels, same order, issued from C)
 _PYCALLS = os.environ.get("KVX_LP_PYCALLS", "0") not in ("", "0")
 
 
@@ -571,156 +568,386 @@ def _kkt_for(kind, dims_key, patterns, chol_opts, build, refresh):
     return kkt
 
 
-def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, primalstart=None, dualstart=None, kktsolver=None):
-    """Solve the LP  minimize c'x  s.t.  Gx <= h, Ax = b  on the GPU.  c: (n,), h: (ml,), G: spmatrix-like
-    (ml x n, sparse); A (p x n, sparse), b (p,) optional -- with equality constraints either G has at most one entry per
-    row (standard form: KKTDiagEqDev, sparse K on a fixed pattern) or any other sparse G (KKTGenEqDev, dense K in HBM).  primalstart = {'x', 's'},
-    dualstart = {'y', 'z'} (y optional) as in the reference (coneprog.py:683-737): s and z must be strictly positive.  Returns the reference's result dictionary (coneprog.py:962-974) with numpy arrays."""
-    opt = _ipm.options(options, {})
-    MAXITERS, ABSTOL, RELTOL, FEASTOL, REFINEMENT, show = opt.maxiters, opt.abstol, opt.reltol, opt.feastol, opt.refinement, opt.show
-    pb = _ipm.problem(c, G, h, None, A, b)
-    n, p, ml, c_h, h_h, b_h = pb.n, pb.p, pb.cdim, pb.c, pb.h, pb.b
-    (Gp, Gi, Gx), (Ap, Ai, Ax) = pb.G, pb.A
-    if dims is not None and (dims.get("q") or dims.get("s") or dims.get("l", ml) != ml):
-        raise NotImplementedError("only the orthant cone dims = {'l': G.size[0], 'q': [], 's': []} runs on the GPU")
-    _lib.require_device()
-    _NoY = _ipm.NoVec                                                # p = 0: the y-blocks of the algorithm are empty
+# what the interior-point loop returns: stats = (gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres)
+Outcome = collections.namedtuple("Outcome", "status iterations stats msg phase_seconds")
 
-    if kktsolver is not None:
-        # the reference's plug-in point (coneprog.py:323-344): kktsolver(W) returns f(x, y, z); host round trips per call
-        if not callable(kktsolver):
-            raise ValueError("kktsolver must be a function W -> f(x, y, z) (the reference's named solvers 'ldl', 'ldl2', 'qr', "
-                             "'chol', 'chol2' are not part of this path: 'chol2' is what runs on the GPU by default)")
-        kkt = KKTUserHost(ml, n, Gp, Gi, Gx, p, Ap, Ai, Ax, kktsolver)
-        fused = False
-        kfactor_solve2 = None
-        ksolve = kkt.solve
-        def ksolve2(xa, ya, za, xb, yb, zb):
-            kkt.solve(xa, ya, za)
-            kkt.solve(xb, yb, zb)
-    elif p > 0:
-        Gi64 = np.asarray(Gi, dtype=np.int64)
-        diag_s = not (Gi64.size and np.bincount(Gi64, minlength=ml).max() > 1)
-        cls = KKTDiagEqDev if diag_s else KKTGenEqDev
-        kkt = _kkt_for(cls.__name__, (ml, n, p), (Gp, Gi, Ap, Ai), chol_opts,
-                       lambda: cls(ml, n, Gp, Gi, Gx, p, Ap, Ai, Ax, chol_opts), lambda k: k.reset(Gx, Ax))
-        ksolve = kkt.solve
-        ksolve2 = kkt.solve2
-        kfactor_solve2 = None
-        fused = False
-    else:
-        kkt = _kkt_for("KKTChol2Dev", (ml, n, 0), (Gp, Gi), chol_opts,
-                       lambda: KKTChol2Dev(ml, n, Gp, Gi, Gx, chol_opts), lambda k: k.reset(Gx))
-        def ksolve(xx, yy, zz):
-            kkt.solve(xx, zz)
-        def ksolve2(xa, ya, za, xb, yb, zb):
-            kkt.solve2(xa, za, xb, zb)
-        def kfactor_solve2(dd, xa, ya, za, xb, yb, zb):
-            kkt.factor_solve2(dd, xa, za, xb, zb)
-        fused = not _UNFUSED and REFINEMENT == 0         # p = 0: the short launches of an iteration fused (kkt.hip, "round 3")
-    if p > 0:
-        bv = DVec(p, b_h)
-        y, dy, y1, ry, hry = (DVec(p) for _ in range(5))
-    else:
-        bv = y = dy = y1 = ry = hry = _NoY()
-    _, Af = _ipm.operators(kkt.G, kkt.A if p else None)
-    Gd = kkt.G
-    cv, hv = DVec(n, c_h), DVec(ml, h_h)
-    x, dx, x1, rx, hrx = (DVec(n) for _ in range(5))
-    s, z, ds, dz, z1, rz, hrz, th, ws3, tmp, lmbda, lmbdasq, d, di = (DVec(ml) for _ in range(14))
 
-    resx0 = max(1.0, cv.nrm2())
-    resy0 = max(1.0, bv.nrm2())
-    resz0 = max(1.0, hv.nrm2())
+def _iterate(engine, opt, ml, gap, res0):
+    """The interior-point loop of conelp on the orthant (coneprog.py:859-1436) from a starting point with tau = kappa = 1 and
+    s'z = gap; res0 = (resx0, resy0, resz0).  Host scalars only: the vectors belong to `engine`, which is asked for
+      stats(tau)        the squared norms of hrx, rx, hry, ry, hrz, rz, then c'x, b'y, h'z and lmbda'lmbda
+      scaling()         the NT scaling of the first iteration; returns lmbda'lmbda
+      direction(i, ...) whatever of direction i (0: predictor, with the factorisation and the constant system; 1: corrector)
+                        can report a failed factorisation, by ArithmeticError
+      bounds(i)         the rest of direction i; returns (dtau, dkappa, max_step(ds), max_step(dz))
+      update(step, tau) the step, the new scaling, and s, z of the next iteration; tau is the new one
+      scale(a, b)       x, s *= a and y, z *= b (None: left alone)
+    and returns an Outcome; the iterates are left scaled as the reference returns them."""
+    resx0, resy0, resz0 = res0
+    tau, kappa = 1.0, 1.0
+    dg = dgi = lmbda_g = 1.0
+    phase = [0.0, 0.0, 0.0]
+    for iters in range(opt.maxiters + 1):
+        # residuals (coneprog.py:861-896): their norms and the objectives
+        v_hrx, v_rx, v_hry, v_ry, v_hrz, v_rz, cx, by, hz, lam2 = engine.stats(tau)
+        t_now = time.perf_counter()
+        if iters > 0:
+            phase[2] += t_now - t_mark
+        t_mark = t_now
+        hresx, resx = math.sqrt(v_hrx), math.sqrt(v_rx) / tau
+        hresy, resy = math.sqrt(v_hry), math.sqrt(v_ry) / tau
+        hresz, resz = math.sqrt(v_hrz), math.sqrt(v_rz) / tau
+        if iters > 0:
+            gap = (math.sqrt(lam2) / tau) ** 2           # (coneprog.py:1436; lmbda of the previous update)
+        rt = kappa + cx + by + hz
+        pcost, dcost = cx / tau, -(by + hz) / tau
+        relgap = _ipm.relgap(gap, pcost, dcost)
+        pres = max(resy / resy0, resz / resz0)
+        dres = resx / resx0
+        pinfres = hresx / resx0 / (-hz - by) if hz + by < 0.0 else None
+        dinfres = max(hresy / resy0, hresz / resz0) / (-cx) if cx < 0.0 else None
+        if opt.show:
+            _ipm.progress(iters, pcost, dcost, gap, pres, dres, kappa / tau)
 
-    t_loop = [None]
-    t_phase = [0.0, 0.0, 0.0]
-    t_mark = [0.0]
-    fast = fused and not _PYCALLS and isinstance(kkt, KKTChol2Dev) and kkt.Px is None
-    if fast:
-        ctx = _lib.LpCtx(ml, n, Gd.cp.ptr, Gd.ri.ptr, Gd.vx.ptr, Gd.max_col, Gd.tcp.ptr, Gd.tri.ptr, Gd.tvx.ptr, Gd.max_row,
-                         kkt._plan, kkt.fac._h, kkt.Sx.ptr, kkt._x2buf().ptr, x.ptr, s.ptr, z.ptr, cv.ptr, hv.ptr, hrx.ptr, rx.ptr,
-                         hrz.ptr, rz.ptr, lmbda.ptr, d.ptr, di.ptr, ds.ptr, dz.ptr, dx.ptr, x1.ptr, z1.ptr, th.ptr, ws3.ptr)
-        out10 = (ctypes.c_double * 10)()
-    next_stats = None                                    # the residual statistics of the coming iteration, when the update has made them
+        if (pres <= opt.feastol and dres <= opt.feastol and (gap <= opt.abstol or (relgap is not None and relgap <= opt.reltol))) \
+                or iters == opt.maxiters:
+            engine.scale(1.0 / tau, 1.0 / tau)
+            if iters == opt.maxiters:
+                return Outcome("unknown", iters, (gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres), _ipm.MAXITERS_MSG, phase)
+            return Outcome("optimal", iters, (gap, relgap, pcost, dcost, pres, dres, None, None), None, phase)
+        elif pinfres is not None and pinfres <= opt.feastol:
+            engine.scale(None, 1.0 / (-hz - by))
+            return Outcome("primal infeasible", iters, (None, None, None, 1.0, None, None, pinfres, None), None, phase)
+        elif dinfres is not None and dinfres <= opt.feastol:
+            engine.scale(1.0 / (-cx), None)
+            return Outcome("dual infeasible", iters, (None, None, -1.0, None, None, None, None, dinfres), None, phase)
 
-    if REFINEMENT:
-        # iterative refinement of the Newton systems (coneprog.py:599-631 res(), :1110-1195 f6_no_ir, :1211-1235 f6), operation by
-        # operation on the device vectors; scalars (tau, kappa blocks) travel in one-element lists.  For the orthant cone
-        # W = diag(d): scale(., W, inverse='I') multiplies by di, scale(., W, trans='T') by d.
-        wx, wx2 = DVec(n), DVec(n)
-        wy, wy2 = (DVec(p), DVec(p)) if p else (_NoY(), _NoY())
-        wz, ws, wz2, ws2, rs3, rz3 = (DVec(ml) for _ in range(6))
+        # NT scaling at the first iteration (coneprog.py:1031-1043 -> misc.py:284-287)
+        if iters == 0:
+            lam2 = engine.scaling()
+            dg = math.sqrt(kappa / tau)
+            dgi = math.sqrt(tau / kappa)
+            lmbda_g = math.sqrt(tau * kappa)
+        mu = (lam2 + lmbda_g ** 2) / (1 + ml)
+        sigma = wkappa3 = 0.0
+        for i in (0, 1):
+            try:
+                engine.direction(i, sigma, mu, rt, dgi, lmbda_g, wkappa3)
+            except ArithmeticError:
+                engine.scale(1.0 / tau, 1.0 / tau)
+                return Outcome("unknown", iters, (gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres), _ipm.SINGULAR_MSG, phase)
+            dtau, dkappa, ts, tz = engine.bounds(i)
+            t_now = time.perf_counter()
+            phase[i] += t_now - t_mark
+            if _TRACE:
+                print("conelp iteration %d direction %d: %.0f us" % (iters, i, 1e6 * (t_now - t_mark)), file=sys.stderr)
+            t_mark = t_now
+            if i == 0:
+                wkappa3 = dtau * dkappa
+            # step to the boundary (coneprog.py:1314-1331)
+            tt, tk = -dtau / lmbda_g, -dkappa / lmbda_g
+            step = _ipm.step_length(max(0.0, ts, tz, tt, tk), i)
+            if i == 0:
+                sigma = (1.0 - step) ** _ipm.EXPON
 
-        def f6_no_ir_g(sc, bx, by, bz, btau, bs, bkappa):
-            by.scal(-1.0)
-            bs.div(lmbda).scal(-1.0)                     # s := -lmbda o\ bs
-            rs3.copy_from(bs).mul(d)
-            bz.axpy(rs3).scal(-1.0)                      # z := -(bz + W' s)
-            ksolve(bx, by, bz)
-            bkappa[0] = -bkappa[0] / sc["lmbda_g"]
-            btau[0] += bkappa[0] / sc["dgi"]
-            btau[0] = sc["dgi"] * (btau[0] + cv.dot(bx) + bv.dot(by) + th.dot(bz)) / (1.0 + z1.dot(z1))
-            bx.axpy(x1, btau[0]); by.axpy(y1, btau[0]); bz.axpy(z1, btau[0])
-            bs.axpy(bz, -1.0)
-            bkappa[0] -= btau[0]
+        # update (coneprog.py:1336-1436)
+        dg *= math.sqrt(1.0 - step * tk) / math.sqrt(1.0 - step * tt)
+        dgi = 1.0 / dg
+        lmbda_g *= math.sqrt(1.0 - step * tt) * math.sqrt(1.0 - step * tk)
+        kappa, tau = lmbda_g / dgi, lmbda_g * dgi
+        engine.update(step, tau)
+    raise AssertionError("unreachable")
 
-        def res_g(sc, ux, uy, uz, utau, us, ukappa, vx, vy, vz, vtau, vs, vkappa):
-            dg_ = 1.0 / sc["dgi"]
-            Af(uy, vx, trans="T", alpha=-1.0, beta=1.0)
-            rz3.copy_from(uz).mul(di)                    # W^{-1} uz
-            Gd.gemv(rz3, vx, trans="T", alpha=-1.0, beta=1.0)
-            vx.axpy(cv, -utau[0] / dg_)
-            Af(ux, vy, trans="N", alpha=1.0, beta=1.0)
-            vy.axpy(bv, -utau[0] / dg_)
-            Gd.gemv(ux, vz, trans="N", alpha=1.0, beta=1.0)
-            vz.axpy(hv, -utau[0] / dg_)
-            rs3.copy_from(us).mul(d)
-            vz.axpy(rs3)
-            vtau[0] += dg_ * ukappa[0] + cv.dot(ux) + bv.dot(uy) + hv.dot(rz3)
-            rs3.copy_from(us).axpy(uz).mul(lmbda)
-            vs.axpy(rs3)
-            vkappa[0] += sc["lmbda_g"] * (utau[0] + ukappa[0])
 
-        def f6_g(sc, *rhs):
-            _ipm.f6(lambda *a: f6_no_ir_g(sc, *a), lambda *a: res_g(sc, *a), REFINEMENT, (wx, wy, wz, ws), (wx2, wy2, wz2, ws2))(*rhs)
+class _Engine:
+    """The device vectors of one conelp run and what the schedules below have in common.  Each schedule is one subclass, to be read
+    top to bottom as its launch order; all four do the same arithmetic with the same roundings."""
 
-    def result(status, iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, xs=True, zs=True, msg=None):
-        return _ipm.conelp_result(
-            show, status, x.get() if xs else None, y.get() if zs else None, s.get() if xs else None, z.get() if zs else None,
-            (gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres), s.max_step() if xs else None, z.max_step() if zs else None,
-            iters, kkt.nfactor, msg, **{
-                # wall time of the interior-point loop proper (coneprog.py:859-1436), i.e. without the symbolic
-                # analysis and the starting point; not a key of the reference's dictionary
-                "loop seconds": (time.perf_counter() - t_loop[0]) if t_loop[0] is not None else 0.0,
-                # the same, split at the three host synchronisations of an iteration: [residual norms -> first direction
-                # (assembly, factorisation, two solves), -> second direction (one solve), -> update + residuals of the next]
-                "phase seconds": list(t_phase)})
+    def __init__(self, kkt, pb):
+        ml, n, p = pb.cdim, pb.n, pb.p
+        self.kkt, self.ml, self.n, self.p = kkt, ml, n, p
+        self.xz = isinstance(kkt, KKTChol2Dev)           # p = 0 on the device: its solves take (x, z)
+        self.G = kkt.G
+        self.Af = _ipm.operators(kkt.G, kkt.A if p else None)[1]
+        self.cv, self.hv = DVec(n, pb.c), DVec(ml, pb.h)
+        self.x, self.dx, self.x1, self.rx, self.hrx = (DVec(n) for _ in range(5))
+        self.bv = DVec(p, pb.b) if p else _ipm.NoVec()   # p = 0: the y-blocks of the algorithm are empty
+        self.y, self.dy, self.y1, self.ry, self.hry = (DVec(p) for _ in range(5)) if p else [self.bv] * 5
+        self.s, self.z, self.ds, self.dz, self.z1, self.rz, self.hrz, self.th, self.ws3, self.lmbda = (DVec(ml) for _ in range(10))
+        self.d, self.di = DVec(ml), DVec(ml)
+        self.out4 = (ctypes.c_double * 4)()              # dtau, z1'z1, max_step(ds), max_step(dz) of the last direction
 
-    # ---- starting point (coneprog.py:662-822): factor with W = I ------------------------------------
-    d.fill(1.0); di.fill(1.0)
+    def ksolve(self, x, y, z):
+        self.kkt.solve(*((x, z) if self.xz else (x, y, z)))
+
+    def reduce(self):
+        e = self
+        return reduce_multi([("dot", e.hrx, e.hrx), ("dot", e.rx, e.rx), ("dot", e.hry, e.hry), ("dot", e.ry, e.ry), ("dot", e.hrz, e.hrz),
+                             ("dot", e.rz, e.rz), ("dot", e.cv, e.x), ("dot", e.bv, e.y), ("dot", e.hv, e.z), ("dot", e.lmbda, e.lmbda)])
+
+    def scaling(self):
+        raise_for(lib().kvx_nt_compute_scaling_dev(self.ml, self.s.ptr, self.z.ptr, self.d.ptr, self.di.ptr, self.lmbda.ptr))
+        return self.lmbda.dot(self.lmbda)
+
+    def scale(self, primal, dual):
+        if primal is not None:
+            self.x.scal(primal); self.s.scal(primal)
+        if dual is not None:
+            self.y.scal(dual); self.z.scal(dual)
+
+    def begin(self, i, sigma, mu, rt, dgi, lmbda_g, wkappa3):
+        """The tau and kappa entries of the right-hand side of direction i (coneprog.py:1250-1298), the same after the first half of
+        f6_no_ir (:1130-1160), and the scalars its launches take."""
+        self.sigma, self.smu, self.dgi, self.lmbda_g = sigma, (sigma * mu if i == 1 else 0.0), dgi, lmbda_g
+        self.rtau = (1.0 - sigma) * rt
+        self.rkappa = lmbda_g ** 2
+        if i == 1:
+            self.rkappa += wkappa3 - sigma * mu
+        self.dkappa = -self.rkappa / lmbda_g
+        self.dtau0 = self.rtau + self.dkappa / dgi
+
+    def newton_rhs(self, i, lmbdasq):
+        """ds := -(lmbdasq (+ ws3 - sigma mu)) o\\ lmbda,  dz := -((1 - sigma) rz + W' ds): one kernel; lmbdasq None: formed inside."""
+        raise_for(lib().kvx_lp_newton_rhs_dev(self.ml, lmbdasq, self.ws3.ptr if i == 1 else None, self.smu, 1.0 - self.sigma,
+                                              self.rz.ptr, self.lmbda.ptr, self.d.ptr, self.ds.ptr, self.dz.ptr))
+
+    def second_half(self, i):
+        """Second half of f6_no_ir (coneprog.py:1162-1195), dz += dtau z1, ds -= dz, [ws3 := ds o dz (:1303-1306)], the scaling by lmbda and
+        the step bounds (:1314-1321): dtau is formed on the device from the inner products, ONE host round trip per direction."""
+        e, p = self, self.p
+        raise_for(lib().kvx_lp_second_half_dev(e.ml, e.n, p, e.cv.ptr, e.bv.ptr if p else None, e.th.ptr, e.x1.ptr, e.y1.ptr if p else None,
+                                               e.z1.ptr, e.lmbda.ptr, e.dx.ptr, e.dy.ptr if p else None, e.dz.ptr, e.ds.ptr,
+                                               e.ws3.ptr if i == 0 else None, e.dgi, e.dtau0, -1.0 if i == 0 else e.out4[1], e.out4))
+
+    def bounds(self, i):
+        dtau, _, ts, tz = self.out4                      # (z1'z1 comes with the first direction and is handed to the second)
+        return dtau, self.dkappa - dtau, ts, tz
+
+
+class _CIssued(_Engine):
+    """p = 0, the default: the fused launches of an iteration issued from C in four calls (kvx_lp_iter_*) -- a direction up to its
+    scalars is ONE call: what newton_rhs, factor_solve_sides / solve_sides, th.xmy and second_half enqueue in _PythonIssued, in that order."""
+
+    def __init__(self, kkt, pb):
+        super().__init__(kkt, pb)
+        e, G = self, self.G
+        self.ctx = _lib.LpCtx(e.ml, e.n, G.cp.ptr, G.ri.ptr, G.vx.ptr, G.max_col, G.tcp.ptr, G.tri.ptr, G.tvx.ptr, G.max_row,
+                              kkt._plan, kkt.fac._h, kkt.Sx.ptr, kkt._x2buf().ptr, e.x.ptr, e.s.ptr, e.z.ptr, e.cv.ptr, e.hv.ptr, e.hrx.ptr,
+                              e.rx.ptr, e.hrz.ptr, e.rz.ptr, e.lmbda.ptr, e.d.ptr, e.di.ptr, e.ds.ptr, e.dz.ptr, e.dx.ptr, e.x1.ptr, e.z1.ptr,
+                              e.th.ptr, e.ws3.ptr)
+        self.out10 = (ctypes.c_double * 10)()
+        self.fresh = False                               # out10 holds the statistics of the coming iteration
+
+    def stats(self, tau):
+        if not self.fresh:
+            raise_for(lib().kvx_lp_iter_residuals(ctypes.byref(self.ctx), tau, self.out10))
+        self.fresh = False
+        return tuple(self.out10)
+
+    def direction(self, i, *scalars):
+        self.begin(i, *scalars)
+        if i == 0:
+            self.kkt.di = self.di
+            self.kkt.nfactor += 1
+            raise_for(lib().kvx_lp_iter_predictor(ctypes.byref(self.ctx), self.dgi, self.dtau0, self.out4))
+        else:
+            self.kkt.check()                             # the stream is idle by now: no extra wait
+            raise_for(lib().kvx_lp_iter_corrector(ctypes.byref(self.ctx), self.smu, 1.0 - self.sigma, self.dgi, self.dtau0, self.out4[1], self.out4))
+
+    def update(self, step, tau):
+        # the update, the residuals of the next iteration (with the new tau) and their reductions in ONE call
+        raise_for(lib().kvx_lp_iter_update(ctypes.byref(self.ctx), step, tau, self.out10))
+        self.fresh = True
+
+
+class _PythonIssued(_Engine):
+    """p = 0, KVX_LP_PYCALLS=1: the same fused launches, one ctypes call each."""
+
+    def stats(self, tau):
+        e, G = self, self.G
+        raise_for(lib().kvx_lp_residuals_dev(e.ml, e.n, G.cp.ptr, G.ri.ptr, G.vx.ptr, G.max_col, G.tcp.ptr, G.tri.ptr, G.tvx.ptr, G.max_row,
+                                             e.x.ptr, e.z.ptr, e.s.ptr, e.cv.ptr, e.hv.ptr, tau, e.hrx.ptr, e.rx.ptr, e.hrz.ptr, e.rz.ptr))
+        return self.reduce()
+
+    def direction(self, i, *scalars):
+        e = self
+        e.begin(i, *scalars)
+        if i == 1:
+            return e.kkt.check()                         # the stream is idle by now: no extra wait
+        e.kkt.async_solves = True                        # enqueue only: the host runs ahead of the GPU up to the next scalar
+        e.newton_rhs(0, None)
+        # factorisation and both solves in one enqueue; x1 := -c, z1 := h, their scaling by dgi and dx := (1 - sigma) rx inside its launches
+        e.kkt.factor_solve_sides(e.di, [(e.cv, -1.0, e.hv, e.x1, e.dgi, e.z1, e.dgi), (e.rx, 1.0 - e.sigma, e.dz, e.dx, 1.0, e.dz, 1.0)])
+        e.th.xmy(1.0, e.hv, e.di)
+
+    def bounds(self, i):
+        e = self
+        if i == 1:
+            e.newton_rhs(1, None)
+            e.kkt.solve_sides([(e.rx, 1.0 - e.sigma, e.dz, e.dx, 1.0, e.dz, 1.0)])
+        e.second_half(i)
+        return super().bounds(i)
+
+    def update(self, step, tau):
+        e = self
+        raise_for(lib().kvx_lp_update_x_dev(e.ml, e.n, step, e.ds.ptr, e.dz.ptr, e.d.ptr, e.di.ptr, e.lmbda.ptr, e.s.ptr, e.z.ptr, e.dx.ptr, e.x.ptr))
+
+
+class _PerOperation(_Engine):
+    """KVX_LP_UNFUSED=1, equality constraints or a user's kktsolver: one launch per operation."""
+
+    def stats(self, tau):
+        e = self
+        e.Af(e.y, e.hrx, trans="T", alpha=-1.0, beta=0.0)
+        e.G.gemv(e.z, e.hrx, trans="T", alpha=-1.0, beta=1.0)
+        e.rx.lincomb(1.0, e.hrx, -tau, e.cv)
+        e.Af(e.x, e.hry, trans="N")
+        e.ry.lincomb(1.0, e.hry, -tau, e.bv)
+        e.G.gemv(e.x, e.hrz, trans="N"); e.hrz.axpy(e.s)
+        e.rz.lincomb(1.0, e.hrz, -tau, e.hv)
+        return e.reduce()
+
+    def scaling(self):
+        lam2 = super().scaling()
+        self.lmbdasq = DVec(self.ml).sqr_of(self.lmbda)  # lmbda o lmbda, renewed with lmbda
+        return lam2
+
+    def rhs(self, i):
+        self.newton_rhs(i, self.lmbdasq.ptr)
+        self.dx.lincomb(1.0 - self.sigma, self.rx)
+        self.dy.lincomb(-(1.0 - self.sigma), self.ry)
+
+    def direction(self, i, *scalars):
+        e, kkt = self, self.kkt
+        e.begin(i, *scalars)
+        if i == 1:
+            return kkt.check()                           # the stream is idle by now: no extra wait
+        # factor + the two solves that do not depend on each other (coneprog.py:1066-1077 and the predictor's f3)
+        kkt.async_solves = True                          # enqueue only: the host runs ahead of the GPU up to the next scalar
+        if not e.xz:
+            kkt.factor(e.di, sync=False)                 # a failed factorisation surfaces in the solve right below
+        e.x1.lincomb(-1.0, e.cv); e.y1.copy_from(e.bv); e.z1.copy_from(e.hv)
+        e.rhs(0)
+        if e.xz:                                         # with the factorisation in one enqueue: the right-hand sides do not depend on it
+            kkt.factor_solve2(e.di, e.x1, e.z1, e.dx, e.dz)
+        elif isinstance(kkt, KKTUserHost):
+            kkt.solve(e.x1, e.y1, e.z1)
+            kkt.solve(e.dx, e.dy, e.dz)
+        else:                                            # one two-column triangular solve with the new factor
+            kkt.solve2(e.x1, e.y1, e.z1, e.dx, e.dy, e.dz)
+        e.x1.scal(e.dgi); e.y1.scal(e.dgi); e.z1.scal(e.dgi)
+        e.th.copy_from(e.hv).mul(e.di)                   # th = W^{-T} h      (coneprog.py:1126-1128)
+
+    def bounds(self, i):
+        if i == 1:
+            self.rhs(1)
+            self.ksolve(self.dx, self.dy, self.dz)
+        self.second_half(i)
+        return super().bounds(i)
+
+    def update(self, step, tau):
+        e = self
+        e.x.axpy(e.dx, step)
+        e.y.axpy(e.dy, step)
+        raise_for(lib().kvx_lp_update_dev(e.ml, step, e.ds.ptr, e.dz.ptr, e.d.ptr, e.di.ptr, e.lmbda.ptr, e.s.ptr, e.z.ptr))
+        e.lmbdasq.sqr_of(e.lmbda)
+
+
+class _Refined(_PerOperation):
+    """options['refinement'] > 0: the Newton systems with iterative refinement (coneprog.py:599-631 res(), :1110-1195 f6_no_ir,
+    :1211-1235 f6), operation by operation; the scalars (tau, kappa blocks) travel in one-element lists.  For the orthant cone
+    W = diag(d): scale(., W, inverse='I') multiplies by di, scale(., W, trans='T') by d."""
+
+    def __init__(self, kkt, pb, nref):
+        super().__init__(kkt, pb)
+        self.rs3, self.rz3 = DVec(self.ml), DVec(self.ml)
+        w, w2 = ((DVec(self.n), DVec(self.p) if self.p else self.y, DVec(self.ml), DVec(self.ml)) for _ in range(2))
+        self.f6 = _ipm.f6(self.f6_no_ir, self.res, nref, w, w2)
+
+    def f6_no_ir(self, bx, by, bz, btau, bs, bkappa):
+        e = self
+        by.scal(-1.0)
+        bs.div(e.lmbda).scal(-1.0)                       # s := -lmbda o\ bs
+        e.rs3.copy_from(bs).mul(e.d)
+        bz.axpy(e.rs3).scal(-1.0)                        # z := -(bz + W' s)
+        e.ksolve(bx, by, bz)
+        bkappa[0] = -bkappa[0] / e.lmbda_g
+        btau[0] += bkappa[0] / e.dgi
+        btau[0] = e.dgi * (btau[0] + e.cv.dot(bx) + e.bv.dot(by) + e.th.dot(bz)) / (1.0 + e.z1.dot(e.z1))
+        bx.axpy(e.x1, btau[0]); by.axpy(e.y1, btau[0]); bz.axpy(e.z1, btau[0])
+        bs.axpy(bz, -1.0)
+        bkappa[0] -= btau[0]
+
+    def res(self, ux, uy, uz, utau, us, ukappa, vx, vy, vz, vtau, vs, vkappa):
+        e, dg = self, 1.0 / self.dgi
+        e.Af(uy, vx, trans="T", alpha=-1.0, beta=1.0)
+        e.rz3.copy_from(uz).mul(e.di)                    # W^{-1} uz
+        e.G.gemv(e.rz3, vx, trans="T", alpha=-1.0, beta=1.0)
+        vx.axpy(e.cv, -utau[0] / dg)
+        e.Af(ux, vy, trans="N", alpha=1.0, beta=1.0)
+        vy.axpy(e.bv, -utau[0] / dg)
+        e.G.gemv(ux, vz, trans="N", alpha=1.0, beta=1.0)
+        vz.axpy(e.hv, -utau[0] / dg)
+        e.rs3.copy_from(us).mul(e.d)
+        vz.axpy(e.rs3)
+        vtau[0] += dg * ukappa[0] + e.cv.dot(ux) + e.bv.dot(uy) + e.hv.dot(e.rz3)
+        e.rs3.copy_from(us).axpy(uz).mul(e.lmbda)
+        vs.axpy(e.rs3)
+        vkappa[0] += e.lmbda_g * (utau[0] + ukappa[0])
+
+    def direction(self, i, *scalars):
+        e = self
+        e.begin(i, *scalars)
+        if i == 0:
+            e.kkt.async_solves = True
+            e.kkt.factor(e.di, sync=False)               # (the directions are solved one by one inside f6)
+            e.x1.lincomb(-1.0, e.cv); e.y1.copy_from(e.bv); e.z1.copy_from(e.hv)
+            e.ksolve(e.x1, e.y1, e.z1)
+            e.x1.scal(e.dgi); e.y1.scal(e.dgi); e.z1.scal(e.dgi)
+            e.th.copy_from(e.hv).mul(e.di)
+            e.kkt.check()                                # (a failed factorisation must not be refined)
+
+    def bounds(self, i):
+        e = self                                         # right-hand side as the reference sets it up (coneprog.py:1250-1333)
+        e.ds.copy_from(e.lmbdasq)
+        if i == 1:
+            e.ds.axpy(e.ws3).addc(-e.smu)
+        e.dx.lincomb(1.0 - e.sigma, e.rx); e.dy.lincomb(1.0 - e.sigma, e.ry); e.dz.lincomb(1.0 - e.sigma, e.rz)
+        dtau, dkappa = [e.rtau], [e.rkappa]
+        e.f6(e.dx, e.dy, e.dz, dtau, e.ds, dkappa)
+        if i == 0:
+            e.ws3.copy_from(e.ds).mul(e.dz)
+        e.ds.div(e.lmbda); e.dz.div(e.lmbda)             # misc.scale2(lmbda, .) on the orthant
+        return dtau[0], dkappa[0], e.ds.max_step(), e.dz.max_step()
+
+
+def _start(e, opt, primalstart, dualstart, res0):
+    """The starting point (coneprog.py:662-842) in the vectors of engine `e`: the KKT system with W = I, or what the caller gives.
+    Returns s'z, or the Outcome if the computed point is optimal already."""
+    x, y, s, z, cv, bv, hv, Af = e.x, e.y, e.s, e.z, e.cv, e.bv, e.hv, e.Af
+    e.d.fill(1.0); e.di.fill(1.0)
     try:
-        kkt.factor(di)
+        e.kkt.factor(e.di)
     except ArithmeticError:
         raise ValueError("Rank(A) < p or Rank([G; A]) < n")
     if primalstart is None:
-        x.fill(0.0); dy.copy_from(bv); s.copy_from(hv)
-        ksolve(x, dy, s)
+        x.fill(0.0); e.dy.copy_from(bv); s.copy_from(hv)
+        e.ksolve(x, e.dy, s)
         s.scal(-1.0)
     else:                                                        # coneprog.py:703-705
-        x.set(_ipm.vector(primalstart["x"], "primalstart['x']", n)); s.set(_ipm.vector(primalstart["s"], "primalstart['s']", ml))
+        x.set(_ipm.vector(primalstart["x"], "primalstart['x']", e.n)); s.set(_ipm.vector(primalstart["s"], "primalstart['s']", e.ml))
     ts = s.max_step()
     if ts >= 0 and primalstart is not None:
         raise ValueError("initial s is not positive")
     if dualstart is None:
-        dx.copy_from(cv).scal(-1.0); y.fill(0.0); z.fill(0.0)
-        ksolve(dx, y, z)
+        e.dx.copy_from(cv).scal(-1.0); y.fill(0.0); z.fill(0.0)
+        e.ksolve(e.dx, y, z)
     else:                                                        # coneprog.py:731-733
-        if p and "y" in dualstart:
-            y.set(_ipm.vector(dualstart["y"], "dualstart['y']", p))
-        elif p:
+        if e.p and "y" in dualstart:
+            y.set(_ipm.vector(dualstart["y"], "dualstart['y']", e.p))
+        elif e.p:
             y.fill(0.0)
-        z.set(_ipm.vector(dualstart["z"], "dualstart['z']", ml))
+        z.set(_ipm.vector(dualstart["z"], "dualstart['z']", e.ml))
     tz = z.max_step()
     if tz >= 0 and dualstart is not None:
         raise ValueError("initial z is not positive")
@@ -729,271 +956,74 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
         gap = s.dot(z)
         pcost = cv.dot(x)
         dcost = -bv.dot(y) - hv.dot(z)
-        relgap = gap / -pcost if pcost < 0.0 else (gap / dcost if dcost > 0.0 else None)
-        if ts <= 0 and tz <= 0 and (gap <= ABSTOL or (relgap is not None and relgap <= RELTOL)):
-            rx.copy_from(cv); Af(y, rx, trans="T", alpha=1.0, beta=1.0); Gd.gemv(z, rx, trans="T", alpha=1.0, beta=1.0)
+        relgap = _ipm.relgap(gap, pcost, dcost)
+        if ts <= 0 and tz <= 0 and (gap <= opt.abstol or (relgap is not None and relgap <= opt.reltol)):
+            rx, ry, rz = e.rx, e.ry, e.rz
+            rx.copy_from(cv); Af(y, rx, trans="T", alpha=1.0, beta=1.0); e.G.gemv(z, rx, trans="T", alpha=1.0, beta=1.0)
             resx = rx.nrm2()
             ry.copy_from(bv); Af(x, ry, trans="N", alpha=1.0, beta=-1.0)
             resy = ry.nrm2()
-            Gd.gemv(x, rz, trans="N"); rz.axpy(s); rz.axpy(hv, -1.0)
+            e.G.gemv(x, rz, trans="N"); rz.axpy(s); rz.axpy(hv, -1.0)
             resz = rz.nrm2()
-            return result("optimal", 0, gap, relgap, pcost, dcost, max(resy / resy0, resz / resz0), resx / resx0, None, None)
+            return Outcome("optimal", 0, (gap, relgap, pcost, dcost, max(resy / res0[1], resz / res0[2]), resx / res0[0], None, None),
+                           None, [0.0, 0.0, 0.0])
     # (coneprog.py:806-842: a computed start is pushed into the cone, a given one is taken as it is)
     if primalstart is None and ts >= -1e-8 * max(nrms, 1.0):
         s.addc(1.0 + ts)
     if dualstart is None and tz >= -1e-8 * max(nrmz, 1.0):
         z.addc(1.0 + tz)
+    e.lmbda.fill(0.0)
+    return s.dot(z)
 
-    tau, kappa = 1.0, 1.0
-    gap = s.dot(z)
-    lmbda.fill(0.0)
-    dg = dgi = lmbda_g = 1.0
-    t_loop[0] = time.perf_counter()
-    for iters in range(MAXITERS + 1):
-        # residuals (coneprog.py:861-896); their norms and the objectives come back in one reduction call
-        if fast:
-            if next_stats is None:
-                raise_for(lib().kvx_lp_iter_residuals(ctypes.byref(ctx), tau, out10))
-                next_stats = tuple(out10)
-        elif fused:                                      # the six launches below in one
-            raise_for(lib().kvx_lp_residuals_dev(ml, n, Gd.cp.ptr, Gd.ri.ptr, Gd.vx.ptr, Gd.max_col, Gd.tcp.ptr, Gd.tri.ptr, Gd.tvx.ptr, Gd.max_row,
-                                                 x.ptr, z.ptr, s.ptr, cv.ptr, hv.ptr, tau, hrx.ptr, rx.ptr, hrz.ptr, rz.ptr))
-        else:
-            Af(y, hrx, trans="T", alpha=-1.0, beta=0.0)
-            Gd.gemv(z, hrx, trans="T", alpha=-1.0, beta=1.0)
-            rx.lincomb(1.0, hrx, -tau, cv)
-            Af(x, hry, trans="N")
-            ry.lincomb(1.0, hry, -tau, bv)
-            Gd.gemv(x, hrz, trans="N"); hrz.axpy(s)
-            rz.lincomb(1.0, hrz, -tau, hv)
-        if fast:
-            (v_hrx, v_rx, v_hry, v_ry, v_hrz, v_rz, cx, by, hz, lam2) = next_stats
-            next_stats = None
-        else:
-            (v_hrx, v_rx, v_hry, v_ry, v_hrz, v_rz, cx, by, hz, lam2) = reduce_multi(
-                [("dot", hrx, hrx), ("dot", rx, rx), ("dot", hry, hry), ("dot", ry, ry), ("dot", hrz, hrz), ("dot", rz, rz),
-                 ("dot", cv, x), ("dot", bv, y), ("dot", hv, z), ("dot", lmbda, lmbda)])
-        t_now = time.perf_counter()
-        if iters > 0:
-            t_phase[2] += t_now - t_mark[0]
-        t_mark[0] = t_now
-        hresx, resx = math.sqrt(v_hrx), math.sqrt(v_rx) / tau
-        hresy, resy = math.sqrt(v_hry), math.sqrt(v_ry) / tau
-        hresz, resz = math.sqrt(v_hrz), math.sqrt(v_rz) / tau
-        if iters > 0:
-            gap = (math.sqrt(lam2) / tau) ** 2           # (coneprog.py:1436; lmbda of the previous update)
-        rt = kappa + cx + by + hz
-        pcost, dcost = cx / tau, -(by + hz) / tau
-        relgap = gap / -pcost if pcost < 0.0 else (gap / dcost if dcost > 0.0 else None)
-        pres = max(resy / resy0, resz / resz0)
-        dres = resx / resx0
-        pinfres = hresx / resx0 / (-hz - by) if hz + by < 0.0 else None
-        dinfres = max(hresy / resy0, hresz / resz0) / (-cx) if cx < 0.0 else None
-        if show:
-            _ipm.progress(iters, pcost, dcost, gap, pres, dres, kappa / tau)
 
-        if (pres <= FEASTOL and dres <= FEASTOL and (gap <= ABSTOL or (relgap is not None and relgap <= RELTOL))) \
-                or iters == MAXITERS:
-            x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
-            if iters == MAXITERS:
-                return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres,
-                              msg=_ipm.MAXITERS_MSG)
-            return result("optimal", iters, gap, relgap, pcost, dcost, pres, dres, None, None)
-        elif pinfres is not None and pinfres <= FEASTOL:
-            y.scal(1.0 / (-hz - by)); z.scal(1.0 / (-hz - by))
-            return result("primal infeasible", iters, None, None, None, 1.0, None, None, pinfres, None, xs=False)
-        elif dinfres is not None and dinfres <= FEASTOL:
-            x.scal(1.0 / (-cx)); s.scal(1.0 / (-cx))
-            return result("dual infeasible", iters, None, None, -1.0, None, None, None, None, dinfres, zs=False)
+def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, primalstart=None, dualstart=None, kktsolver=None):
+    """Solve the LP  minimize c'x  s.t.  Gx <= h, Ax = b  on the GPU.  c: (n,), h: (ml,), G: spmatrix-like
+    (ml x n, sparse); A (p x n, sparse), b (p,) optional -- with equality constraints either G has at most one entry per
+    row (standard form: KKTDiagEqDev, sparse K on a fixed pattern) or any other sparse G (KKTGenEqDev, dense K in HBM).  primalstart = {'x', 's'},
+    dualstart = {'y', 'z'} (y optional) as in the reference (coneprog.py:683-737): s and z must be strictly positive.  Returns the reference's result dictionary (coneprog.py:962-974) with numpy arrays."""
+    opt = _ipm.options(options, {})
+    pb = _ipm.problem(c, G, h, None, A, b)
+    n, p, ml = pb.n, pb.p, pb.cdim
+    (Gp, Gi, Gx), (Ap, Ai, Ax) = pb.G, pb.A
+    if dims is not None and (dims.get("q") or dims.get("s") or dims.get("l", ml) != ml):
+        raise NotImplementedError("only the orthant cone dims = {'l': G.size[0], 'q': [], 's': []} runs on the GPU")
+    _lib.require_device()
 
-        # NT scaling at the first iteration (coneprog.py:1031-1043 -> misc.py:284-287)
-        if iters == 0:
-            raise_for(lib().kvx_nt_compute_scaling_dev(ml, s.ptr, z.ptr, d.ptr, di.ptr, lmbda.ptr))
-            dg = math.sqrt(kappa / tau)
-            dgi = math.sqrt(tau / kappa)
-            lmbda_g = math.sqrt(tau * kappa)
-            lam2 = lmbda.dot(lmbda)
-        if not fused:
-            lmbdasq.sqr_of(lmbda)                        # (fused: formed inside kvx_lp_newton_rhs_dev)
-        lmbdasq_g = lmbda_g ** 2
+    if kktsolver is not None:
+        # the reference's plug-in point (coneprog.py:323-344): kktsolver(W) returns f(x, y, z); host round trips per call
+        if not callable(kktsolver):
+            raise ValueError("kktsolver must be a function W -> f(x, y, z) (the reference's named solvers 'ldl', 'ldl2', 'qr', "
+                             "'chol', 'chol2' are not part of this path: 'chol2' is what runs on the GPU by default)")
+        kkt = KKTUserHost(ml, n, Gp, Gi, Gx, p, Ap, Ai, Ax, kktsolver)
+    elif p > 0:
+        Gi64 = np.asarray(Gi, dtype=np.int64)
+        diag_s = not (Gi64.size and np.bincount(Gi64, minlength=ml).max() > 1)
+        cls = KKTDiagEqDev if diag_s else KKTGenEqDev
+        kkt = _kkt_for(cls.__name__, (ml, n, p), (Gp, Gi, Ap, Ai), chol_opts,
+                       lambda: cls(ml, n, Gp, Gi, Gx, p, Ap, Ai, Ax, chol_opts), lambda k: k.reset(Gx, Ax))
+    else:
+        kkt = _kkt_for("KKTChol2Dev", (ml, n, 0), (Gp, Gi), chol_opts,
+                       lambda: KKTChol2Dev(ml, n, Gp, Gi, Gx, chol_opts), lambda k: k.reset(Gx))
+    if opt.refinement:
+        engine = _Refined(kkt, pb, opt.refinement)
+    elif _UNFUSED or not isinstance(kkt, KKTChol2Dev):
+        engine = _PerOperation(kkt, pb)
+    else:                                                # p = 0: the short launches of an iteration fused (kkt.hip, "round 3")
+        engine = (_PythonIssued if _PYCALLS else _CIssued)(kkt, pb)
+    res0 = (max(1.0, engine.cv.nrm2()), max(1.0, engine.bv.nrm2()), max(1.0, engine.hv.nrm2()))
 
-        mu = (lam2 + lmbda_g ** 2) / (1 + ml)
-        sigma = 0.0
-        wkappa3 = 0.0
-        st8 = {}                                          # dkappa, dtau of the Newton step under construction
-
-        def newton_rhs(i):
-            # right-hand side of the Newton system (coneprog.py:1250-1298) and the first half of f6_no_ir (:1130-1160)
-            dkappa = lmbdasq_g
-            if i == 1:
-                dkappa += wkappa3 - sigma * mu
-            # ds := -(lmbdasq (+ ws3 - sigma mu)) o\ lmbda,  dz := -((1 - sigma) rz + W' ds): one fused kernel
-            raise_for(lib().kvx_lp_newton_rhs_dev(ml, None if fused else lmbdasq.ptr, ws3.ptr if i == 1 else None,
-                                                  sigma * mu if i == 1 else 0.0, 1.0 - sigma, rz.ptr, lmbda.ptr, d.ptr, ds.ptr, dz.ptr))
-            if not fused:                                # fused: dx := (1 - sigma) rx is the first operation of the KKT solve
-                dx.lincomb(1.0 - sigma, rx)
-                dy.lincomb(-(1.0 - sigma), ry)
-            st8["dtau"] = (1.0 - sigma) * rt
-            st8["dkappa"] = dkappa
-
-        # factor + the two solves that do not depend on each other (coneprog.py:1066-1077 and the predictor's f3):
-        # one two-column triangular solve with the new factor
-        try:
-            kkt.async_solves = True                      # enqueue only: the host runs ahead of the GPU up to the next scalar
-            if fast:
-                pass                                     # (the predictor's launches go out with its second half, below: kvx_lp_iter_predictor)
-            elif fused:
-                # as below, with the vector operations around the solves inside their two launches: x1 := -c, z1 := h, the
-                # scaling of (x1, z1) by dgi, dx := (1 - sigma) rx
-                newton_rhs(0)
-                kkt.factor_solve_sides(di, [(cv, -1.0, hv, x1, dgi, z1, dgi), (rx, 1.0 - sigma, dz, dx, 1.0, dz, 1.0)])
-            elif REFINEMENT:
-                kkt.factor(di, sync=False)               # (the directions are solved one by one inside f6_g)
-                x1.lincomb(-1.0, cv)
-                y1.copy_from(bv)
-                z1.copy_from(hv)
-                ksolve(x1, y1, z1)
-            elif kfactor_solve2 is not None:
-                # the factorisation and the two solves in one enqueue: their right-hand sides do not depend on the factor
-                x1.lincomb(-1.0, cv)
-                y1.copy_from(bv)
-                z1.copy_from(hv)
-                newton_rhs(0)
-                kfactor_solve2(di, x1, y1, z1, dx, dy, dz)
-            else:
-                kkt.factor(di, sync=False)               # a failed factorisation surfaces in the solve right below
-                x1.lincomb(-1.0, cv)
-                y1.copy_from(bv)
-                z1.copy_from(hv)
-                newton_rhs(0)
-                ksolve2(x1, y1, z1, dx, dy, dz)
-            if fast:
-                pass
-            elif fused:
-                th.xmy(1.0, hv, di)
-            else:
-                x1.scal(dgi); y1.scal(dgi); z1.scal(dgi)
-                th.copy_from(hv).mul(di)                 # th = W^{-T} h      (coneprog.py:1126-1128)
-        except ArithmeticError:
-            kkt.async_solves = False
-            x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
-            return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, msg=_ipm.SINGULAR_MSG)
-
-        z1z1 = -1.0                                      # computed on the device with the first direction
-        out4 = (ctypes.c_double * 4)()
-        for i in (0, 1):
-            if REFINEMENT:
-                # the direction with iterative refinement (coneprog.py:1250-1333 around f6): right-hand side as the reference
-                # sets it up, then f6, the Mehrotra products, the scaling by lmbda and the step bounds, one operation at a time
-                sc = {"dgi": dgi, "lmbda_g": lmbda_g}
-                if i == 0:
-                    try:
-                        kkt.check()                      # (a failed factorisation must not be refined)
-                    except ArithmeticError:
-                        kkt.async_solves = False
-                        x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
-                        return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres,
-                                      msg=_ipm.SINGULAR_MSG)
-                ds.copy_from(lmbdasq)
-                dkap = [lmbdasq_g]
-                if i == 1:
-                    ds.axpy(ws3).addc(-sigma * mu)
-                    dkap[0] += wkappa3 - sigma * mu
-                dx.lincomb(1.0 - sigma, rx)
-                dy.lincomb(1.0 - sigma, ry)
-                dz.lincomb(1.0 - sigma, rz)
-                dta = [(1.0 - sigma) * rt]
-                f6_g(sc, dx, dy, dz, dta, ds, dkap)
-                dtau, dkappa = dta[0], dkap[0]
-                if i == 0:
-                    ws3.copy_from(ds).mul(dz)
-                    wkappa3 = dtau * dkappa
-                ds.div(lmbda); dz.div(lmbda)             # misc.scale2(lmbda, .) on the orthant
-                ts, tz = ds.max_step(), dz.max_step()
-                tt = -dtau / lmbda_g
-                tk = -dkappa / lmbda_g
-                t = max(0.0, ts, tz, tt, tk)
-                step = 1.0 if t == 0.0 else (min(1.0, 1.0 / t) if i == 0 else min(1.0, STEP / t))
-                if i == 0:
-                    sigma = (1.0 - step) ** EXPON
-                continue
-            if fast:
-                # the launches of the direction up to its scalars in ONE call (kvx_lp_iter_predictor / _corrector: what newton_rhs,
-                # factor_solve_sides / solve_sides, th.xmy and kvx_lp_second_half_dev enqueue, in that order, issued from C)
-                dkappa = -(lmbdasq_g if i == 0 else lmbdasq_g + (wkappa3 - sigma * mu)) / lmbda_g      # (newton_rhs's association)
-                dtau0 = (1.0 - sigma) * rt + dkappa / dgi
-                try:
-                    if i == 0:
-                        kkt.di = di
-                        kkt.nfactor += 1
-                        raise_for(lib().kvx_lp_iter_predictor(ctypes.byref(ctx), dgi, dtau0, out4))
-                    else:
-                        raise_for(lib().kvx_lp_iter_corrector(ctypes.byref(ctx), sigma * mu, 1.0 - sigma, dgi, dtau0, z1z1, out4))
-                except ArithmeticError:
-                    kkt.async_solves = False
-                    x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
-                    return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, msg=_ipm.SINGULAR_MSG)
-            elif i == 1:
-                newton_rhs(1)
-                if fused:
-                    kkt.solve_sides([(rx, 1.0 - sigma, dz, dx, 1.0, dz, 1.0)])
-                else:
-                    ksolve(dx, dy, dz)
-            # second half of f6_no_ir (coneprog.py:1162-1195), dz += dtau z1, ds -= dz, [ws3 := ds o dz for the corrector
-            # (coneprog.py:1303-1306)], the scaling by lmbda and the step bounds (coneprog.py:1314-1321): dtau is formed on the
-            # device from the inner products, ONE host round trip per direction (the first one after the factorisation)
-            if not fast:
-                dkappa = -st8["dkappa"] / lmbda_g
-                dtau0 = st8["dtau"] + dkappa / dgi
-                raise_for(lib().kvx_lp_second_half_dev(ml, n, p, cv.ptr, bv.ptr if p else None, th.ptr, x1.ptr, y1.ptr if p else None,
-                                                       z1.ptr, lmbda.ptr, dx.ptr, dy.ptr if p else None, dz.ptr, ds.ptr,
-                                                       ws3.ptr if i == 0 else None, dgi, dtau0, z1z1, out4))
-            dtau, z1z1, ts, tz = out4[0], out4[1], out4[2], out4[3]
-            t_now = time.perf_counter()
-            t_phase[i] += t_now - t_mark[0]
-            if _TRACE:
-                print("conelp iteration %d direction %d: %.0f us" % (iters, i, 1e6 * (t_now - t_mark[0])), file=sys.stderr)
-            t_mark[0] = t_now
-            if i == 0:
-                try:
-                    kkt.check()                          # the stream is idle by now: no extra wait
-                except ArithmeticError:
-                    kkt.async_solves = False
-                    x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
-                    return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres,
-                                  msg=_ipm.SINGULAR_MSG)
-            dkappa -= dtau
-            if i == 0:
-                wkappa3 = dtau * dkappa
-            tt = -dtau / lmbda_g
-            tk = -dkappa / lmbda_g
-            t = max(0.0, ts, tz, tt, tk)
-            if t == 0.0:
-                step = 1.0
-            else:
-                step = min(1.0, 1.0 / t) if i == 0 else min(1.0, STEP / t)
-            if i == 0:
-                sigma = (1.0 - step) ** EXPON
-
-        # update (coneprog.py:1336-1436)
-        # scaled iterates, NT scaling update and unscaled s, z (coneprog.py:1343-1432, misc.py:444-464): one fused kernel
-        if fast:
-            pass                                         # (with the residuals of the next iteration, below)
-        elif fused:
-            raise_for(lib().kvx_lp_update_x_dev(ml, n, step, ds.ptr, dz.ptr, d.ptr, di.ptr, lmbda.ptr, s.ptr, z.ptr, dx.ptr, x.ptr))
-        else:
-            x.axpy(dx, step)
-            y.axpy(dy, step)
-            raise_for(lib().kvx_lp_update_dev(ml, step, ds.ptr, dz.ptr, d.ptr, di.ptr, lmbda.ptr, s.ptr, z.ptr))
-        dg *= math.sqrt(1.0 - step * tk) / math.sqrt(1.0 - step * tt)
-        dgi = 1.0 / dg
-        lmbda_g *= math.sqrt(1.0 - step * tt) * math.sqrt(1.0 - step * tk)
-        kappa, tau = lmbda_g / dgi, lmbda_g * dgi
-        if fast:
-            # the update, the residuals of the next iteration (with the new tau) and their reductions in ONE call
-            raise_for(lib().kvx_lp_iter_update(ctypes.byref(ctx), step, tau, out10))
-            next_stats = tuple(out10)
-    raise AssertionError("unreachable")
+    out, t_loop = _start(engine, opt, primalstart, dualstart, res0), time.perf_counter()
+    looped = not isinstance(out, Outcome)
+    if looped:
+        out = _iterate(engine, opt, ml, out, res0)
+    e, xs, zs = engine, out.status != "primal infeasible", out.status != "dual infeasible"      # a certificate comes without the other half
+    return _ipm.conelp_result(
+        opt.show, out.status, e.x.get() if xs else None, e.y.get() if zs else None, e.s.get() if xs else None, e.z.get() if zs else None,
+        out.stats, e.s.max_step() if xs else None, e.z.max_step() if zs else None, out.iterations, kkt.nfactor, out.msg, **{
+            # wall time of the loop proper (coneprog.py:859-1436): no symbolic analysis, no starting point; not a key of the reference's
+            "loop seconds": (time.perf_counter() - t_loop) if looped else 0.0,
+            # the same, split at the three host synchronisations of an iteration: [-> first direction, -> second, -> next residual norms]
+            "phase seconds": list(out.phase_seconds)})
 
 
 def coneqp(P, q, G, h, options=None, chol_opts=None, A=None, b=None, initvals=None, kktsolver=None):
@@ -1141,7 +1171,7 @@ def coneqp(P, q, G, h, options=None, chol_opts=None, A=None, b=None, initvals=No
         resx, resz, resy = math.sqrt(v_rx), math.sqrt(v_rz), math.sqrt(v_ry)
         pcost = f0
         dcost = f0 + yry + zrz - gap
-        relgap = gap / -pcost if pcost < 0.0 else (gap / dcost if dcost > 0.0 else None)
+        relgap = _ipm.relgap(gap, pcost, dcost)
         pres, dres = max(resy / resy0, resz / resz0), resx / resx0
         if show:
             _ipm.progress(iters, pcost, dcost, gap, pres, dres)
@@ -1183,12 +1213,9 @@ def coneqp(P, q, G, h, options=None, chol_opts=None, A=None, b=None, initvals=No
             # step to the boundary (coneprog.py:2431-2451)
             ds.div(lmbda); dz.div(lmbda)
             t = max(0.0, *reduce_multi([("max", ds), ("max", dz)]))
-            if t == 0.0:
-                step = 1.0
-            else:
-                step = min(1.0, 1.0 / t) if i == 0 else min(1.0, STEP / t)
+            step = _ipm.step_length(t, i)
             if i == 0:
-                sigma = min(1.0, max(0.0, 1.0 - step + dsdz / gap * step ** 2)) ** EXPON
+                sigma = min(1.0, max(0.0, 1.0 - step + dsdz / gap * step ** 2)) ** _ipm.EXPON
                 eta = 0.0
 
         # update iterates and scaling (coneprog.py:2454-2545)

@@ -24,6 +24,7 @@ one kept Cholesky factor) with the options of `options['osqp']`.  coneqp reads '
 """
 import numpy as np
 
+from . import _ipm
 from . import base as _base
 from . import cone as _cone
 from . import cvx as _cvx
@@ -135,10 +136,6 @@ def _nrm2(v):
     return float(np.sqrt(np.dot(v, v)))
 
 
-def _relgap(gap, pcost, dcost):
-    return gap / -pcost if pcost < 0.0 else (gap / dcost if dcost > 0.0 else None)
-
-
 def _lp_osqp(c, G, h, A, b, opts):
     """solvers.lp(..., solver='osqp') (coneprog.py:2818-2906): osqp.qp, then the reference's dictionary from x, z, y."""
     G, A = _sp(G), _sp(A)
@@ -157,7 +154,7 @@ def _lp_osqp(c, G, h, A, b, opts):
     ry = b - _mv(A, x) if b.size else np.zeros(0)
     rz = _mv(G, x) + s - h
     pres = max(_nrm2(ry) / max(1.0, _nrm2(b)), _nrm2(rz) / max(1.0, _nrm2(h)))
-    return _osqp_result(status, x, s, y, z, pcost, dcost, gap, _relgap(gap, pcost, dcost), pres, _nrm2(rx) / max(1.0, _nrm2(c)),
+    return _osqp_result(status, x, s, y, z, pcost, dcost, gap, _ipm.relgap(gap, pcost, dcost), pres, _nrm2(rx) / max(1.0, _nrm2(c)),
                         float(s.min()), float(z.min()))
 
 
@@ -186,7 +183,7 @@ def _qp_osqp(P, q, G, h, A, b, opts):
     gap = float(np.dot(s, z))
     dcost = pcost + float(np.dot(y, ry)) + float(np.dot(z, rz)) - gap
     pres = max(_nrm2(ry) / max(1.0, _nrm2(b)), _nrm2(rz) / max(1.0, _nrm2(h)))
-    return _osqp_result("optimal", x, s, y, z, pcost, dcost, gap, _relgap(gap, pcost, dcost), pres, _nrm2(rx) / max(1.0, _nrm2(q)),
+    return _osqp_result("optimal", x, s, y, z, pcost, dcost, gap, _ipm.relgap(gap, pcost, dcost), pres, _nrm2(rx) / max(1.0, _nrm2(q)),
                         float(s.min()), float(z.min()))
 
 

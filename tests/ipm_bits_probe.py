@@ -53,4 +53,20 @@ n = P["n"]
 G = spmatrix.from_ccs(P["ml"], n, P["Gp"], P["Gi"], P["Gx"])
 H = spmatrix.from_ccs(n, n, np.arange(n + 1), np.arange(n), np.full(n, 0.5))
 res["qp25x18"] = digest(kvx_lp.coneqp(H, P["c"], G, P["h"]))
+
+# the schedules that have no fused form -- equality constraints (general G: KKTGenEqDev; standard form: KKTDiagEqDev) and iterative
+# refinement -- under the same switches: the library reads KVX_LP_UNFUSED too
+L = workloads.lp_grid_eq(6, 5, 4)
+G = spmatrix.from_ccs(L["ml"], L["n"], L["Gp"], L["Gi"], L["Gx"])
+A = spmatrix.from_ccs(L["p"], L["n"], L["Ap"], L["Ai"], L["Ax"])
+res["eq6x5p4"] = digest(kvx_lp.conelp(L["c"], G, L["h"], A=A, b=L["b"]))
+res["eq6x5p4_r1"] = digest(kvx_lp.conelp(L["c"], G, L["h"], A=A, b=L["b"], options={"refinement": 1}))
+L = workloads.lp_grid_std(6, 5)
+G = spmatrix.from_ccs(L["ml"], L["n"], L["Gp"], L["Gi"], L["Gx"])
+A = spmatrix.from_ccs(L["p"], L["n"], L["Ap"], L["Ai"], L["Ax"])
+res["std6x5"] = digest(kvx_lp.conelp(L["c"], G, L["h"], A=A, b=L["b"]))
+P = workloads.lp_grid(6, 5)
+G = spmatrix.from_ccs(P["ml"], P["n"], P["Gp"], P["Gi"], P["Gx"])
+for r in (1, 2):
+    res["grid6x5_r%d" % r] = digest(kvx_lp.conelp(P["c"], G, P["h"], options={"refinement": r}))
 print(json.dumps(res))

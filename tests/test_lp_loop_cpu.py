@@ -1,0 +1,162 @@
+"""The interior-point loop of lp.conelp (lp._iterate) on the host: a numpy engine with dense G and the p = 0 KKT solve stands in for
+the device engines, so the host logic that picks "optimal", "primal infeasible", "dual infeasible" or "unknown" runs without a GPU.
+Compared with the reference's own runs in tests/golden/g4_conelp.* to 1e-10 relative (a numpy restatement of the loop differs from
+them by 1e-16 to 1.1e-15)."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+from kvxopt_amd import _ipm, lp, workloads
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+class NumpyEngine:
+    """lp._iterate's engine protocol in numpy.  KKT solve (misc.py:1489-1563 with p = 0): x += G' di^2 z; x = S^-1 x; z = di (G x) - di z."""
+
+    def __init__(self, c, G, h):
+        self.c, self.G, self.h = (np.asarray(a, dtype=float) for a in (c, G, h))
+        self.d = self.di = np.ones(len(self.h))
+        self.lmbda = np.zeros(len(self.h))
+        self.scaled = []
+        self.tau = 1.0
+        # starting point (coneprog.py:662-842): W = I, s = h - G x with G'G x = G'h, z = G x with G'G x = -c, pushed into the cone
+        self.S = self.G.T @ self.G
+        self.x, s = self.ksolve(np.zeros(len(self.c)), self.h)
+        _, z = self.ksolve(-self.c, np.zeros(len(self.h)))
+        self.s, self.z = (v + (1.0 + max(-v)) if max(-v) >= -1e-8 * max(np.linalg.norm(v), 1.0) else v for v in (-s, z))
+
+    def ksolve(self, x, z):
+        x = np.linalg.solve(self.S, x + self.G.T @ (self.di * (self.di * z)))
+        return x, self.di * (self.G @ x) - self.di * z
+
+    def stats(self, tau):
+        c, G, h = self.c, self.G, self.h
+        hrx = -(G.T @ self.z)
+        hrz = G @ self.x + self.s
+        self.rx, self.rz = hrx - tau * c, hrz - tau * h
+        return (hrx @ hrx, self.rx @ self.rx, 0.0, 0.0, hrz @ hrz, self.rz @ self.rz, c @ self.x, 0.0, h @ self.z, self.lmbda @ self.lmbda)
+
+    def scaling(self):
+        self.d = np.sqrt(self.s / self.z)
+        self.di = 1.0 / self.d
+        self.lmbda = np.sqrt(self.s * self.z)
+        return self.lmbda @ self.lmbda
+
+    def direction(self, i, sigma, mu, rt, dgi, lmbda_g, wkappa3):
+        if i == 0:
+            self.S = self.G.T @ ((self.di ** 2)[:, None] * self.G)
+            self.x1, self.z1 = (dgi * v for v in self.ksolve(-self.c, self.h))
+        ds = self.lmbda ** 2
+        dkappa = lmbda_g ** 2
+        if i == 1:
+            ds = ds + self.ws3 - sigma * mu
+            dkappa += wkappa3 - sigma * mu
+        ds = -ds / self.lmbda
+        dx, dz = self.ksolve((1.0 - sigma) * self.rx, -((1.0 - sigma) * self.rz + self.d * ds))
+        dkappa = -dkappa / lmbda_g
+        dtau = dgi * ((1.0 - sigma) * rt + dkappa / dgi + self.c @ dx + (self.di * self.h) @ dz) / (1.0 + self.z1 @ self.z1)
+        self.dx, dz = dx + dtau * self.x1, dz + dtau * self.z1
+        ds = ds - dz
+        if i == 0:
+            self.ws3 = ds * dz
+        self.dtau, self.dkappa, self.ds, self.dz = dtau, dkappa - dtau, ds / self.lmbda, dz / self.lmbda
+
+    def bounds(self, i):
+        return self.dtau, self.dkappa, max(-self.ds), max(-self.dz)
+
+    def update(self, step, tau):
+        self.x = self.x + step * self.dx
+        rs, rz = (np.sqrt((1.0 + step * v) * self.lmbda) for v in (self.ds, self.dz))       # misc.py:444-464
+        self.d = self.d * rs / rz
+        self.di = 1.0 / self.d
+        self.lmbda = rs * rz
+        self.s, self.z = self.d * self.lmbda, self.di * self.lmbda
+        self.tau = tau
+
+    def scale(self, primal, dual):
+        self.scaled.append((primal, dual))
+        if primal is not None:
+            self.x, self.s = primal * self.x, primal * self.s
+        if dual is not None:
+            self.z = dual * self.z
+
+
+def run(c, G, h, options=None, engine=NumpyEngine):
+    e = engine(c, G, h)
+    res0 = (max(1.0, np.linalg.norm(e.c)), 1.0, max(1.0, np.linalg.norm(e.h)))
+    return e, lp._iterate(e, _ipm.options(options, {}), len(e.h), e.s @ e.z, res0)
+
+
+def rel(a, b):
+    a, b = np.asarray(a, float), np.asarray(b, float)
+    return np.abs(a - b).max() / np.abs(b).max()
+
+
+DOC_LP = ([-4., -5.], [[2., 1.], [1., 2.], [-1., 0.], [0., -1.]], [3., 3., 0., 0.])       # examples/doc/chap8/lp.py
+CASES = {"doc_lp": DOC_LP + ("optimal", 4, "x"),
+         "primal_infeasible": ([1.0], [[-1.0], [1.0]], [-1.0, 0.0], "primal infeasible", 4, "z"),
+         "dual_infeasible": ([-1.0, 0.5], [[-1.0, 0.0], [0.0, -1.0]], [0.0, 0.0], "dual infeasible", 4, "x")}
+
+
+@pytest.fixture(scope="module")
+def meta():
+    return json.load(open(os.path.join(GOLDEN, "g4_conelp.json")))["cases"]
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_loop_doc_and_infeasible(meta, name):
+    c, G, h, status, iters, key = CASES[name]
+    e, out = run(c, G, h)
+    assert out.status == status == meta[name].get("status", status) and out.msg is None
+    assert out.iterations == iters == meta[name]["iterations"]
+    assert rel(getattr(e, key), meta[name][key]) < 1e-10
+    if status == "optimal":
+        assert e.scaled == [(1.0 / e.tau, 1.0 / e.tau)] and out.stats[6:] == (None, None)
+    else:
+        # a certificate: only its own half is scaled (and returned), by the objective of the other half
+        (primal, dual), = e.scaled
+        assert (primal is None) == (status == "primal infeasible") and (dual is None) == (status == "dual infeasible")
+        assert out.stats[:6] == ((None, None, None, 1.0, None, None) if primal is None else (None, None, -1.0, None, None, None))
+        assert out.stats[6 if primal is None else 7] <= 1e-7 and out.stats[7 if primal is None else 6] is None
+
+
+def test_loop_grid6x5(meta):
+    P = workloads.lp_grid(6, 5)
+    G = np.zeros((P["ml"], P["n"]))
+    G[P["Gi"], np.repeat(np.arange(P["n"]), np.diff(P["Gp"]))] = P["Gx"]
+    e, out = run(P["c"], G, P["h"])
+    assert out.status == meta["grid6x5"]["status"] == "optimal"
+    assert out.iterations == meta["grid6x5"]["iterations"] == 10
+    assert rel(e.x, np.load(os.path.join(GOLDEN, "g4_conelp.npz"))["grid6x5_x"]) < 1e-10
+    assert len(out.phase_seconds) == 3 and all(t > 0.0 for t in out.phase_seconds)
+
+
+def test_loop_maxiters():
+    e, out = run(*DOC_LP[:3], options={"maxiters": 2})
+    assert (out.status, out.iterations, out.msg) == ("unknown", 2, _ipm.MAXITERS_MSG)
+    assert e.scaled == [(1.0 / e.tau, 1.0 / e.tau)]
+
+
+def test_loop_singular_kkt():
+    class Singular(NumpyEngine):
+        factored = 0
+
+        def direction(self, i, *scalars):
+            if i == 0:
+                self.factored += 1
+                if self.factored == 2:
+                    raise ArithmeticError("singular")
+            super().direction(i, *scalars)
+
+    e, out = run(*DOC_LP[:3], engine=Singular)
+    assert (out.status, out.iterations, out.msg) == ("unknown", 1, _ipm.SINGULAR_MSG)
+    assert e.scaled == [(1.0 / e.tau, 1.0 / e.tau)] and e.tau != 1.0          # the iterates scaled by 1 / tau, exactly once
+    assert None not in out.stats[:6]
+
+
+def test_helpers():
+    assert _ipm.relgap(1.0, -4.0, 9.0) == 0.25 and _ipm.relgap(1.0, 4.0, 8.0) == 0.125 and _ipm.relgap(1.0, 0.0, 0.0) is None
+    assert [_ipm.step_length(t, i) for t in (0.0, 0.5, 4.0) for i in (0, 1)] == [1.0, 1.0, 1.0, 1.0, 0.25, _ipm.STEP / 4.0]
