@@ -587,6 +587,30 @@ int kvx_admm_polish(kvx_admm *S, double delta, int64_t refine_iter, double *out_
 int kvx_admm_polish_state(kvx_admm *S, double *x, double *z, double *y, int64_t *act);
 int kvx_admm_polish_accept(kvx_admm *S);
 
+/* ---- a batch on the kept factor: B data sets (q_b, l_b, u_b) through the one factor of the kept problem, at its current rho.
+ * All after kvx_admm_setup_dev.  Matrices are column-major, member b in column b: n x B (ld = n) or m x B (ld = m).  The batch
+ * has buffers of its own: the kept problem's q, l, u, state, rho and factor are not touched.
+ * kvx_admm_batch_begin(B, Q, L, U): host pointers to unscaled data, any of them NULL (the kept problem's vector in every
+ *   column).  1 <= B <= 65535.  Rescaled on the device with the plan's D, E, c by the rule of kvx_admm_update; x = z = y = dx =
+ *   dy = 0 for every member.  Every member must give every row the rho class (equality, free, other) it has in the kept problem
+ *   and l <= u: otherwise KVX_EINVAL, the message names member and row, nothing is changed.  Device memory: 4 n B + 5 m B doubles
+ *   and the B x 24 x (workgroups) partial results.
+ * kvx_admm_batch_iterate(k, running, out): running[b] != 0: member b is iterated; a member with running[b] == 0 is frozen --
+ *   its state and its 24 numbers are not written.  k x {right-hand sides, one triangular solve with B right-hand sides, update},
+ *   then the residual kernels and one copy: out[b * 24 + i] is entry [i] of kvx_admm_iterate for member b.  A factor a polish
+ *   left stale is rebuilt first at the current rho (k > 0; one counted factorisation), as kvx_admm_iterate does.  No rho ever
+ *   changes inside a batch.
+ * kvx_admm_batch_state: the scaled x (n x B), z, y (m x B), dx, dy to the host; any pointer may be NULL.
+ * kvx_admm_batch_solution(kinds, X, Y): per member the unscaled result of kvx_admm_solution for kind 0, 1, 2 (the part a kind
+ *   does not give is zero), kind -1: zeros.
+ * kvx_admm_batch_end: frees the batch buffers (kvx_admm_free frees them too); a later begin allocates again.
+ * Fixed summation order, no floating-point atomics; KVX_EDEVICE without a GPU, KVX_EINVAL before setup or before begin. */
+int kvx_admm_batch_begin(kvx_admm *S, int64_t B, const double *Q, const double *L, const double *U);
+int kvx_admm_batch_iterate(kvx_admm *S, int64_t k, const int64_t *running, double *out_host);
+int kvx_admm_batch_state(kvx_admm *S, double *x, double *z, double *y, double *dx, double *dy);
+int kvx_admm_batch_solution(kvx_admm *S, const int64_t *kinds, double *X, double *Y);
+int kvx_admm_batch_end(kvx_admm *S);
+
 /* ---- dense helpers of the equality-constrained KKT solve with a general S (misc.py:1476-1487, 1545): K = A S^-1 A' formed
  * as a dense p x p matrix from X = S^-1 A' (kvx_chol_solve_dev with nrhs = p) when p is moderate ------------------------- */
 /* Y(j, c) = sum_i A(i, j) X(i, c) for the CCS matrix A with n columns and every column c < ncols of the dense X */

@@ -232,6 +232,11 @@ _SIGS = {
     "kvx_admm_polish": (ctypes.c_int, [vp, f64, i64, f64p]),
     "kvx_admm_polish_state": (ctypes.c_int, [vp, f64p, f64p, f64p, i64p]),
     "kvx_admm_polish_accept": (ctypes.c_int, [vp]),
+    "kvx_admm_batch_begin": (ctypes.c_int, [vp, i64, f64p, f64p, f64p]),
+    "kvx_admm_batch_iterate": (ctypes.c_int, [vp, i64, i64p, f64p]),
+    "kvx_admm_batch_state": (ctypes.c_int, [vp, f64p, f64p, f64p, f64p, f64p]),
+    "kvx_admm_batch_solution": (ctypes.c_int, [vp, i64p, f64p, f64p]),
+    "kvx_admm_batch_end": (ctypes.c_int, [vp]),
     "kvx_vec_scatter_dev": (ctypes.c_int, [i64, vp, vp, vp]),
     "kvx_nts_colscale_dev": (ctypes.c_int, [i64, vp, vp, vp, vp]),
     "kvx_spmm_t_dev": (ctypes.c_int, [i64, i64, vp, vp, vp, vp, i64, vp, i64]),

@@ -13,9 +13,14 @@
 // when a row changes its rho class), kvx_admm_warm_start / kvx_admm_cold_start set the state, and kvx_admm_polish solves the
 // equality-constrained QP of the guessed active set on S_pol = P + delta I + A' diag(w) A -- the analysed pattern, the same
 // kvx_chol, whose numeric factor it takes over: the handle marks the ADMM factor stale and the next iteration rebuilds it.
+//
+// A batch (kvx_admm_batch_*, admm_batch.hip) runs B data sets (q_b, l_b, u_b) through that one factor: buffers of its own,
+// column-major, one triangular solve with B right-hand sides per iteration, one host read of B x 24 numbers per check.  The kept
+// problem's data, state, rho and factor are not touched (a stale factor is rebuilt once, as kvx_admm_iterate does).
 #include "../../include/kvxhip.h"
 #include "abi_guard.hpp"
 #include "admm.hpp"
+#include "admm_batch.hpp"
 #include "admm_polish.hpp"
 #include "devpool.hpp"
 
@@ -56,6 +61,11 @@ struct kvx_admm {
     PolishDev p{};
     double *d_stage = nullptr, *d_ppart = nullptr, *d_pres = nullptr, *d_Lxd = nullptr;
     double lxd_delta = 0.0;
+    // a batch on the kept factor (admm_batch.hip): B members, buffers from kvx_admm_batch_begin (they are in `owned` as well)
+    AdmmBatchDev b{};
+    std::vector<void *> bowned;
+    int *d_run = nullptr;
+    double *d_bpart = nullptr, *d_bres = nullptr;
 };
 
 namespace {
@@ -513,6 +523,176 @@ int polish_accept_impl(kvx_admm *S)
     return KVX_OK;
 }
 
+// ---- a batch on the kept factor ---------------------------------------------------------------------------------------------
+int batch_end_impl(kvx_admm *S)
+{
+    if (!S) return KVX_EINVAL;
+    for (void *p : S->bowned) {
+        S->owned.erase(std::remove(S->owned.begin(), S->owned.end(), p), S->owned.end());
+        (void)pool_free(p);
+    }
+    S->bowned.clear();
+    S->b = AdmmBatchDev{};
+    S->d_run = nullptr;
+    S->d_bpart = S->d_bres = nullptr;
+    return KVX_OK;
+}
+
+int batch_zeros(kvx_admm *S, double **dst, int64_t count)
+{
+    const int rc = zeros(S, dst, count);                                // on failure nothing was pushed for this pointer
+    if (!rc) S->bowned.push_back(*dst);
+    return rc;
+}
+
+int batch_begin_impl(kvx_admm *S, int64_t B, const double *Q, const double *L, const double *U)
+{
+    if (!S) return KVX_EINVAL;
+    if (B < 1 || B > 65535) { set_last_error("kvx_admm_batch_begin: 1 <= B <= 65535 is required"); return KVX_EINVAL; }
+    const int64_t m = S->m, n = S->n;
+    // every member gives every row the rho class it has in the kept problem: one rho vector, one factor
+    if (L || U)
+        for (int64_t bm = 0; bm < B; bm++)
+            for (int64_t i = 0; i < m; i++) {
+                const double lr = L ? L[i + bm * m] : 0.0, ur = U ? U[i + bm * m] : 0.0;
+                const double l = !L ? S->l[i] : (lr <= -OSQP_INFTY * MIN_SCALING ? -OSQP_INFTY : S->E[i] * lr);
+                const double u = !U ? S->u[i] : (ur >= OSQP_INFTY * MIN_SCALING ? OSQP_INFTY : S->E[i] * ur);
+                if (!(l <= u)) {
+                    set_last_error("kvx_admm_batch_begin: l <= u does not hold in member " + std::to_string(bm) + ", row " + std::to_string(i));
+                    return KVX_EINVAL;
+                }
+                if (rho_class(l, u) != rho_class(S->l[i], S->u[i])) {
+                    set_last_error("kvx_admm_batch_begin: member " + std::to_string(bm) + ", row " + std::to_string(i) +
+                                   " is not in the rho class the row has in the kept problem");
+                    return KVX_EINVAL;
+                }
+            }
+    int rc = need_setup(S, "kvx_admm_batch_begin");
+    if (rc) return rc;
+    AdmmBatchDev &b = S->b;
+    if (b.B != B) {
+        batch_end_impl(S);
+        b.a = S->d;
+        b.B = B;
+        double *run = nullptr;                                          // B int flags in a buffer of doubles
+        const int64_t nb = admm_batch_residual_blocks(b);
+        if ((rc = batch_zeros(S, &b.q, n * B)) || (rc = batch_zeros(S, &b.x, n * B)) || (rc = batch_zeros(S, &b.dx, n * B)) ||
+            (rc = batch_zeros(S, &b.xt, n * B)) || (rc = batch_zeros(S, &b.l, m * B)) || (rc = batch_zeros(S, &b.u, m * B)) ||
+            (rc = batch_zeros(S, &b.z, m * B)) || (rc = batch_zeros(S, &b.y, m * B)) || (rc = batch_zeros(S, &b.dy, m * B)) ||
+            (rc = batch_zeros(S, &S->d_bpart, B * ADMM_NRES * nb)) || (rc = batch_zeros(S, &S->d_bres, B * ADMM_NRES)) ||
+            (rc = batch_zeros(S, &run, B))) {
+            batch_end_impl(S);
+            return rc;
+        }
+        S->d_run = reinterpret_cast<int *>(run);
+        b.run = S->d_run;
+    }
+    b.a = S->d;                                                         // the kept q, l, u as they are now
+    const size_t nb_ = (size_t)(n * B) * sizeof(double), mb_ = (size_t)(m * B) * sizeof(double);
+    if (Q) HIPCHK(hipMemcpy(b.xt, Q, nb_, hipMemcpyHostToDevice));     // xt and dy stage the raw data
+    launch_admm_batch_scale_q(nullptr, b, S->c, Q ? b.xt : nullptr);
+    if (L) HIPCHK(hipMemcpy(b.dy, L, mb_, hipMemcpyHostToDevice));
+    launch_admm_batch_scale_bound(nullptr, b, false, L ? b.dy : nullptr);
+    if (U) HIPCHK(hipMemcpy(b.dy, U, mb_, hipMemcpyHostToDevice));
+    launch_admm_batch_scale_bound(nullptr, b, true, U ? b.dy : nullptr);
+    HIPCHK(hipMemsetAsync(b.x, 0, nb_, nullptr));
+    HIPCHK(hipMemsetAsync(b.dx, 0, nb_, nullptr));
+    HIPCHK(hipMemsetAsync(b.z, 0, mb_, nullptr));
+    HIPCHK(hipMemsetAsync(b.y, 0, mb_, nullptr));
+    HIPCHK(hipMemsetAsync(b.dy, 0, mb_, nullptr));
+    HIPCHK(hipMemsetAsync(S->d_bres, 0, (size_t)(B * ADMM_NRES) * sizeof(double), nullptr));
+    HIPCHK(hipGetLastError());
+    return KVX_OK;
+}
+
+int need_batch(kvx_admm *S, const char *who)
+{
+    const int rc = need_setup(S, who);
+    if (rc) return rc;
+    if (S->b.B < 1) { set_last_error(std::string(who) + ": kvx_admm_batch_begin has not run"); return KVX_EINVAL; }
+    return KVX_OK;
+}
+
+int batch_iterate_impl(kvx_admm *S, int64_t k, const int64_t *running, double *out)
+{
+    if (!S || k < 0 || !running || !out) return KVX_EINVAL;
+    int rc = need_batch(S, "kvx_admm_batch_iterate");
+    if (rc) return rc;
+    const AdmmBatchDev &b = S->b;
+    std::vector<int> run((size_t)b.B);
+    for (int64_t bm = 0; bm < b.B; bm++) run[(size_t)bm] = running[bm] != 0;
+    HIPCHK(hipMemcpy(S->d_run, run.data(), run.size() * sizeof(int), hipMemcpyHostToDevice));
+    const int64_t ld = std::max<int64_t>(1, S->n);
+    if (S->stale && k > 0) {                                            // a polish took the factor over: S at the current rho again
+        if ((rc = refactor(S, S->rho0))) return rc;
+    }
+    for (int64_t it = 0; it < k; it++) {
+        launch_admm_batch_rhs(nullptr, b);
+        if ((rc = kvx_chol_solve_async_dev(S->F, 0, b.xt, b.B, ld))) return rc;
+        launch_admm_batch_update(nullptr, b);
+    }
+    launch_admm_batch_residuals(nullptr, b, S->d_bpart, S->d_bres);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, S->d_bres, (size_t)(b.B * ADMM_NRES) * sizeof(double), hipMemcpyDeviceToHost));      // the one host synchronisation
+    return KVX_OK;
+}
+
+int batch_state_impl(kvx_admm *S, double *x, double *z, double *y, double *dx, double *dy)
+{
+    if (!S) return KVX_EINVAL;
+    int rc = need_batch(S, "kvx_admm_batch_state");
+    if (rc) return rc;
+    const AdmmBatchDev &b = S->b;
+    if ((rc = fetch(x, b.x, S->n * b.B)) || (rc = fetch(z, b.z, S->m * b.B)) || (rc = fetch(y, b.y, S->m * b.B)) ||
+        (rc = fetch(dx, b.dx, S->n * b.B)) || (rc = fetch(dy, b.dy, S->m * b.B)))
+        return rc;
+    return KVX_OK;
+}
+
+int batch_solution_impl(kvx_admm *S, const int64_t *kinds, double *X, double *Y)
+{
+    if (!S || !kinds || !X || !Y) return KVX_EINVAL;
+    int rc = need_batch(S, "kvx_admm_batch_solution");
+    if (rc) return rc;
+    const AdmmBatchDev &b = S->b;
+    const int64_t m = S->m, n = S->n, B = b.B;
+    bool any[3] = {false, false, false};
+    for (int64_t bm = 0; bm < B; bm++) {
+        if (kinds[bm] < -1 || kinds[bm] > 2) { set_last_error("kvx_admm_batch_solution: a kind is -1, 0, 1 or 2"); return KVX_EINVAL; }
+        if (kinds[bm] >= 0) any[kinds[bm]] = true;
+    }
+    std::vector<double> x, dx, y, dy, l, u;
+    if (any[0]) { x.resize((size_t)(n * B)); y.resize((size_t)(m * B)); if ((rc = fetch(x.data(), b.x, n * B)) || (rc = fetch(y.data(), b.y, m * B))) return rc; }
+    if (any[1]) {
+        dy.resize((size_t)(m * B)); l.resize((size_t)(m * B)); u.resize((size_t)(m * B));
+        if ((rc = fetch(dy.data(), b.dy, m * B)) || (rc = fetch(l.data(), b.l, m * B)) || (rc = fetch(u.data(), b.u, m * B))) return rc;
+    }
+    if (any[2]) { dx.resize((size_t)(n * B)); if ((rc = fetch(dx.data(), b.dx, n * B))) return rc; }
+    const double cinv = 1.0 / S->c;
+    for (int64_t bm = 0; bm < B; bm++) {
+        const int64_t kind = kinds[bm];
+        double *xo = X + bm * n, *yo = Y + bm * m;
+        std::fill(xo, xo + n, 0.0);
+        std::fill(yo, yo + m, 0.0);
+        if (kind == 0 || kind == 2) {                                   // x = D x, or the certificate D dx
+            const double *src = (kind == 0 ? x.data() : dx.data()) + bm * n;
+            for (int64_t j = 0; j < n; j++) xo[j] = src[j] * S->D[j];
+        }
+        if (kind == 0 || kind == 1) {                                   // y = E y / c, or the certificate E dy / c
+            const double *src = (kind == 0 ? y.data() : dy.data()) + bm * m;
+            for (int64_t i = 0; i < m; i++) {
+                double v = src[i];
+                if (kind == 1) {                                        // without the parts that push against an infinite bound
+                    const bool ui = u[(size_t)(i + bm * m)] >= OSQP_INFTY * MIN_SCALING, li = l[(size_t)(i + bm * m)] <= -OSQP_INFTY * MIN_SCALING;
+                    v = ui && li ? 0.0 : (ui ? std::min(v, 0.0) : (li ? std::max(v, 0.0) : v));
+                }
+                yo[i] = S->E[i] * v * cinv;
+            }
+        }
+    }
+    return KVX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -636,6 +816,31 @@ int kvx_admm_info(kvx_admm *S, int64_t info[8])
     const int64_t v[8] = {S->m, S->n, S->snz, S->nfact, S->niter, (int64_t)S->rs.size(), (int64_t)S->rl.size(), S->dev ? 1 : 0};
     std::copy(v, v + 8, info);
     return KVX_OK;
+}
+
+int kvx_admm_batch_begin(kvx_admm *S, int64_t B, const double *Q, const double *L, const double *U)
+{
+    return guarded([&] { return batch_begin_impl(S, B, Q, L, U); });
+}
+
+int kvx_admm_batch_iterate(kvx_admm *S, int64_t k, const int64_t *running, double *out_host)
+{
+    return guarded([&] { return batch_iterate_impl(S, k, running, out_host); });
+}
+
+int kvx_admm_batch_state(kvx_admm *S, double *x, double *z, double *y, double *dx, double *dy)
+{
+    return guarded([&] { return batch_state_impl(S, x, z, y, dx, dy); });
+}
+
+int kvx_admm_batch_solution(kvx_admm *S, const int64_t *kinds, double *X, double *Y)
+{
+    return guarded([&] { return batch_solution_impl(S, kinds, X, Y); });
+}
+
+int kvx_admm_batch_end(kvx_admm *S)
+{
+    return guarded([&] { return batch_end_impl(S); });
 }
 
 void kvx_admm_free(kvx_admm *S)

@@ -5,6 +5,7 @@
     options                                                          the module-level dict of the reference
     Problem(q, A, l, u, P=None, options=None)                        the same problem kept on the device (not in the reference):
         .update(q, l, u)  .warm_start(x, y)  .solve() -> (status, x, y)  .info  .close()
+        .solve_batch(Q, L=None, U=None, chunk=1024) -> (statuses, X, Y)  .batch_info     B data sets on the kept factor
 
 The reference binds the external OSQP library; here the published algorithm (Stellato et al. 2020) runs in HBM through the
 kvx_admm_* entry points of include/kvxhip.h: the plan equilibrates the data on the host, S = P + sigma I + A' diag(rho) A is
@@ -22,6 +23,11 @@ numeric refactorisation only when a row changes its rho class), every solve() co
 (warm_start = 0: from zero), rho persists, and 'polish', 'delta', 'polish_refine_iter' take effect: after 'solved' the active
 set is guessed, one equality-constrained QP is solved on the analysed pattern and refined, and the result is taken when its
 residuals are smaller ("A kept problem").
+
+solve_batch() runs B data sets (q_b, l_b, u_b), the columns of Q, L, U, through the kept factor at the problem's current rho: every
+member starts from zero, one triangular solve with B right-hand sides per iteration, one host read per termination check for the
+whole batch, a member stops at its own check.  No rho adapts, nothing is polished, the kept problem is left as it was (DESIGN
+section 11, "A batch on the kept factor").
 """
 import ctypes
 import math
@@ -97,6 +103,58 @@ def _vector(v, name, rows):
     return _base.flat(v).copy()
 
 
+def _matrix2(v, name, rows, cols=None):
+    """A dense 'd' matrix of `rows` x `cols` entries (cols None: any) as a column-major float64 array, with the checks and texts
+    of _vector."""
+    if isinstance(v, _base.matrix) or (hasattr(v, "typecode") and hasattr(v, "size") and not hasattr(v, "CCS")):
+        if v.typecode != "d":
+            raise TypeError("%s must be a matrix with typecode 'd'" % name)
+        size = tuple(v.size)
+    elif isinstance(v, np.ndarray) and v.dtype == np.float64 and v.ndim == 2:
+        size = v.shape
+    else:
+        raise TypeError("%s must be a matrix with typecode 'd'" % name)
+    if size[0] != rows or (cols is not None and size[1] != cols):
+        raise ValueError("incompatible dimensions")
+    return _base.flat(v).copy().reshape((int(size[0]), int(size[1])), order="F")
+
+
+def _rho_classes(lb, ub):
+    """On scaled bounds: 0 without a finite bound, 1 equality (u - l < 1e-4), 2 the others (the rho vector)."""
+    free = (lb <= -INFTY * 1e-4) & (ub >= INFTY * 1e-4)
+    return np.where(free, 0, np.where(ub - lb < 1e-4, 1, 2))
+
+
+def _check_batch(Q, L, U, n, m, E, l, u):
+    """The arguments of Problem.solve_batch on the host: (Q, L, U) as column-major float64 arrays n x B, m x B (None stays None).
+    E: the row scaling of the kept problem, l, u: its current unscaled bounds.  Every member must have l <= u and give every
+    row the rho class it has in the kept problem; ValueError names the first (member, row)."""
+    Q = _matrix2(Q, "Q", n)
+    B = Q.shape[1]
+    if B < 1:
+        raise ValueError("incompatible dimensions")
+    L = None if L is None else _matrix2(L, "L", m, B)
+    U = None if U is None else _matrix2(U, "U", m, B)
+    if L is None and U is None:
+        return Q, L, U
+    E = np.asarray(E, dtype=np.float64)
+    scale = lambda raw, sign: np.where(sign * raw >= INFTY * 1e-4, sign * INFTY, (E * raw.T).T)
+    kl, ku = scale(np.asarray(l, dtype=np.float64), -1.0), scale(np.asarray(u, dtype=np.float64), 1.0)
+    lb = kl[:, None] if L is None else scale(L, -1.0)
+    ub = ku[:, None] if U is None else scale(U, 1.0)
+    lb, ub = np.broadcast_to(lb, (m, B)), np.broadcast_to(ub, (m, B))
+    bad = ~(lb <= ub)
+    if bad.any():
+        b, i = min(zip(*np.nonzero(bad.T)))
+        raise ValueError("l <= u does not hold in member %d, row %d" % (b, i))
+    moved = _rho_classes(lb, ub) != _rho_classes(kl, ku)[:, None]
+    if moved.any():
+        b, i = min(zip(*np.nonzero(moved.T)))
+        raise ValueError("member %d, row %d is not in the rho class (equality, free, other) the row has in the kept problem; "
+                         "update() the problem to bounds of that shape first" % (b, i))
+    return Q, L, U
+
+
 class _Solver:
     """One problem on the device: the handle of kvx_admm_plan / kvx_admm_setup_dev.  D, E, c are the plan's scaling."""
 
@@ -119,6 +177,7 @@ class _Solver:
         self._h, self.c, self.snz = h, c.value, snz.value
         self.rho = None
         self.last_res = None
+        self._B = 0                                                     # members of the batch that has begun
 
     def pattern(self):
         Sp, Si = np.empty(self.n + 1, dtype=np.int64), np.empty(self.snz, dtype=np.int64)
@@ -194,6 +253,37 @@ class _Solver:
                        "kvx_admm_solution")
         return x, y
 
+    # ---- a batch on the kept factor: column-major n x B, m x B ---------------------------------------------------------------
+    def batch_begin(self, Q, L=None, U=None):
+        """B = Q.shape[1] members from unscaled Q, L, U (None: the kept vector in every column), every state zero."""
+        keep = [None if v is None else np.asfortranarray(v, dtype=np.float64) for v in (Q, L, U)]
+        self._B = int(keep[0].shape[1])
+        _lib.raise_for(_lib.lib().kvx_admm_batch_begin(self._h, self._B, *(None if v is None else pd(v) for v in keep)), "kvx_admm_batch_begin")
+
+    def batch_iterate(self, k, running):
+        """k iterations of the members with running[b] != 0, then the B x 24 residual numbers (frozen members: their last)."""
+        run = np.ascontiguousarray(running, dtype=np.int64)
+        out = np.empty((self._B, 24))
+        _lib.raise_for(_lib.lib().kvx_admm_batch_iterate(self._h, int(k), pi(run), pd(out)), "kvx_admm_batch_iterate")
+        return out
+
+    def batch_state(self):
+        """The scaled x (n x B), z, y (m x B), dx, dy."""
+        B = self._B
+        out = [np.empty((r, B), order="F") for r in (self.n, self.m, self.m, self.n, self.m)]
+        _lib.raise_for(_lib.lib().kvx_admm_batch_state(self._h, *(pd(v) for v in out)), "kvx_admm_batch_state")
+        return tuple(out)
+
+    def batch_solution(self, kinds):
+        """Per member the unscaled (x, y) of solution(kind); kind -1: zeros."""
+        kinds = np.ascontiguousarray(kinds, dtype=np.int64)
+        X, Y = np.empty((self.n, self._B), order="F"), np.empty((self.m, self._B), order="F")
+        _lib.raise_for(_lib.lib().kvx_admm_batch_solution(self._h, pi(kinds), pd(X), pd(Y)), "kvx_admm_batch_solution")
+        return X, Y
+
+    def batch_end(self):
+        _lib.raise_for(_lib.lib().kvx_admm_batch_end(self._h), "kvx_admm_batch_end")
+
     def info(self):
         out = np.zeros(8, dtype=np.int64)
         _lib.raise_for(_lib.lib().kvx_admm_info(self._h, pi(out)))
@@ -265,6 +355,32 @@ def _run(S, o):
             rho = _new_rho(res, S.rho)
             if rho > o["adaptive_rho_tolerance"] * S.rho or rho < S.rho / o["adaptive_rho_tolerance"]:
                 S.set_rho(rho)
+
+
+def _run_batch(S, o, B):
+    """The loop of _run without adaptive rho on a batch that has begun: (statuses, iterations, the B x 24 numbers of every
+    member's last check).  A member that gets a status is frozen; the loop ends when no member runs."""
+    check, max_iter = o["check_termination"], o["max_iter"]
+    running = np.ones(B, dtype=np.int64)
+    statuses, its, last = [None] * B, np.zeros(B, dtype=np.int64), np.empty((B, 24))
+    it = 0
+    while running.any():
+        nxt = max_iter
+        if check > 0:
+            nxt = min(nxt, (it // check + 1) * check)
+        res = S.batch_iterate(max(nxt - it, 0), running)
+        it = max(nxt, it)
+        checked = check > 0 and it % check == 0
+        if not (checked or it >= max_iter):
+            continue
+        for b in np.nonzero(running)[0]:
+            status = _judge(res[b], o, 1.0) if checked else None
+            if status is None and it >= max_iter:
+                status = _judge(res[b], o, 10.0)
+                status = status + " inaccurate" if status else "maximum iterations reached"
+            if status is not None:
+                statuses[b], its[b], last[b], running[b] = status, it, res[b], 0
+    return statuses, its, last
 
 
 def _solve(q, Acc, l, u, Pcc, opts, stats=None):
@@ -351,7 +467,9 @@ class Problem:
         Pcc = _lower(P, n, "incompatible dimensions") if P is not None else None
         self._o = _read_options(options, 3)
         self.info = None
+        self.batch_info = None
         self._S = None
+        self._l, self._u = l, u                                         # the current unscaled bounds: solve_batch checks against them
         _lib.require_device()
         S = _Solver(q, Acc, l, u, Pcc, self._o["scaling"])
         try:
@@ -370,8 +488,9 @@ class Problem:
         """Replace q, l, u (None: kept).  The scaling is kept; a row that changes between equality, free and the other rows
         costs one numeric refactorisation."""
         S = self._solver()
-        S.update(None if q is None else _vector(q, "q", S.n), None if l is None else _vector(l, "l", S.m),
-                 None if u is None else _vector(u, "u", S.m))
+        l, u = None if l is None else _vector(l, "l", S.m), None if u is None else _vector(u, "u", S.m)
+        S.update(None if q is None else _vector(q, "q", S.n), l, u)
+        self._l, self._u = self._l if l is None else l, self._u if u is None else u
 
     def warm_start(self, x=None, y=None):
         """The state the next solve() continues from: x (with z = Ax) and y (None: kept).  With 'warm_start' = 0 every solve()
@@ -407,6 +526,49 @@ class Problem:
             print("status: %s, %d iterations, %d factorisations, polish: %s" % (status, it, info["factorisations"],
                                                                               {1: "accepted", -1: "rejected", 0: "not run"}[info["status_polish"]]))
         return status, x, y
+
+    def solve_batch(self, Q, L=None, U=None, chunk=1024):
+        """B data sets on the kept factor: (statuses, X, Y).  Q is n x B, L and U are m x B (None: the problem's current l / u for
+        every member), dense 'd' matrices or 2-D float64 arrays.  Member b is what update(q_b, l_b, u_b), a start from
+        x = z = y = 0 and the loop of solve() with adaptive_rho = 0 at the problem's current rho give: statuses[b] in the wording
+        of solve(), columns b of X (n x B) and Y (m x B) the solution, the certificate or zeros as solve() returns them.
+
+        One rho, one factor: nothing adapts and nothing is factored (a factor a polish left stale is rebuilt once); settle rho
+        with a solve() first.  Every member must have l <= u and give every row the rho class (equality, free, other) it has in
+        the problem now, otherwise ValueError names the first (member, row) and nothing is changed.  'sigma', 'alpha', 'eps_*',
+        'check_termination', 'max_iter' and 'scaled_termination' act as in solve(); 'polish', 'warm_start' and 'adaptive_rho*'
+        are ignored.  A member stops at its own termination check and is frozen from then on; one host read per check serves
+        the whole batch.  More than `chunk` members run in passes of at most `chunk` (device memory of a pass: about ten
+        vectors of (n + m) x chunk doubles).  The problem itself -- q, l, u, state, rho, factor -- is left as it was.
+
+        `batch_info` holds per member `iterations`, `pri_res`, `dua_res`, `obj_val` (arrays of length B), and `rho`,
+        `factorisations`."""
+        S, o = self._solver(), self._o
+        chunk = int(chunk)
+        if not 1 <= chunk <= 65535:
+            raise ValueError("chunk must be between 1 and 65535")
+        Q, L, U = _check_batch(Q, L, U, S.n, S.m, S.E, self._l, self._u)
+        B = Q.shape[1]
+        statuses = [None] * B
+        X, Y = np.empty((S.n, B), order="F"), np.empty((S.m, B), order="F")
+        its, res = np.zeros(B, dtype=np.int64), np.empty((B, 24))
+        try:
+            for b0 in range(0, B, chunk):
+                b1 = min(B, b0 + chunk)
+                S.batch_begin(Q[:, b0:b1], None if L is None else L[:, b0:b1], None if U is None else U[:, b0:b1])
+                st, its[b0:b1], res[b0:b1] = _run_batch(S, o, b1 - b0)
+                statuses[b0:b1] = st
+                kinds = [0 if t.startswith("solved") else 1 if t.startswith("primal infeasible") else 2 if t.startswith("dual infeasible") else -1
+                         for t in st]
+                X[:, b0:b1], Y[:, b0:b1] = S.batch_solution(kinds)
+        finally:
+            S.batch_end()
+        k = 0 if o["scaled_termination"] else 7
+        self.batch_info = {"iterations": its, "pri_res": res[:, k].copy(), "dua_res": res[:, k + 3].copy(),
+                           "obj_val": (0.5 * res[:, 22] + res[:, 23]) / S.c, "rho": S.rho, "factorisations": S.info()["factorisations"]}
+        if o["verbose"]:
+            print("batch of %d: %d solved, %d to %d iterations, rho %.2e" % (B, sum(t == "solved" for t in statuses), its.min(), its.max(), S.rho))
+        return statuses, X, Y
 
     def close(self):
         if self._S is not None:
