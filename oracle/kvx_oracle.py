@@ -261,7 +261,7 @@ def compute_scaling_q(s, z):
     dd = 2 * cc + s[0] / aa + z[0] / bb
     lm[1:] = (cc + z[0] / bb) / dd / aa * s[1:] + (cc + s[0] / aa) / dd / bb * z[1:]
     lm *= np.sqrt(aa * bb)
-    return v, float(beta), lm
+    return v, beta, lm
 
 
 def scale_q(x, v, beta, inverse="N"):
@@ -287,7 +287,75 @@ def sprod_q(x, y):
 
 def max_step_q(x):
     """misc_solvers.c:1073-1085 for one cone: |x1| - x0."""
-    return float(np.linalg.norm(x[1:]) - x[0])
+    return np.linalg.norm(x[1:]) - x[0]
+
+
+def update_scaling_q(v, beta, s, z):
+    """misc.py:467-580 for one cone: v, beta of the current scaling and the new iterates s, z in that scaling; returns s / a,
+    z / b (what the reference leaves in s and z), the new v and beta, and lmbda."""
+    aa, bb = _jnrm2(s), _jnrm2(z)
+    s = s * (1.0 / aa)
+    z = z * (1.0 / bb)
+    cc = np.sqrt((1.0 + np.dot(s, z)) / 2.0)
+    vs = np.dot(v, s)
+    vz = v[0] * z[0] - np.dot(v[1:], z[1:])
+    vq = (vs + vz) / 2.0 / cc
+    vu = vs - vz
+    wk0 = 2 * v[0] * vq - (s[0] + z[0]) / 2.0 / cc
+    dd = (v[0] * vu - s[0] / 2.0 + z[0] / 2.0) / (wk0 + 1.0)
+    lm = np.empty_like(s)
+    lm[0] = cc
+    lm[1:] = v[1:] * (2.0 * (-dd * vq + 0.5 * vu))
+    lm[1:] += (0.5 * (1.0 - dd / cc)) * s[1:]
+    lm[1:] += (0.5 * (1.0 + dd / cc)) * z[1:]
+    lm *= np.sqrt(aa * bb)
+    w = v * (2.0 * vq)
+    w[0] -= s[0] / 2.0 / cc
+    w[1:] += (0.5 / cc) * s[1:]
+    w += (-0.5 / cc) * z
+    w[0] += 1.0
+    w *= 1.0 / np.sqrt(2.0 * w[0])
+    return s, z, w, beta * np.sqrt(aa / bb), lm
+
+
+def scale2_q(lm, x, inverse="N"):
+    """misc_solvers.c:301-341 for one cone: with a = sqrt(lm' J lm), l = lm / a, x := (1/a) [l' J x; x1 - (x0 + l' J x) /
+    (l0 + 1) l1] ('N') or a [l' x; x1 + (x0 + l' x) / (l0 + 1) l1] ('I')."""
+    a = np.linalg.norm(lm[1:])
+    a = np.sqrt(lm[0] + a) * np.sqrt(lm[0] - a)
+    if inverse == "N":
+        lx = (lm[0] * x[0] - np.dot(lm[1:], x[1:])) / a
+    else:
+        lx = np.dot(lm, x) / a
+    out = x.copy()
+    out[0] = lx
+    b = (x[0] + lx) / (lm[0] / a + 1.0) / a
+    if inverse == "N":
+        b *= -1.0
+    out[1:] += b * lm[1:]
+    if inverse == "N":
+        a = 1.0 / a
+    return out * a
+
+
+def sinv_q(x, y):
+    """misc_solvers.c:803-835 for one cone: with y = (l0, l1) and a = l0^2 - l1' l1, (1/a) [l0, -l1'; -l1, (a I + l1 l1') / l0] x."""
+    a = np.linalg.norm(y[1:])
+    a = (y[0] + a) * (y[0] - a)
+    c = x[0]
+    d = np.dot(x[1:], y[1:])
+    out = x.copy()
+    out[0] = c * y[0] - d
+    out[1:] *= a / y[0]
+    out[1:] += (d / y[0] - c) * y[1:]
+    return out * (1.0 / a)
+
+
+def ssqr_q(y):
+    """misc.py:951-959 for one cone: (y o y)_0 = |y|^2, (y o y)_1 = 2 y0 y1."""
+    out = y * (2.0 * y[0])
+    out[0] = np.linalg.norm(y) ** 2
+    return out
 
 
 # --- semidefinite ('s') blocks, one block at a time (m x m numpy matrices) --------------
@@ -339,7 +407,7 @@ def sinv_s(X, y):
 
 def sdot_s(X, Y):
     """misc_solvers.c:1029-1046 for one block: trace inner product of the symmetric matrices in the lower triangles."""
-    return float(np.sum(np.diag(X) * np.diag(Y)) + 2.0 * np.sum(np.tril(X, -1) * np.tril(Y, -1)))
+    return np.sum(np.diag(X) * np.diag(Y)) + 2.0 * np.sum(np.tril(X, -1) * np.tril(Y, -1))
 
 
 def max_step_s(X):
@@ -359,6 +427,49 @@ def pack_s(X):
         col[0] /= np.sqrt(2.0)
         out.append(col)
     return np.concatenate(out) * np.sqrt(2.0)
+
+
+def unpack_s(p, Y):
+    """misc_solvers.c:552-601 for one block: the packed lower triangle p (by columns) goes into the lower triangle of the m x m
+    matrix Y, off-diagonal entries times the rounded 1 / sqrt(2); the strict upper triangle of Y is returned unchanged."""
+    m = Y.shape[0]
+    out, a, ip = Y.copy(), 1.0 / np.sqrt(2.0), 0
+    for k in range(m):
+        out[k:, k] = p[ip:ip + m - k]
+        out[k + 1:, k] *= a
+        ip += m - k
+    return out
+
+
+def pack2_s(X):
+    """misc_solvers.c:476-541 for one block and one column: the lower triangle by columns, off-diagonal entries times sqrt(2),
+    the diagonal copied as it is."""
+    m = X.shape[0]
+    out = []
+    for k in range(m):
+        col = X[k:, k].copy()
+        col[1:] *= np.sqrt(2.0)
+        out.append(col)
+    return np.concatenate(out)
+
+
+def trisc_s(X):
+    """misc_solvers.c:887-932 for one block: the strict upper triangle set to zero, the strict lower triangle times 2."""
+    out = np.tril(X)
+    out[np.tril_indices_from(out, -1)] *= 2.0
+    return out
+
+
+def triusc_s(X):
+    """misc_solvers.c:940-984 for one block: the strict lower triangle times 0.5."""
+    out = X.copy()
+    out[np.tril_indices_from(out, -1)] *= 0.5
+    return out
+
+
+def symm_s(X):
+    """misc_solvers.c:610-625 for one block: the strict upper triangle becomes the mirror image of the strict lower one."""
+    return np.tril(X) + np.tril(X, -1).T
 
 
 class OracleKLU:

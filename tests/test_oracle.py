@@ -233,6 +233,17 @@ def test_cone_block_restatements_against_the_reference_goldens():
                     got = orc.scale_q(g[tag + "_X"][ind:ind + m, c], v, beta, inv)
                     assert rel(got, g["%s_scale_N%s" % (tag, inv)][ind:ind + m, c]) < 1e-12
             assert rel(orc.sprod_q(g[tag + "_x1"][ind:ind + m], g[tag + "_y1"][ind:ind + m]), g[tag + "_sprod"][ind:ind + m]) < 1e-12
+            x1, y1, lmk = g[tag + "_x1"][ind:ind + m], g[tag + "_y1"][ind:ind + m], g[tag + "_lmbda"][ind:ind + m]
+            assert rel(orc.scale2_q(lmk, x1, "N"), g[tag + "_scale2_N"][ind:ind + m]) < 1e-12
+            assert rel(orc.scale2_q(lmk, x1, "I"), g[tag + "_scale2_I"][ind:ind + m]) < 1e-12
+            assert rel(orc.sinv_q(x1, y1), g[tag + "_sinv"][ind:ind + m]) < 1e-12
+            assert rel(orc.ssqr_q(y1), g[tag + "_ssqr"][ind:ind + m]) < 1e-12
+            # update_scaling from the reference's own v, beta: s / a, z / b, the new v and beta, lmbda
+            us = orc.update_scaling_q(g[tag + "_v"][iv:iv + m], g[tag + "_beta"][bidx], g[tag + "_us_s_in"][ind:ind + m],
+                                      g[tag + "_us_z_in"][ind:ind + m])
+            for got, name, lo in zip(us, ("us_s", "us_z", "us_v", "us_beta", "us_lmbda"), (ind, ind, iv, None, ind)):
+                want = g[tag + "_" + name][bidx] if lo is None else g[tag + "_" + name][lo:lo + m]
+                assert rel(got, want) < 1e-12, name
             ind += m
             iv += m
     # --- 's' (G16): dims = {'l': 3, 'q': [4], 's': [3, 1, 6]}
@@ -272,6 +283,21 @@ def test_cone_block_restatements_against_the_reference_goldens():
         assert abs(max(tmax, tq, float(np.max(-x1[:k + 3]))) - float(g[tag + "_max_step"])) < 1e-12
         packed = np.concatenate([orc.pack_s(B) for B in X1])
         assert np.array_equal(packed, g[tag + "_pack"][2 + nlq:2 + nlq + packed.size])
+        # the other storage helpers, bit for bit: unpack (of the reference's pack, into a vector of 7.0 at offset 1), pack2 on
+        # the columns (x1, y1), trisc / triusc of x1 and symm of its block of order 6
+        ip = 0
+        for i, m in enumerate(sd):
+            npk = m * (m + 1) // 2
+            want = _blocks(g[tag + "_unpack"], 1 + nlq, sd)[i]
+            assert np.array_equal(orc.unpack_s(g[tag + "_pack"][2 + nlq + ip:2 + nlq + ip + npk], np.full((m, m), 7.0)), want)
+            for c, B in enumerate((X1[i], Y1[i])):
+                assert np.array_equal(orc.pack2_s(B), g[tag + "_pack2"][nlq + ip:nlq + ip + npk, c])
+            if tag == "a":
+                assert np.array_equal(orc.trisc_s(X1[i]), _blocks(g["a_trisc"], nlq, sd)[i])
+                assert np.array_equal(orc.triusc_s(X1[i]), _blocks(g["a_triusc"], nlq, sd)[i])
+                want = _blocks(g["a_symm"], nlq, sd)[i]
+                assert np.array_equal(orc.symm_s(X1[i]) if m == 6 else X1[i], want)
+            ip += npk
         # update_scaling: lambda and the new scaling point through r r', rti rti'
         Ls, Lz = _blocks(g[tag + "_us_s_in"], nlq, sd), _blocks(g[tag + "_us_z_in"], nlq, sd)
         Rn, Tn = _blocks(g[tag + "_us_r"], 0, sd), _blocks(g[tag + "_us_rti"], 0, sd)
