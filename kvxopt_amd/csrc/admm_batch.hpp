@@ -1,5 +1,5 @@
 // Launchers of admm_batch.hip: the ADMM iteration of admm.hip for B data sets (q_b, l_b, u_b) on one scaled A, P, rho and one
-// kept factor (kvx_admm_batch_*, admm_api.cpp; DESIGN section 11, "A batch on the kept factor").
+// kept factor (kvx_admm_batch_*, admm_batch_api.cpp; DESIGN section 11, "A batch on the kept factor").
 #pragma once
 #include "admm.hpp"
 
@@ -25,7 +25,6 @@ void launch_admm_batch_scale_bound(hipStream_t st, const AdmmBatchDev &b, bool u
 // the three steps of admm.hpp for every running member; the right-hand side of a frozen member is zero
 void launch_admm_batch_rhs(hipStream_t st, const AdmmBatchDev &b);
 void launch_admm_batch_update(hipStream_t st, const AdmmBatchDev &b);
-// part: B * ADMM_NRES * admm_batch_residual_blocks(b) doubles; res: B x ADMM_NRES, member b in res[b * ADMM_NRES ...]
-int64_t admm_batch_residual_blocks(const AdmmBatchDev &b);
+// part: B * ADMM_NRES * admm_residual_blocks(b.a) doubles; res: B x ADMM_NRES, member b in res[b * ADMM_NRES ...]
 void launch_admm_batch_residuals(hipStream_t st, const AdmmBatchDev &b, double *part, double *res);
 }  // namespace kvx

@@ -88,35 +88,32 @@ def _is_sparse_d(A):
     return hasattr(A, "CCS") and getattr(A, "typecode", None) == "d"
 
 
-def _vector(v, name, rows):
-    """A dense 'd' vector of `rows` entries as a float64 array (the checks of osqp.c:393-409)."""
+def _dense(v, name, ndims, rows, cols):
+    """The entries of a dense 'd' matrix, or of a float64 array with ndim in `ndims`, of `rows` x `cols` entries (cols None: any)
+    as a flat column-major float64 array, and its size (the checks of osqp.c:393-409)."""
     if isinstance(v, _base.matrix) or (hasattr(v, "typecode") and hasattr(v, "size") and not hasattr(v, "CCS")):
         if v.typecode != "d":
             raise TypeError("%s must be a matrix with typecode 'd'" % name)
         size = tuple(v.size)
-    elif isinstance(v, np.ndarray) and v.dtype == np.float64 and v.ndim in (1, 2):
+    elif isinstance(v, np.ndarray) and v.dtype == np.float64 and v.ndim in ndims:
         size = (v.shape[0], 1 if v.ndim == 1 else v.shape[1])
     else:
         raise TypeError("%s must be a matrix with typecode 'd'" % name)
-    if size[0] != rows or size[1] != 1:
+    if size[0] != rows or (cols is not None and size[1] != cols):
         raise ValueError("incompatible dimensions")
-    return _base.flat(v).copy()
+    return _base.flat(v).copy(), size
+
+
+def _vector(v, name, rows):
+    """A dense 'd' vector of `rows` entries as a float64 array."""
+    return _dense(v, name, (1, 2), rows, 1)[0]
 
 
 def _matrix2(v, name, rows, cols=None):
     """A dense 'd' matrix of `rows` x `cols` entries (cols None: any) as a column-major float64 array, with the checks and texts
     of _vector."""
-    if isinstance(v, _base.matrix) or (hasattr(v, "typecode") and hasattr(v, "size") and not hasattr(v, "CCS")):
-        if v.typecode != "d":
-            raise TypeError("%s must be a matrix with typecode 'd'" % name)
-        size = tuple(v.size)
-    elif isinstance(v, np.ndarray) and v.dtype == np.float64 and v.ndim == 2:
-        size = v.shape
-    else:
-        raise TypeError("%s must be a matrix with typecode 'd'" % name)
-    if size[0] != rows or (cols is not None and size[1] != cols):
-        raise ValueError("incompatible dimensions")
-    return _base.flat(v).copy().reshape((int(size[0]), int(size[1])), order="F")
+    flat, size = _dense(v, name, (2,), rows, cols)
+    return flat.reshape((int(size[0]), int(size[1])), order="F")
 
 
 def _rho_classes(lb, ub):
@@ -301,10 +298,33 @@ class _Solver:
             pass
 
 
+def _measure(o):
+    """Where the seven residual numbers of the measure 'scaled_termination' selects begin in the 24 (or B x 24) numbers."""
+    return 0 if o["scaled_termination"] else 7
+
+
+def _pri_dua(res, o):
+    """The primal and the dual residual of `res` (24 numbers, or B x 24: then per member)."""
+    return res.T[_measure(o)], res.T[_measure(o) + 3]
+
+
+def _objective(res, c):
+    """The unscaled objective of `res` (24 numbers, or B x 24: then per member); c: the plan's cost scaling."""
+    return (0.5 * res.T[22] + res.T[23]) / c
+
+
+def _kind(status):
+    """What _Solver.solution returns for `status`: 0 the solution, 1 / 2 the certificate of primal / dual infeasibility, None zeros."""
+    for kind, text in enumerate(("solved", "primal infeasible", "dual infeasible")):
+        if status.startswith(text):
+            return kind
+    return None
+
+
 def _judge(res, o, mult):
     """The status the residual vector `res` gives at tolerances times `mult`, or None (termination, certificates)."""
     ea, er, epi, edi = o["eps_abs"] * mult, o["eps_rel"] * mult, o["eps_prim_inf"] * mult, o["eps_dual_inf"] * mult
-    b = 0 if o["scaled_termination"] else 7
+    b = _measure(o)
     prim = res[b] <= ea + er * max(res[b + 1], res[b + 2])
     dual = res[b + 3] <= ea + er * max(res[b + 4], res[b + 5], res[b + 6])
     if prim and dual:
@@ -324,31 +344,44 @@ def _new_rho(res, rho):
     return min(max(rho * math.sqrt(pr / (du + 1e-10)), 1e-6), 1e6)
 
 
+def _next_stop(it, o, interval):
+    """The iteration count of the host read after `it`: the next multiple of 'check_termination' or of `interval` (each when
+    not 0), 'max_iter' at the latest."""
+    nxt, check = o["max_iter"], o["check_termination"]
+    if check > 0:
+        nxt = min(nxt, (it // check + 1) * check)
+    if interval:
+        nxt = min(nxt, (it // interval + 1) * interval)
+    return nxt
+
+
+def _verdict(res, o, checked, it):
+    """The status `res` gives after `it` iterations, or None to go on.  checked: `it` is a termination check; at 'max_iter' the
+    tolerances times 10 decide between '... inaccurate' and 'maximum iterations reached'."""
+    status = _judge(res, o, 1.0) if checked else None
+    if status is None and it >= o["max_iter"]:
+        status = _judge(res, o, 10.0)
+        status = status + " inaccurate" if status else "maximum iterations reached"
+    return status
+
+
 def _run(S, o):
     """The ADMM loop on a solver that is set up: (status, iterations).  One host read per check."""
-    check, max_iter = o["check_termination"], o["max_iter"]
+    check = o["check_termination"]
     adaptive = bool(o["adaptive_rho"])
     interval = (o["adaptive_rho_interval"] or 100) if adaptive else 0
     it = 0
     if o["verbose"]:
         print("iter   objective    pri res    dua res    rho")
     while True:
-        nxt = max_iter
-        if check > 0:
-            nxt = min(nxt, (it // check + 1) * check)
-        if adaptive:
-            nxt = min(nxt, (it // interval + 1) * interval)
+        nxt = _next_stop(it, o, interval)
         res = S.iterate(max(nxt - it, 0))
         it = max(nxt, it)
         checked = check > 0 and it % check == 0
-        if checked or it >= max_iter:
+        if checked or it >= o["max_iter"]:
             if o["verbose"]:
-                b = 0 if o["scaled_termination"] else 7
-                print("%4d %12.4e  %9.2e  %9.2e  %8.2e" % (it, (0.5 * res[22] + res[23]) / S.c, res[b], res[b + 3], S.rho))
-            status = _judge(res, o, 1.0) if checked else None
-            if status is None and it >= max_iter:
-                status = _judge(res, o, 10.0)
-                status = status + " inaccurate" if status else "maximum iterations reached"
+                print("%4d %12.4e  %9.2e  %9.2e  %8.2e" % ((it, _objective(res, S.c)) + _pri_dua(res, o) + (S.rho,)))
+            status = _verdict(res, o, checked, it)
             if status is not None:
                 return status, it
         if adaptive and it % interval == 0:
@@ -360,24 +393,17 @@ def _run(S, o):
 def _run_batch(S, o, B):
     """The loop of _run without adaptive rho on a batch that has begun: (statuses, iterations, the B x 24 numbers of every
     member's last check).  A member that gets a status is frozen; the loop ends when no member runs."""
-    check, max_iter = o["check_termination"], o["max_iter"]
+    check = o["check_termination"]
     running = np.ones(B, dtype=np.int64)
     statuses, its, last = [None] * B, np.zeros(B, dtype=np.int64), np.empty((B, 24))
     it = 0
     while running.any():
-        nxt = max_iter
-        if check > 0:
-            nxt = min(nxt, (it // check + 1) * check)
+        nxt = _next_stop(it, o, 0)
         res = S.batch_iterate(max(nxt - it, 0), running)
         it = max(nxt, it)
         checked = check > 0 and it % check == 0
-        if not (checked or it >= max_iter):
-            continue
         for b in np.nonzero(running)[0]:
-            status = _judge(res[b], o, 1.0) if checked else None
-            if status is None and it >= max_iter:
-                status = _judge(res[b], o, 10.0)
-                status = status + " inaccurate" if status else "maximum iterations reached"
+            status = _verdict(res[b], o, checked, it)
             if status is not None:
                 statuses[b], its[b], last[b], running[b] = status, it, res[b], 0
     return statuses, its, last
@@ -390,14 +416,8 @@ def _solve(q, Acc, l, u, Pcc, opts, stats=None):
     try:
         S.setup(o["sigma"], o["rho"], o["alpha"])
         status, it = _run(S, o)
-        if status.startswith("solved"):
-            x, y = S.solution(0)
-        elif status.startswith("primal infeasible"):
-            x, y = S.solution(1)
-        elif status.startswith("dual infeasible"):
-            x, y = S.solution(2)
-        else:
-            x, y = np.zeros(S.n), np.zeros(S.m)
+        kind = _kind(status)
+        x, y = S.solution(kind) if kind is not None else (np.zeros(S.n), np.zeros(S.m))
         if stats is not None:
             stats.update(S.info())
             stats["rho"] = S.rho
@@ -425,8 +445,8 @@ def _lower(P, n, text):
     return lp_, Pi[keep].copy(), Px[keep].copy()
 
 
-def solve(q, A, l, u, P=None, options=None, _stats=None):
-    """minimize 0.5 x' P x + q' x  subject to  l <= A x <= u  (osqp.c:374-432): (status, x, y)."""
+def _problem_args(q, A, l, u, P):
+    """The arguments of solve() and Problem() checked in the order of osqp.c:374-432: (q, Acc, l, u, Pcc)."""
     Acc = _sparse_arg(A, "A", TypeError)
     m, n = Acc[0], Acc[1]
     if m <= 0:
@@ -437,6 +457,12 @@ def solve(q, A, l, u, P=None, options=None, _stats=None):
     u = _vector(u, "u", m)
     l = _vector(l, "l", m)
     Pcc = _lower(P, n, "incompatible dimensions") if P is not None else None
+    return q, Acc, l, u, Pcc
+
+
+def solve(q, A, l, u, P=None, options=None, _stats=None):
+    """minimize 0.5 x' P x + q' x  subject to  l <= A x <= u  (osqp.c:374-432): (status, x, y)."""
+    q, Acc, l, u, Pcc = _problem_args(q, A, l, u, P)
     return _solve(q, Acc, l, u, Pcc, options, _stats)
 
 
@@ -455,16 +481,7 @@ class Problem:
     active_lower / active_upper (None when no polish ran)."""
 
     def __init__(self, q, A, l, u, P=None, options=None):
-        Acc = _sparse_arg(A, "A", TypeError)
-        m, n = Acc[0], Acc[1]
-        if m <= 0:
-            raise ValueError("m must be a positive integer")
-        if n <= 0:
-            raise ValueError("n must be a positive integer")
-        q = _vector(q, "q", n)
-        u = _vector(u, "u", m)
-        l = _vector(l, "l", m)
-        Pcc = _lower(P, n, "incompatible dimensions") if P is not None else None
+        q, Acc, l, u, Pcc = _problem_args(q, A, l, u, P)
         self._o = _read_options(options, 3)
         self.info = None
         self.batch_info = None
@@ -505,18 +522,18 @@ class Problem:
             S.cold_start()
         status, it = _run(S, o)
         res = S.last_res
-        b = 0 if o["scaled_termination"] else 7
-        info = {"status": status, "iterations": it, "status_polish": 0, "pri_res": float(res[b]), "dua_res": float(res[b + 3]),
-                "pri_res_polish": None, "dua_res_polish": None, "obj_val": (0.5 * res[22] + res[23]) / S.c, "active_lower": None,
+        rp, rd = _pri_dua(res, o)
+        info = {"status": status, "iterations": it, "status_polish": 0, "pri_res": float(rp), "dua_res": float(rd),
+                "pri_res_polish": None, "dua_res_polish": None, "obj_val": _objective(res, S.c), "active_lower": None,
                 "active_upper": None}
-        kind = 0 if status.startswith("solved") else 1 if status.startswith("primal infeasible") else 2 if status.startswith("dual infeasible") else None
+        kind = _kind(status)
         if o["polish"] and status == "solved":
             out = S.polish(o["delta"], o["polish_refine_iter"])
             info["active_lower"], info["active_upper"], info["status_polish"] = int(out[1]), int(out[2]), -1
             if out[0] > 0:
                 hp, hd = (out[3], out[4]) if o["scaled_termination"] else (out[5], out[6])
                 info["pri_res_polish"], info["dua_res_polish"] = float(hp), float(hd)
-                if _polish_accepted(res[b], res[b + 3], hp, hd):
+                if _polish_accepted(rp, rd, hp, hd):
                     S.polish_accept()
                     info["status_polish"], info["obj_val"], kind = 1, (0.5 * out[7] + out[8]) / S.c, 3
         x, y = S.solution(kind) if kind is not None else (np.zeros(S.n), np.zeros(S.m))
@@ -558,14 +575,12 @@ class Problem:
                 S.batch_begin(Q[:, b0:b1], None if L is None else L[:, b0:b1], None if U is None else U[:, b0:b1])
                 st, its[b0:b1], res[b0:b1] = _run_batch(S, o, b1 - b0)
                 statuses[b0:b1] = st
-                kinds = [0 if t.startswith("solved") else 1 if t.startswith("primal infeasible") else 2 if t.startswith("dual infeasible") else -1
-                         for t in st]
-                X[:, b0:b1], Y[:, b0:b1] = S.batch_solution(kinds)
+                X[:, b0:b1], Y[:, b0:b1] = S.batch_solution([-1 if _kind(t) is None else _kind(t) for t in st])
         finally:
             S.batch_end()
-        k = 0 if o["scaled_termination"] else 7
-        self.batch_info = {"iterations": its, "pri_res": res[:, k].copy(), "dua_res": res[:, k + 3].copy(),
-                           "obj_val": (0.5 * res[:, 22] + res[:, 23]) / S.c, "rho": S.rho, "factorisations": S.info()["factorisations"]}
+        rp, rd = _pri_dua(res, o)
+        self.batch_info = {"iterations": its, "pri_res": rp.copy(), "dua_res": rd.copy(), "obj_val": _objective(res, S.c), "rho": S.rho,
+                           "factorisations": S.info()["factorisations"]}
         if o["verbose"]:
             print("batch of %d: %d solved, %d to %d iterations, rho %.2e" % (B, sum(t == "solved" for t in statuses), its.min(), its.max(), S.rho))
         return statuses, X, Y
