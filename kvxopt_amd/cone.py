@@ -13,22 +13,25 @@ beta, r, rti) and all work vectors stay in HBM; the host reads scalars only (inn
 `coneqp` restates the reference's `coneprog.coneqp` (coneprog.py:1440-2547) the same way, with the reduced matrix
 S = P + Gs' Gs: the plan takes the lower pattern of P (kvx_cone_plan_h) and the gather of the assembly adds its values
 (kvx_cone_assemble_h_dev).
+
+Both loops and both starting points are those of _ipm.py (`conelp_loop`, `coneqp_loop`), written once for every cone; this module
+holds the engines that own the vectors and the launches on general cones, `_ConeEngine` and `_ConeQpEngine`.  They stay apart from
+the orthant engines of lp.py: those scale with the `mul(d)` / `div(lmbda)` kernels, these with `scale` / `sinv`, and the two have not
+been shown to round alike.
 """
 import ctypes
-import math
 import time
 
 import numpy as np
 
 from . import _ipm, _lib
 from ._lib import lib, raise_for
-from .base import ccs as _ccs, lower_ccs
+from .base import ccs as _ccs, lower_ccs                        # noqa: F401  (cone._ccs, cone.lower_ccs: tools and tests)
 from .chol import Factor
 from .coneops import (Dims, WDev, compute_scaling as _compute_scaling, max_step, put_diag, scale, scale2, sdot, sinv, snrm2,
                       sprod, ssqr, step_and_update_scaling, tri)
 from .devvec import DVec, SpMatDev, SymSpMatDev
 from .lp import dense_schur
-
 
 
 class ConePlan:
@@ -184,17 +187,217 @@ class KKTConeDev:
         z.copy_from(self.u)
 
 
-_vec = _ipm.vector
-
-
 def compute_scaling(D, s, z, W, lmbda):
     if _compute_scaling(D, s, z, W, lmbda) is not None:
         raise ArithmeticError("compute_scaling: an 's' block of s or z is not positive definite")
 
 
-def check_dims(dims, h_size=None):
-    """coneprog.py:499-521: the dims checks and their TypeErrors."""
-    _ipm.check_dims(dims)
+class _ConeOps:
+    """What the starting points of _ipm ask an engine for, on a product of 'l', 'q' and 's' cones, and what the two engines below
+    have in common: the scaling W, the operators with G and A, and the end of an iteration."""
+
+    def __init__(self, kkt, pb, D):
+        self.kkt, self.D, self.W, self.n, self.p = kkt, D, WDev(D), pb.n, pb.p
+        self.Gf, self.Af = _ipm.operators(kkt.G, kkt.A if pb.p else None, (lambda t: tri(D, t.ptr, 1)) if D.tot2 else None, DVec(D.N))
+        self.hv, self.bv = DVec(D.N, pb.h), DVec(pb.p, pb.b if pb.p else None)
+        self.x, self.dx, self.rx = (DVec(pb.n) for _ in range(3))
+        self.y, self.dy, self.ry = (DVec(pb.p) for _ in range(3))
+        self.s, self.z, self.ds, self.dz, self.rz, self.ws3, self.wz3 = (DVec(D.N) for _ in range(7))
+        self.sigs, self.sigz = DVec(D.tot1), DVec(D.tot1)
+        self.lmbda, self.lmbdasq = DVec(D.Nd), DVec(D.Nd)
+        self.y.fill(0.0)
+
+    def factor_identity(self, needed):
+        if needed:
+            self.W.identity()
+            self.kkt.factor(self.W)
+
+    def start_solve(self, x, y, z):
+        self.kkt.solve(x, y, z)
+
+    def max_step(self, v):
+        return max_step(self.D, v.ptr)
+
+    def nrm2(self, v):
+        return snrm2(self.D, v.ptr)
+
+    def dot(self, u, v):
+        return sdot(self.D, u.ptr, v.ptr)
+
+    def add_e(self, v, a):
+        v.axpy(self.D.e, a)
+
+    def symm(self, v):
+        tri(self.D, v.ptr, 0)
+
+    def scaled_bounds(self, i):
+        """ds, dz scaled by lmbda (misc.scale2) and their largest steps; at the second direction also the eigenvalues and
+        eigenvectors of their 's' blocks, which step() consumes (coneprog.py:1308-1321, 2431-2456)."""
+        D, ds, dz = self.D, self.ds, self.dz
+        scale2(D, self.lmbda.ptr, ds.ptr)
+        scale2(D, self.lmbda.ptr, dz.ptr)
+        if i == 0:
+            return max_step(D, ds.ptr), max_step(D, dz.ptr)
+        return max_step(D, ds.ptr, sigma=self.sigs), max_step(D, dz.ptr, sigma=self.sigz)
+
+    def step(self, step):
+        """x, y, the scaling and lmbda after the step, s = W' lmbda and z = W^-1 lmbda (coneprog.py:1336-1431, 2459-2545);
+        returns lmbda'lmbda."""
+        D, W, s, z, lmbda = self.D, self.W, self.s, self.z, self.lmbda
+        self.x.axpy(self.dx, step)
+        self.y.axpy(self.dy, step)
+        step_and_update_scaling(D, W, lmbda, self.ds, self.dz, self.sigs, self.sigz, step)
+        put_diag(D, s, lmbda.ptr)
+        scale(D, W, s.ptr, trans="T")
+        put_diag(D, z, lmbda.ptr)
+        scale(D, W, z.ptr, inverse="I")
+        return lmbda.dot(lmbda)
+
+
+class _ConeEngine(_ConeOps):
+    """The device vectors and launches of one conelp run (the protocol of _ipm.conelp_loop), to be read top to bottom as the launch
+    order of an iteration.  The Newton systems are solved as the reference solves them (coneprog.py:578-631 res, :1130-1195 f6_no_ir,
+    :1211-1235 f6), operation by operation; the scalars (tau, kappa blocks) travel in one-element lists."""
+
+    def __init__(self, kkt, pb, D, nref, starts_given):
+        super().__init__(kkt, pb, D)
+        n, p, N = pb.n, pb.p, D.N
+        self.cv = DVec(n, pb.c)
+        self.x.fill(0.0)                                                 # coneprog.py:655-656
+        self.x1, self.hrx = DVec(n), DVec(n)
+        self.y1, self.hry = DVec(p), DVec(p)
+        self.z1, self.hrz, self.th = DVec(N), DVec(N), DVec(N)
+        w, w2 = ((DVec(n), DVec(p), DVec(N), DVec(N)) for _ in range(2))
+        self.f6 = _ipm.f6(self.f6_no_ir, self.res, nref, w, w2)
+        self.lam2 = 0.0
+        self.unfactored = starts_given                                   # no factorisation has succeeded yet (coneprog.py:1078)
+        self.rank_msg = "Rank(A) < p or Rank([G; A]) < n"
+        if p:
+            # the elimination through S^-1 needs S = G' W^-1 W^-T G itself positive definite, i.e. Rank(G) = n; the reference's QR
+            # elimination (misc.py:1244-1282) needs it on the null space of A only
+            self.rank_msg += (", or Rank(G) < n: with equality constraints this path eliminates A through S^-1, S = G' W^-1 W^-T G, "
+                              "which needs G to have full column rank")
+
+    def start_solve(self, x, y, z):
+        try:
+            self.kkt.solve(x, y, z)
+        except ArithmeticError:
+            raise ValueError(self.rank_msg)
+
+    def stats(self, tau):
+        e, D = self, self.D                                               # residuals (coneprog.py:861-896)
+        e.Af(e.y, e.hrx, alpha=-1.0, trans="T")
+        e.Gf(e.z, e.hrx, alpha=-1.0, beta=1.0, trans="T")
+        v_hrx = e.hrx.dot(e.hrx)
+        e.rx.copy_from(e.hrx)
+        e.rx.axpy(e.cv, -tau)
+        v_rx = e.rx.dot(e.rx)
+        e.Af(e.x, e.hry)
+        v_hry = e.hry.dot(e.hry)
+        e.ry.copy_from(e.hry)
+        e.ry.axpy(e.bv, -tau)
+        v_ry = e.ry.dot(e.ry)
+        e.Gf(e.x, e.hrz)
+        e.hrz.axpy(e.s)
+        v_hrz = sdot(D, e.hrz.ptr, e.hrz.ptr)
+        e.rz.fill(0.0)
+        e.rz.axpy(e.hrz)
+        e.rz.axpy(e.hv, -tau)
+        v_rz = sdot(D, e.rz.ptr, e.rz.ptr)
+        return v_hrx, v_rx, v_hry, v_ry, v_hrz, v_rz, e.cv.dot(e.x), e.bv.dot(e.y), sdot(D, e.hv.ptr, e.z.ptr), e.lam2
+
+    def scaling(self):
+        compute_scaling(self.D, self.s, self.z, self.W, self.lmbda)
+        return self.lmbda.dot(self.lmbda)
+
+    def scale(self, primal, dual):
+        if primal is not None:
+            self.x.scal(primal); self.s.scal(primal)
+            self.symm(self.s)
+        if dual is not None:
+            self.y.scal(dual); self.z.scal(dual)
+            self.symm(self.z)
+
+    def f6_no_ir(self, bx, by, bz, btau, bs, bkappa):                     # coneprog.py:1130-1195
+        e, D = self, self.D
+        by.scal(-1.0)
+        sinv(D, bs.ptr, e.lmbda.ptr)
+        bs.scal(-1.0)
+        e.ws3.copy_from(bs)
+        scale(D, e.W, e.ws3.ptr, trans="T")
+        bz.axpy(e.ws3)
+        bz.scal(-1.0)
+        e.kkt.solve(bx, by, bz)
+        bkappa[0] = -bkappa[0] / e.lmbda_g
+        btau[0] += bkappa[0] / e.dgi
+        btau[0] = e.dgi * (btau[0] + e.cv.dot(bx) + e.bv.dot(by) + sdot(D, e.th.ptr, bz.ptr)) / (1.0 + e.z1z1)
+        bx.axpy(e.x1, btau[0]); by.axpy(e.y1, btau[0]); bz.axpy(e.z1, btau[0])
+        bs.axpy(bz, -1.0)
+        bkappa[0] -= btau[0]
+
+    def res(self, ux, uy, uz, utau, us, ukappa, vx, vy, vz, vtau, vs, vkappa):   # coneprog.py:578-631
+        e, D, dg, ws3, wz3 = self, self.D, self.dg, self.ws3, self.wz3
+        e.Af(uy, vx, alpha=-1.0, beta=1.0, trans="T")
+        wz3.copy_from(uz)
+        scale(D, e.W, wz3.ptr, inverse="I")
+        e.Gf(wz3, vx, alpha=-1.0, beta=1.0, trans="T")
+        vx.axpy(e.cv, -utau[0] / dg)
+        e.Af(ux, vy, alpha=1.0, beta=1.0)
+        vy.axpy(e.bv, -utau[0] / dg)
+        e.Gf(ux, vz, alpha=1.0, beta=1.0)
+        vz.axpy(e.hv, -utau[0] / dg)
+        ws3.copy_from(us)
+        scale(D, e.W, ws3.ptr, trans="T")
+        vz.axpy(ws3)
+        vtau[0] += dg * ukappa[0] + e.cv.dot(ux) + e.bv.dot(uy) + sdot(D, e.hv.ptr, wz3.ptr)
+        ws3.copy_from(us)
+        ws3.axpy(uz)
+        sprod(D, ws3.ptr, e.lmbda.ptr, diag="D")
+        vs.axpy(ws3)
+        vkappa[0] += e.lmbda_g * (utau[0] + ukappa[0])
+
+    def direction(self, i, sigma, mu, rt, dg, dgi, lmbda_g, wkappa3):
+        e, D = self, self.D
+        e.sigma, e.mu, e.rt, e.dg, e.dgi, e.lmbda_g, e.wkappa3 = sigma, mu, rt, dg, dgi, lmbda_g, wkappa3
+        if i == 1:
+            return
+        unfactored, e.unfactored = e.unfactored, False
+        ssqr(D, e.lmbdasq.ptr, e.lmbda.ptr)
+        try:                                                              # factor, and the constant system (coneprog.py:1066-1128)
+            e.kkt.factor(e.W)
+            e.x1.copy_from(e.cv).scal(-1.0)
+            e.y1.copy_from(e.bv)
+            e.z1.copy_from(e.hv)
+            e.kkt.solve(e.x1, e.y1, e.z1)
+            e.x1.scal(dgi); e.y1.scal(dgi); e.z1.scal(dgi)
+        except ArithmeticError:
+            if unfactored:
+                raise ValueError(e.rank_msg)
+            raise
+        e.th.copy_from(e.hv)
+        scale(D, e.W, e.th.ptr, trans="T", inverse="I")
+        e.z1z1 = sdot(D, e.z1.ptr, e.z1.ptr)
+
+    def bounds(self, i):
+        e, D, sigma = self, self.D, self.sigma                            # right-hand side (coneprog.py:1250-1298), f6, ws3
+        put_diag(D, e.ds, e.lmbdasq.ptr)
+        dkappa = [e.lmbda_g ** 2]
+        if i == 1:
+            e.ds.axpy(e.ws3)
+            e.ds.axpy(D.e, -sigma * e.mu)
+            dkappa[0] += e.wkappa3 - sigma * e.mu
+        e.dx.copy_from(e.rx).scal(1.0 - sigma)
+        e.dy.copy_from(e.ry).scal(1.0 - sigma)
+        e.dz.copy_from(e.rz).scal(1.0 - sigma)
+        dtau = [(1.0 - sigma) * e.rt]
+        e.f6(e.dx, e.dy, e.dz, dtau, e.ds, dkappa)
+        if i == 0:
+            e.ws3.copy_from(e.ds)
+            sprod(D, e.ws3.ptr, e.dz.ptr)
+        return (dtau[0], dkappa[0]) + e.scaled_bounds(i)
+
+    def update(self, step, tau):
+        self.lam2 = self.step(step)
 
 
 def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualstart=None, kktsolver=None, chol_opts=None):
@@ -203,289 +406,106 @@ def conelp(c, G, h, dims, A=None, b=None, options=None, primalstart=None, dualst
     if kktsolver is not None:
         raise NotImplementedError("conelp with 'q' / 's' cones runs misc.kkt_chol on the GPU; kktsolver is not selectable")
     opt = _ipm.options(options, dims)
-    MAXITERS, ABSTOL, RELTOL, FEASTOL, REFINEMENT, show = opt.maxiters, opt.abstol, opt.reltol, opt.feastol, opt.refinement, opt.show
     pb = _ipm.problem(c, G, h, dims, A, b)
-    n, p, cdim, c_h, h_h, b_h = pb.n, pb.p, pb.cdim, pb.c, pb.h, pb.b
     _lib.require_device()
     D = Dims(pb.dims)
-    kkt = KKTConeDev(D, n, *pb.G, p, *pb.A, chol_opts)
-    vec = DVec
-    Gf, Af = _ipm.operators(kkt.G, kkt.A if p else None, (lambda t: tri(D, t.ptr, 1)) if D.tot2 else None, vec(cdim))
-    cv, hv, bv = vec(n, c_h), vec(cdim, h_h), vec(p, b_h if p else None)
-    ws3, wz3 = vec(cdim), vec(cdim)
-    W = WDev(D)
+    kkt = KKTConeDev(D, pb.n, *pb.G, pb.p, *pb.A, chol_opts)
+    e = _ConeEngine(kkt, pb, D, opt.refinement, bool(primalstart and dualstart))
+    res0 = (max(1.0, e.cv.nrm2()), max(1.0, e.bv.nrm2()), max(1.0, e.nrm2(e.hv)))
+    t_start = time.perf_counter()
+    out = _ipm.conelp_start(e, opt, primalstart, dualstart, res0)
+    if not isinstance(out, _ipm.Outcome):
+        out = _ipm.conelp_loop(e, opt, D.Nd, out, res0)
+    xs, zs = out.status != "primal infeasible", out.status != "dual infeasible"      # a certificate comes without the other half
+    return _ipm.conelp_result(
+        opt.show, out.status, e.x.get() if xs else None, e.y.get() if zs else None, e.s.get() if xs else None, e.z.get() if zs else None,
+        out.stats, e.max_step(e.s) if xs else None, e.max_step(e.z) if zs else None, out.iterations, kkt.nfactor, out.msg,
+        **{"loop seconds": time.perf_counter() - t_start})
 
-    def res(ux, uy, uz, utau, us, ukappa, vx, vy, vz, vtau, vs, vkappa, dg, lmbda_g):   # coneprog.py:578-631
-        Af(uy, vx, alpha=-1.0, beta=1.0, trans="T")
+
+class _ConeQpEngine(_ConeOps):
+    """The device vectors and launches of one coneqp run (the protocol of _ipm.coneqp_loop), to be read top to bottom as the launch
+    order of an iteration."""
+
+    def __init__(self, kkt, pb, D, nref):
+        super().__init__(kkt, pb, D)
+        n, p, N = pb.n, pb.p, D.N
+        self.P = SymSpMatDev(n, *pb.P)
+        self.qv, self.tmpx, self.dtmp = DVec(n, pb.c), DVec(n), DVec(N)
+        w, w2 = ((DVec(n), DVec(p), DVec(N), DVec(N)) for _ in range(2)) if nref else ((), ())
+        self.f4 = _ipm.f4(self.f4_no_ir, self.res, nref, w, w2)
+
+    def f4_no_ir(self, bx, by, bz, bs):                                   # coneprog.py:2288-2316
+        sinv(self.D, bs.ptr, self.lmbda.ptr)
+        self.ws3.copy_from(bs)
+        scale(self.D, self.W, self.ws3.ptr, trans="T")
+        bz.axpy(self.ws3, -1.0)
+        self.kkt.solve(bx, by, bz)
+        bs.axpy(bz, -1.0)
+
+    def res(self, ux, uy, uz, us, vx, vy, vz, vs):                        # coneprog.py:1930-1960
+        e, D, ws3, wz3 = self, self.D, self.ws3, self.wz3
+        e.P.symv(ux, vx, alpha=-1.0, beta=1.0)
+        e.Af(uy, vx, alpha=-1.0, beta=1.0, trans="T")
         wz3.copy_from(uz)
-        scale(D, W, wz3.ptr, inverse="I")
-        Gf(wz3, vx, alpha=-1.0, beta=1.0, trans="T")
-        vx.axpy(cv, -utau[0] / dg)
-        Af(ux, vy, alpha=1.0, beta=1.0)
-        vy.axpy(bv, -utau[0] / dg)
-        Gf(ux, vz, alpha=1.0, beta=1.0)
-        vz.axpy(hv, -utau[0] / dg)
+        scale(D, e.W, wz3.ptr, inverse="I")
+        e.Gf(wz3, vx, alpha=-1.0, beta=1.0, trans="T")
+        e.Af(ux, vy, alpha=-1.0, beta=1.0)
+        e.Gf(ux, vz, alpha=-1.0, beta=1.0)
         ws3.copy_from(us)
-        scale(D, W, ws3.ptr, trans="T")
-        vz.axpy(ws3)
-        vtau[0] += dg * ukappa[0] + cv.dot(ux) + bv.dot(uy) + sdot(D, hv.ptr, wz3.ptr)
+        scale(D, e.W, ws3.ptr, trans="T")
+        vz.axpy(ws3, -1.0)
         ws3.copy_from(us)
         ws3.axpy(uz)
-        sprod(D, ws3.ptr, lmbda.ptr, diag="D")
-        vs.axpy(ws3)
-        vkappa[0] += lmbda_g * (utau[0] + ukappa[0])
+        sprod(D, ws3.ptr, e.lmbda.ptr, diag="D")
+        vs.axpy(ws3, -1.0)
 
-    resx0 = max(1.0, math.sqrt(cv.dot(cv)))
-    resy0 = max(1.0, math.sqrt(bv.dot(bv)))
-    resz0 = max(1.0, snrm2(D, hv.ptr))
-    x, y = vec(n).fill(0.0), vec(p).fill(0.0)                       # coneprog.py:655-656
-    s, z = vec(cdim), vec(cdim)
-    dx, dy = vec(n), vec(p)
-    ds, dz = vec(cdim), vec(cdim)
-    t_start = time.perf_counter()
+    def stats(self):
+        # rx = Px + q + A'y + G'z, ry = Ax - b, rz = s + Gx - h  (coneprog.py:2169-2186)
+        e, x, y, z, rx, ry, rz = self, self.x, self.y, self.z, self.rx, self.ry, self.rz
+        rx.copy_from(e.qv)
+        e.P.symv(x, rx, alpha=1.0, beta=1.0)
+        e.tmpx.copy_from(rx)
+        xPq, xq = x.dot(e.tmpx), x.dot(e.qv)
+        e.Af(y, rx, beta=1.0, trans="T")
+        e.Gf(z, rx, beta=1.0, trans="T")
+        v_rx = rx.dot(rx)
+        ry.copy_from(e.bv)
+        e.Af(x, ry, alpha=1.0, beta=-1.0)
+        v_ry = ry.dot(ry)
+        rz.copy_from(e.s)
+        rz.axpy(e.hv, -1.0)
+        e.Gf(x, rz, beta=1.0)
+        v_rz = e.dot(rz, rz)
+        return xPq, xq, v_rx, v_ry, v_rz, y.dot(ry), e.dot(z, rz)
 
-    def finish(status, iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, xs=True, zs=True, ts=None, tz=None, msg=None):
-        return _ipm.conelp_result(show, status, x.get() if xs else None, y.get() if zs else None, s.get() if xs else None,
-                                  z.get() if zs else None, (gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres), ts, tz, iters,
-                                  kkt.nfactor, msg, **{"loop seconds": time.perf_counter() - t_start})
+    def scaling(self):
+        compute_scaling(self.D, self.s, self.z, self.W, self.lmbda)
 
-    rank_msg = "Rank(A) < p or Rank([G; A]) < n"
-    if p:
-        # the elimination through S^-1 needs S = G' W^-1 W^-T G itself positive definite, i.e. Rank(G) = n; the reference's QR
-        # elimination (misc.py:1244-1282) needs it on the null space of A only
-        rank_msg += (", or Rank(G) < n: with equality constraints this path eliminates A through S^-1, S = G' W^-1 W^-T G, "
-                     "which needs G to have full column rank")
-    if primalstart is None or dualstart is None:
-        W.identity()
-        try:
-            kkt.factor(W)
-        except ArithmeticError:
-            raise ValueError(rank_msg)
-    if primalstart is None:
-        x.fill(0.0)
-        dy.copy_from(bv)
-        s.copy_from(hv)
-        try:
-            kkt.solve(x, dy, s)
-        except ArithmeticError:
-            raise ValueError(rank_msg)
-        s.scal(-1.0)
-    else:
-        x.set(_vec(primalstart["x"], "primalstart['x']", n))
-        s.set(_vec(primalstart["s"], "primalstart['s']", cdim))
-    ts = max_step(D, s.ptr)
-    if ts >= 0 and primalstart:
-        raise ValueError("initial s is not positive")
-    if dualstart is None:
-        dx.copy_from(cv).scal(-1.0)
-        y.fill(0.0)
-        z.fill(0.0)
-        try:
-            kkt.solve(dx, y, z)
-        except ArithmeticError:
-            raise ValueError(rank_msg)
-    else:
-        if "y" in dualstart and p:
-            y.set(_vec(dualstart["y"], "dualstart['y']", p))
-        z.set(_vec(dualstart["z"], "dualstart['z']", cdim))
-    tz = max_step(D, z.ptr)
-    if tz >= 0 and dualstart:
-        raise ValueError("initial z is not positive")
-    nrms, nrmz = snrm2(D, s.ptr), snrm2(D, z.ptr)
+    def factor(self):
+        ssqr(self.D, self.lmbdasq.ptr, self.lmbda.ptr)
+        self.kkt.factor(self.W)
 
-    if primalstart is None and dualstart is None:
-        gap = sdot(D, s.ptr, z.ptr)
-        pcost = cv.dot(x)
-        dcost = -bv.dot(y) - sdot(D, hv.ptr, z.ptr)
-        relgap = _ipm.relgap(gap, pcost, dcost)
-        if ts <= 0 and tz <= 0 and (gap <= ABSTOL or (relgap is not None and relgap <= RELTOL)):
-            tri(D, s.ptr, 0); tri(D, z.ptr, 0)
-            rx = vec(n, c_h)
-            Af(y, rx, beta=1.0, trans="T")
-            Gf(z, rx, beta=1.0, trans="T")
-            resx = math.sqrt(rx.dot(rx))
-            ry = vec(p, b_h if p else None)
-            Af(x, ry, alpha=-1.0, beta=1.0)
-            resy = math.sqrt(ry.dot(ry))
-            rz = vec(cdim)
-            Gf(x, rz)
-            rz.axpy(s)
-            rz.axpy(hv, -1.0)
-            resz = snrm2(D, rz.ptr)
-            pres, dres = max(resy / resy0, resz / resz0), resx / resx0
-            cx, by, hz = cv.dot(x), bv.dot(y), sdot(D, hv.ptr, z.ptr)
-            return finish("optimal", 0, gap, relgap, cx, -(by + hz), pres, dres, None, None, ts=ts, tz=tz)
-        if ts >= -1e-8 * max(nrms, 1.0):
-            s.axpy(D.e, 1.0 + ts)
-        if tz >= -1e-8 * max(nrmz, 1.0):
-            z.axpy(D.e, 1.0 + tz)
-    elif primalstart is None and dualstart is not None:
-        if ts >= -1e-8 * max(nrms, 1.0):
-            s.axpy(D.e, 1.0 + ts)
-    elif primalstart is not None and dualstart is None:
-        if tz >= -1e-8 * max(nrmz, 1.0):
-            z.axpy(D.e, 1.0 + tz)
+    def direction(self, i, sigma_mu, eta, correction):
+        # ds = -lmbdasq + sigma mu e (i = 0), -lmbdasq - dsa o dza + sigma mu e (i = 1)  (coneprog.py:2376-2392)
+        e, D, ds, dz = self, self.D, self.ds, self.dz
+        ds.fill(0.0)
+        if correction and i == 1:
+            ds.axpy(e.ws3, -1.0)
+        put_diag(D, e.dtmp, e.lmbdasq.ptr)
+        ds.axpy(e.dtmp, -1.0)
+        ds.axpy(D.e, sigma_mu)
+        e.dx.fill(0.0).axpy(e.rx, -1.0 + eta)
+        e.dy.fill(0.0).axpy(e.ry, -1.0 + eta)
+        dz.fill(0.0).axpy(e.rz, -1.0 + eta)
+        e.f4(e.dx, e.dy, dz, ds)
+        dsdz = e.dot(ds, dz)
+        if correction and i == 0:                                         # ds o dz for the Mehrotra correction
+            e.ws3.copy_from(ds)
+            sprod(D, e.ws3.ptr, dz.ptr)
+        return (dsdz,) + e.scaled_bounds(i)
 
-    tau, kappa = 1.0, 1.0
-    rx, hrx = vec(n), vec(n)
-    ry, hry = vec(p), vec(p)
-    rz, hrz = vec(cdim), vec(cdim)
-    sigs, sigz = vec(D.tot1), vec(D.tot1)
-    lmbda, lmbdasq = vec(D.Nd), vec(D.Nd)
-    lmbda_g = 0.0
-    x1, y1, z1 = vec(n), vec(p), vec(cdim)
-    th = vec(cdim)
-    wx, wy, wz, ws = vec(n), vec(p), vec(cdim), vec(cdim)
-    wx2, wy2, wz2, ws2 = vec(n), vec(p), vec(cdim), vec(cdim)
-    gap = sdot(D, s.ptr, z.ptr)
-    dg = dgi = 1.0
-    ind = D.ind
-    st = np.zeros(1, dtype=np.int32)
-
-    for iters in range(MAXITERS + 1):
-        # residuals (coneprog.py:861-896)
-        Af(y, hrx, alpha=-1.0, trans="T")
-        Gf(z, hrx, alpha=-1.0, beta=1.0, trans="T")
-        hresx = math.sqrt(hrx.dot(hrx))
-        rx.copy_from(hrx)
-        rx.axpy(cv, -tau)
-        resx = math.sqrt(rx.dot(rx)) / tau
-        Af(x, hry)
-        hresy = math.sqrt(hry.dot(hry))
-        ry.copy_from(hry)
-        ry.axpy(bv, -tau)
-        resy = math.sqrt(ry.dot(ry)) / tau
-        Gf(x, hrz)
-        hrz.axpy(s)
-        hresz = snrm2(D, hrz.ptr)
-        rz.fill(0.0)
-        rz.axpy(hrz)
-        rz.axpy(hv, -tau)
-        resz = snrm2(D, rz.ptr) / tau
-        cx, by, hz = cv.dot(x), bv.dot(y), sdot(D, hv.ptr, z.ptr)
-        rt = kappa + cx + by + hz
-        pcost, dcost = cx / tau, -(by + hz) / tau
-        relgap = _ipm.relgap(gap, pcost, dcost)
-        pres = max(resy / resy0, resz / resz0)
-        dres = resx / resx0
-        pinfres = hresx / resx0 / (-hz - by) if hz + by < 0.0 else None
-        dinfres = max(hresy / resy0, hresz / resz0) / (-cx) if cx < 0.0 else None
-        if show:
-            _ipm.progress(iters, pcost, dcost, gap, pres, dres, kappa / tau)
-
-        if (pres <= FEASTOL and dres <= FEASTOL and (gap <= ABSTOL or (relgap is not None and relgap <= RELTOL))) or iters == MAXITERS:
-            x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
-            tri(D, s.ptr, 0); tri(D, z.ptr, 0)
-            ts, tz = max_step(D, s.ptr), max_step(D, z.ptr)
-            if iters == MAXITERS:
-                return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, ts=ts, tz=tz,
-                              msg=_ipm.MAXITERS_MSG)
-            return finish("optimal", iters, gap, relgap, pcost, dcost, pres, dres, None, None, ts=ts, tz=tz)
-        elif pinfres is not None and pinfres <= FEASTOL:
-            y.scal(1.0 / (-hz - by)); z.scal(1.0 / (-hz - by))
-            tri(D, z.ptr, 0)
-            tz = max_step(D, z.ptr)
-            return finish("primal infeasible", iters, None, None, None, 1.0, None, None, pinfres, None, xs=False, tz=tz)
-        elif dinfres is not None and dinfres <= FEASTOL:
-            x.scal(1.0 / (-cx)); s.scal(1.0 / (-cx))
-            tri(D, s.ptr, 0)
-            ts = max_step(D, s.ptr)
-            return finish("dual infeasible", iters, None, None, -1.0, None, None, None, None, dinfres, zs=False, ts=ts)
-
-        if iters == 0:
-            compute_scaling(D, s, z, W, lmbda)
-            dg = math.sqrt(kappa / tau)
-            dgi = math.sqrt(tau / kappa)
-            lmbda_g = math.sqrt(tau * kappa)
-
-        ssqr(D, lmbdasq.ptr, lmbda.ptr)
-        lmbdasq_g = lmbda_g ** 2
-
-        try:
-            kkt.factor(W)
-            x1.copy_from(cv).scal(-1.0)
-            y1.copy_from(bv)
-            z1.copy_from(hv)
-            kkt.solve(x1, y1, z1)
-            x1.scal(dgi); y1.scal(dgi); z1.scal(dgi)
-        except ArithmeticError:
-            if iters == 0 and primalstart and dualstart:
-                raise ValueError(rank_msg)
-            x.scal(1.0 / tau); y.scal(1.0 / tau); s.scal(1.0 / tau); z.scal(1.0 / tau)
-            tri(D, s.ptr, 0); tri(D, z.ptr, 0)
-            ts, tz = max_step(D, s.ptr), max_step(D, z.ptr)
-            return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres, ts=ts, tz=tz,
-                          msg=_ipm.SINGULAR_MSG)
-
-        th.copy_from(hv)
-        scale(D, W, th.ptr, trans="T", inverse="I")
-        z1z1 = sdot(D, z1.ptr, z1.ptr)
-
-        def f6_no_ir(bx, by_, bz, btau, bs, bkappa):                  # coneprog.py:1130-1195
-            by_.scal(-1.0)
-            sinv(D, bs.ptr, lmbda.ptr)
-            bs.scal(-1.0)
-            ws3.copy_from(bs)
-            scale(D, W, ws3.ptr, trans="T")
-            bz.axpy(ws3)
-            bz.scal(-1.0)
-            kkt.solve(bx, by_, bz)
-            bkappa[0] = -bkappa[0] / lmbda_g
-            btau[0] += bkappa[0] / dgi
-            btau[0] = dgi * (btau[0] + cv.dot(bx) + bv.dot(by_) + sdot(D, th.ptr, bz.ptr)) / (1.0 + z1z1)
-            bx.axpy(x1, btau[0]); by_.axpy(y1, btau[0]); bz.axpy(z1, btau[0])
-            bs.axpy(bz, -1.0)
-            bkappa[0] -= btau[0]
-
-        f6 = _ipm.f6(f6_no_ir, lambda *a: res(*a, dg, lmbda_g), REFINEMENT, (wx, wy, wz, ws), (wx2, wy2, wz2, ws2))
-
-        mu = lmbda.dot(lmbda) + 0.0
-        mu = (mu + lmbda_g ** 2) / (1 + D.Nd)                          # blas.nrm2(lmbda)**2 / (1 + cdim_diag)
-        sigma = 0.0
-        wkappa3 = 0.0
-        for i in (0, 1):
-            put_diag(D, ds, lmbdasq.ptr)                              # coneprog.py:1273-1280
-            dkappa = [lmbdasq_g]
-            if i == 1:
-                ds.axpy(ws3)
-                ds.axpy(D.e, -sigma * mu)
-                dkappa[0] += wkappa3 - sigma * mu
-            dx.copy_from(rx).scal(1.0 - sigma)
-            dy.copy_from(ry).scal(1.0 - sigma)
-            dz.copy_from(rz).scal(1.0 - sigma)
-            dtau = [(1.0 - sigma) * rt]
-            f6(dx, dy, dz, dtau, ds, dkappa)
-            if i == 0:
-                ws3.copy_from(ds)
-                sprod(D, ws3.ptr, dz.ptr)
-                wkappa3 = dtau[0] * dkappa[0]
-            scale2(D, lmbda.ptr, ds.ptr)
-            scale2(D, lmbda.ptr, dz.ptr)
-            if i == 0:
-                ts, tz = max_step(D, ds.ptr), max_step(D, dz.ptr)
-            else:
-                ts, tz = max_step(D, ds.ptr, sigma=sigs), max_step(D, dz.ptr, sigma=sigz)
-            tt = -dtau[0] / lmbda_g
-            tk = -dkappa[0] / lmbda_g
-            t = max([0.0, ts, tz, tt, tk])
-            step = _ipm.step_length(t, i)
-            if i == 0:
-                sigma = (1.0 - step) ** _ipm.EXPON
-
-        # update (coneprog.py:1336-1436)
-        x.axpy(dx, step)
-        y.axpy(dy, step)
-        step_and_update_scaling(D, W, lmbda, ds, dz, sigs, sigz, step)
-        dg *= math.sqrt(1.0 - step * tk) / math.sqrt(1.0 - step * tt)
-        dgi = 1.0 / dg
-        lmbda_g *= math.sqrt(1.0 - step * tt) * math.sqrt(1.0 - step * tk)
-        put_diag(D, s, lmbda.ptr)
-        scale(D, W, s.ptr, trans="T")
-        put_diag(D, z, lmbda.ptr)
-        scale(D, W, z.ptr, inverse="I")
-        kappa, tau = lmbda_g / dgi, lmbda_g * dgi
-        gap = (math.sqrt(lmbda.dot(lmbda)) / tau) ** 2
-    raise AssertionError("unreachable")
+    update = _ConeOps.step
 
 
 def coneqp(P, q, G, h, dims, A=None, b=None, initvals=None, options=None, chol_opts=None):
@@ -504,194 +524,15 @@ def coneqp(P, q, G, h, dims, A=None, b=None, initvals=None, options=None, chol_o
         if callable(M):
             raise ValueError("use of function valued P, G, A requires a user-provided kktsolver")
     opt = _ipm.options(options, dims, qp=True)
-    MAXITERS, ABSTOL, RELTOL, FEASTOL, REFINEMENT, show = opt.maxiters, opt.abstol, opt.reltol, opt.feastol, opt.refinement, opt.show
-    correction = opt.correction
     pb = _ipm.problem(q, G, h, dims, A, b, P, qp=True)
-    n, p, cdim, q_h, h_h, b_h = pb.n, pb.p, pb.cdim, pb.c, pb.h, pb.b
-    if cdim == 0:
+    if pb.cdim == 0:
         raise NotImplementedError("coneqp without cone constraints is not part of the general-cone path")
     _lib.require_device()
     D = Dims(pb.dims)
-    kkt = KKTConeDev(D, n, *pb.G, p, *pb.A, chol_opts, *pb.P)
-    Pd = SymSpMatDev(n, *pb.P)
-    vec = DVec
-    Gf, Af = _ipm.operators(kkt.G, kkt.A if p else None, (lambda t: tri(D, t.ptr, 1)) if D.tot2 else None, vec(cdim))
-
-    qv, hv, bv = vec(n, q_h), vec(cdim, h_h), vec(p, b_h if p else None)
-    ws3, wz3, dtmp = vec(cdim), vec(cdim), vec(cdim)
-    W = WDev(D)
-    lmbda, lmbdasq = vec(D.Nd), vec(D.Nd)
-
-    def res(ux, uy, uz, us, vx, vy, vz, vs):                          # coneprog.py:1930-1960
-        Pd.symv(ux, vx, alpha=-1.0, beta=1.0)
-        Af(uy, vx, alpha=-1.0, beta=1.0, trans="T")
-        wz3.copy_from(uz)
-        scale(D, W, wz3.ptr, inverse="I")
-        Gf(wz3, vx, alpha=-1.0, beta=1.0, trans="T")
-        Af(ux, vy, alpha=-1.0, beta=1.0)
-        Gf(ux, vz, alpha=-1.0, beta=1.0)
-        ws3.copy_from(us)
-        scale(D, W, ws3.ptr, trans="T")
-        vz.axpy(ws3, -1.0)
-        ws3.copy_from(us)
-        ws3.axpy(uz)
-        sprod(D, ws3.ptr, lmbda.ptr, diag="D")
-        vs.axpy(ws3, -1.0)
-
-    resx0 = max(1.0, math.sqrt(qv.dot(qv)))
-    resy0 = max(1.0, math.sqrt(bv.dot(bv))) if p else 1.0
-    resz0 = max(1.0, snrm2(D, hv.ptr))
-    x, y = vec(n), vec(p)
-    s, z = vec(cdim), vec(cdim)
-    y.fill(0.0)
-
-    def finish(status, iters, gap, relgap, pcost, dcost, pres, dres, msg):
-        tri(D, s.ptr, 0); tri(D, z.ptr, 0)                            # misc.symm of the 's' blocks
-        ts, tz = max_step(D, s.ptr), max_step(D, z.ptr)
-        return _ipm.coneqp_result(show, status, x.get(), y.get() if p else np.zeros(0), s.get(), z.get(),
-                                  (gap, relgap, pcost, dcost, pres, dres), ts, tz, iters, kkt.nfactor, msg)
-
-    # ---- starting point (coneprog.py:2044-2150)
-    if initvals is None:
-        W.identity()
-        try:
-            kkt.factor(W)
-        except ArithmeticError:
-            raise ValueError("Rank(A) < p or Rank([P; A; G]) < n")
-        x.copy_from(qv).scal(-1.0)
-        y.copy_from(bv)
-        z.copy_from(hv)
-        try:
-            kkt.solve(x, y, z)
-        except ArithmeticError:
-            raise ValueError("Rank(A) < p or Rank([P; G; A]) < n")
-        s.copy_from(z).scal(-1.0)
-        nrms = snrm2(D, s.ptr)
-        ts = max_step(D, s.ptr)
-        if ts >= -1e-8 * max(nrms, 1.0):
-            s.axpy(D.e, 1.0 + ts)
-        nrmz = snrm2(D, z.ptr)
-        tz = max_step(D, z.ptr)
-        if tz >= -1e-8 * max(nrmz, 1.0):
-            z.axpy(D.e, 1.0 + tz)
-    else:
-        x.set(_vec(initvals["x"], "initvals['x']", n)) if "x" in initvals else x.fill(0.0)
-        if "s" in initvals:
-            s.set(_vec(initvals["s"], "initvals['s']", cdim))
-            if max_step(D, s.ptr) >= 0:
-                raise ValueError("initial s is not positive")
-        else:
-            s.copy_from(D.e)
-        if "y" in initvals and p:
-            y.set(_vec(initvals["y"], "initvals['y']", p))
-        if "z" in initvals:
-            z.set(_vec(initvals["z"], "initvals['z']", cdim))
-            if max_step(D, z.ptr) >= 0:
-                raise ValueError("initial z is not positive")
-        else:
-            z.copy_from(D.e)
-
-    rx, ry, rz = vec(n), vec(p), vec(cdim)
-    dx, dy = vec(n), vec(p)
-    dz, ds = vec(cdim), vec(cdim)
-    sigs, sigz = vec(D.tot1), vec(D.tot1)
-    if REFINEMENT:
-        wx, wy, wz, ws = vec(n), vec(p), vec(cdim), vec(cdim)
-        wx2, wy2, wz2, ws2 = vec(n), vec(p), vec(cdim), vec(cdim)
-    tmpx = vec(n)
-    gap = sdot(D, s.ptr, z.ptr)
-
-    def f4_no_ir(bx, by_, bz, bs):                                    # coneprog.py:2288-2316
-        sinv(D, bs.ptr, lmbda.ptr)
-        ws3.copy_from(bs)
-        scale(D, W, ws3.ptr, trans="T")
-        bz.axpy(ws3, -1.0)
-        kkt.solve(bx, by_, bz)
-        bs.axpy(bz, -1.0)
-
-    f4 = _ipm.f4(f4_no_ir, res, REFINEMENT, (wx, wy, wz, ws) if REFINEMENT else (), (wx2, wy2, wz2, ws2) if REFINEMENT else ())
-
-    for iters in range(MAXITERS + 1):
-        # f0 = (1/2) x'Px + q'x, rx = Px + q + A'y + G'z, ry = Ax - b, rz = s + Gx - h  (coneprog.py:2169-2186)
-        rx.copy_from(qv)
-        Pd.symv(x, rx, alpha=1.0, beta=1.0)
-        tmpx.copy_from(rx)
-        f0 = 0.5 * (x.dot(tmpx) + x.dot(qv))
-        Af(y, rx, beta=1.0, trans="T")
-        Gf(z, rx, beta=1.0, trans="T")
-        resx = math.sqrt(rx.dot(rx))
-        ry.copy_from(bv)
-        Af(x, ry, alpha=1.0, beta=-1.0)
-        resy = math.sqrt(ry.dot(ry)) if p else 0.0
-        rz.copy_from(s)
-        rz.axpy(hv, -1.0)
-        Gf(x, rz, beta=1.0)
-        resz = snrm2(D, rz.ptr)
-        pcost = f0
-        dcost = f0 + (y.dot(ry) if p else 0.0) + sdot(D, z.ptr, rz.ptr) - gap
-        relgap = _ipm.relgap(gap, pcost, dcost)
-        pres = max(resy / resy0, resz / resz0)
-        dres = resx / resx0
-        if show:
-            _ipm.progress(iters, pcost, dcost, gap, pres, dres)
-        if (pres <= FEASTOL and dres <= FEASTOL and (gap <= ABSTOL or (relgap is not None and relgap <= RELTOL))) or iters == MAXITERS:
-            if iters == MAXITERS:
-                return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, _ipm.MAXITERS_MSG)
-            return finish("optimal", iters, gap, relgap, pcost, dcost, pres, dres, "Optimal solution found.")
-
-        if iters == 0:
-            compute_scaling(D, s, z, W, lmbda)
-        ssqr(D, lmbdasq.ptr, lmbda.ptr)
-        try:
-            kkt.factor(W)
-        except ArithmeticError:
-            if iters == 0:
-                raise ValueError("Rank(A) < p or Rank([P; A; G]) < n")
-            return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, _ipm.SINGULAR_MSG)
-
-        mu = gap / (D.ml + D.nq + D.tot1)
-        sigma, eta = 0.0, 0.0
-        for i in (0, 1):
-            # ds = -lmbdasq + sigma mu e (i = 0), -lmbdasq - dsa o dza + sigma mu e (i = 1)  (coneprog.py:2376-2392)
-            ds.fill(0.0)
-            if correction and i == 1:
-                ds.axpy(ws3, -1.0)
-            put_diag(D, dtmp, lmbdasq.ptr)
-            ds.axpy(dtmp, -1.0)
-            ds.axpy(D.e, sigma * mu)
-            dx.fill(0.0).axpy(rx, -1.0 + eta)
-            dy.fill(0.0).axpy(ry, -1.0 + eta)
-            dz.fill(0.0).axpy(rz, -1.0 + eta)
-            try:
-                f4(dx, dy, dz, ds)
-            except ArithmeticError:
-                if iters == 0:
-                    raise ValueError("Rank(A) < p or Rank([P; A; G]) < n")
-                return finish("unknown", iters, gap, relgap, pcost, dcost, pres, dres, _ipm.SINGULAR_MSG)
-            dsdz = sdot(D, ds.ptr, dz.ptr)
-            if correction and i == 0:                                 # ds o dz for the Mehrotra correction
-                ws3.copy_from(ds)
-                sprod(D, ws3.ptr, dz.ptr)
-            # step to the boundary; i = 1: also the eigen-decompositions of the 's' blocks of ds, dz (coneprog.py:2431-2456)
-            scale2(D, lmbda.ptr, ds.ptr)
-            scale2(D, lmbda.ptr, dz.ptr)
-            if i == 0:
-                ts, tz = max_step(D, ds.ptr), max_step(D, dz.ptr)
-            else:
-                ts, tz = max_step(D, ds.ptr, sigma=sigs), max_step(D, dz.ptr, sigma=sigz)
-            t = max([0.0, ts, tz])
-            step = _ipm.step_length(t, i)
-            if i == 0:
-                sigma = min(1.0, max(0.0, 1.0 - step + dsdz / gap * step ** 2)) ** _ipm.EXPON
-                eta = 0.0
-
-        # update (coneprog.py:2459-2547)
-        x.axpy(dx, step)
-        y.axpy(dy, step)
-        step_and_update_scaling(D, W, lmbda, ds, dz, sigs, sigz, step)
-        put_diag(D, s, lmbda.ptr)
-        scale(D, W, s.ptr, trans="T")
-        put_diag(D, z, lmbda.ptr)
-        scale(D, W, z.ptr, inverse="I")
-        gap = lmbda.dot(lmbda)
-    raise AssertionError("unreachable")
+    kkt = KKTConeDev(D, pb.n, *pb.G, pb.p, *pb.A, chol_opts, *pb.P)
+    e = _ConeQpEngine(kkt, pb, D, opt.refinement)
+    res0 = (max(1.0, e.qv.nrm2()), max(1.0, e.bv.nrm2()), max(1.0, e.nrm2(e.hv)))
+    out = _ipm.coneqp_loop(e, opt, D.ml + D.nq + D.tot1, _ipm.coneqp_start(e, initvals), res0)
+    e.symm(e.s); e.symm(e.z)                                              # misc.symm of the 's' blocks
+    return _ipm.coneqp_result(opt.show, out.status, e.x.get(), e.y.get() if pb.p else np.zeros(0), e.s.get(), e.z.get(), out.stats,
+                              e.max_step(e.s), e.max_step(e.z), out.iterations, kkt.nfactor, out.msg)

@@ -10,29 +10,27 @@ and 2 with G', the NT-scaling update -- all HIP kernels of libkvxhip.so.  No CPU
 (p > 0, diagonal S, sparse K = A S^{-1} A' on a fixed pattern), KKTGenEqDev (p > 0, general S, dense K in HBM); `misc.kkt_chol2` is built
 on the same classes.
 
-conelp's loop is written once, on host scalars (`_iterate`); the launches of an iteration belong to one of four engines, all with the
-same arithmetic and roundings (tests/test_kkt_gpu.py compares them bit for bit): `_CIssued`, the default for p = 0 (fused kernels, an
-iteration in four C calls); `_PythonIssued`, KVX_LP_PYCALLS=1 (the same launches, one ctypes call each); `_PerOperation`, KVX_LP_UNFUSED=1,
-p > 0 or a user's kktsolver (one launch per BLAS-1-sized operation); `_Refined`, options['refinement'] > 0 (iterative refinement of
-the Newton systems).  tests/test_lp_loop_cpu.py runs the loop on a numpy engine.
+Both loops and both starting points are written once, on host scalars, in _ipm.py (`conelp_loop`, `coneqp_loop`); this module holds the
+engines that own the vectors and the launches.  conelp has four, all with the same arithmetic and roundings (tests/test_kkt_gpu.py
+compares them bit for bit): `_CIssued`, the default for p = 0 (fused kernels, an iteration in four C calls); `_PythonIssued`,
+KVX_LP_PYCALLS=1 (the same launches, one ctypes call each); `_PerOperation`, KVX_LP_UNFUSED=1, p > 0 or a user's kktsolver (one launch
+per BLAS-1-sized operation); `_Refined`, options['refinement'] > 0 (iterative refinement of the Newton systems).  coneqp has one,
+`_QpEngine`.  cone.py holds the engines of the general cones.
 """
 import collections
 import ctypes
-import math
 import os
-import sys
 import time
 
 import numpy as np
 
 from . import _ipm, _lib, base
-from ._lib import DeviceBuffer, lib, raise_for
+from ._lib import lib, raise_for
 from .chol import Factor
 from .devvec import DVec, SpMatDev, SymSpMatDev, reduce_multi      # noqa: F401  (lp.DVec, lp.SpMatDev, ... are public names)
 
 # the schedule of conelp's iteration (module docstring); the library reads KVX_LP_UNFUSED too
 _UNFUSED = os.environ.get("KVX_LP_UNFUSED", "0") not in ("", "0")
-_TRACE = os.environ.get("KVX_LP_TRACE", "0") not in ("", "0")      # per-iteration wall times of conelp on stderr
 _PYCALLS = os.environ.get("KVX_LP_PYCALLS", "0") not in ("", "0")
 
 
@@ -568,117 +566,55 @@ def _kkt_for(kind, dims_key, patterns, chol_opts, build, refresh):
     return kkt
 
 
-# what the interior-point loop returns: stats = (gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres)
-Outcome = collections.namedtuple("Outcome", "status iterations stats msg phase_seconds")
+class _Orthant:
+    """What the starting points of _ipm ask an engine for, on the orthant: W = diag(d), e = 1, every vector a DVec."""
+    rank_msg = "Rank(A) < p or Rank([G; A]) < n"
+
+    def __init__(self, kkt, pb):
+        self.kkt, self.ml, self.n, self.p = kkt, pb.cdim, pb.n, pb.p
+        self.xz = isinstance(kkt, KKTChol2Dev)           # p = 0 on the device: its solves take (x, z)
+        self.G = kkt.G
+        self.Gf, self.Af = _ipm.operators(kkt.G, kkt.A if pb.p else None)
+        self.d, self.di = DVec(pb.cdim), DVec(pb.cdim)
+
+    def ksolve(self, x, y, z):
+        self.kkt.solve(*((x, z) if self.xz else (x, y, z)))
+
+    start_solve = ksolve
+
+    def factor_identity(self, needed):                   # (the orthant drivers factor whether or not the start needs it)
+        self.d.fill(1.0); self.di.fill(1.0)
+        self.kkt.factor(self.di)
+
+    def max_step(self, v):
+        return v.max_step()
+
+    def nrm2(self, v):
+        return v.nrm2()
+
+    def dot(self, u, v):
+        return u.dot(v)
+
+    def add_e(self, v, a):
+        v.addc(a)
+
+    def symm(self, v):
+        pass
 
 
-def _iterate(engine, opt, ml, gap, res0):
-    """The interior-point loop of conelp on the orthant (coneprog.py:859-1436) from a starting point with tau = kappa = 1 and
-    s'z = gap; res0 = (resx0, resy0, resz0).  Host scalars only: the vectors belong to `engine`, which is asked for
-      stats(tau)        the squared norms of hrx, rx, hry, ry, hrz, rz, then c'x, b'y, h'z and lmbda'lmbda
-      scaling()         the NT scaling of the first iteration; returns lmbda'lmbda
-      direction(i, ...) whatever of direction i (0: predictor, with the factorisation and the constant system; 1: corrector)
-                        can report a failed factorisation, by ArithmeticError
-      bounds(i)         the rest of direction i; returns (dtau, dkappa, max_step(ds), max_step(dz))
-      update(step, tau) the step, the new scaling, and s, z of the next iteration; tau is the new one
-      scale(a, b)       x, s *= a and y, z *= b (None: left alone)
-    and returns an Outcome; the iterates are left scaled as the reference returns them."""
-    resx0, resy0, resz0 = res0
-    tau, kappa = 1.0, 1.0
-    dg = dgi = lmbda_g = 1.0
-    phase = [0.0, 0.0, 0.0]
-    for iters in range(opt.maxiters + 1):
-        # residuals (coneprog.py:861-896): their norms and the objectives
-        v_hrx, v_rx, v_hry, v_ry, v_hrz, v_rz, cx, by, hz, lam2 = engine.stats(tau)
-        t_now = time.perf_counter()
-        if iters > 0:
-            phase[2] += t_now - t_mark
-        t_mark = t_now
-        hresx, resx = math.sqrt(v_hrx), math.sqrt(v_rx) / tau
-        hresy, resy = math.sqrt(v_hry), math.sqrt(v_ry) / tau
-        hresz, resz = math.sqrt(v_hrz), math.sqrt(v_rz) / tau
-        if iters > 0:
-            gap = (math.sqrt(lam2) / tau) ** 2           # (coneprog.py:1436; lmbda of the previous update)
-        rt = kappa + cx + by + hz
-        pcost, dcost = cx / tau, -(by + hz) / tau
-        relgap = _ipm.relgap(gap, pcost, dcost)
-        pres = max(resy / resy0, resz / resz0)
-        dres = resx / resx0
-        pinfres = hresx / resx0 / (-hz - by) if hz + by < 0.0 else None
-        dinfres = max(hresy / resy0, hresz / resz0) / (-cx) if cx < 0.0 else None
-        if opt.show:
-            _ipm.progress(iters, pcost, dcost, gap, pres, dres, kappa / tau)
-
-        if (pres <= opt.feastol and dres <= opt.feastol and (gap <= opt.abstol or (relgap is not None and relgap <= opt.reltol))) \
-                or iters == opt.maxiters:
-            engine.scale(1.0 / tau, 1.0 / tau)
-            if iters == opt.maxiters:
-                return Outcome("unknown", iters, (gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres), _ipm.MAXITERS_MSG, phase)
-            return Outcome("optimal", iters, (gap, relgap, pcost, dcost, pres, dres, None, None), None, phase)
-        elif pinfres is not None and pinfres <= opt.feastol:
-            engine.scale(None, 1.0 / (-hz - by))
-            return Outcome("primal infeasible", iters, (None, None, None, 1.0, None, None, pinfres, None), None, phase)
-        elif dinfres is not None and dinfres <= opt.feastol:
-            engine.scale(1.0 / (-cx), None)
-            return Outcome("dual infeasible", iters, (None, None, -1.0, None, None, None, None, dinfres), None, phase)
-
-        # NT scaling at the first iteration (coneprog.py:1031-1043 -> misc.py:284-287)
-        if iters == 0:
-            lam2 = engine.scaling()
-            dg = math.sqrt(kappa / tau)
-            dgi = math.sqrt(tau / kappa)
-            lmbda_g = math.sqrt(tau * kappa)
-        mu = (lam2 + lmbda_g ** 2) / (1 + ml)
-        sigma = wkappa3 = 0.0
-        for i in (0, 1):
-            try:
-                engine.direction(i, sigma, mu, rt, dgi, lmbda_g, wkappa3)
-            except ArithmeticError:
-                engine.scale(1.0 / tau, 1.0 / tau)
-                return Outcome("unknown", iters, (gap, relgap, pcost, dcost, pres, dres, pinfres, dinfres), _ipm.SINGULAR_MSG, phase)
-            dtau, dkappa, ts, tz = engine.bounds(i)
-            t_now = time.perf_counter()
-            phase[i] += t_now - t_mark
-            if _TRACE:
-                print("conelp iteration %d direction %d: %.0f us" % (iters, i, 1e6 * (t_now - t_mark)), file=sys.stderr)
-            t_mark = t_now
-            if i == 0:
-                wkappa3 = dtau * dkappa
-            # step to the boundary (coneprog.py:1314-1331)
-            tt, tk = -dtau / lmbda_g, -dkappa / lmbda_g
-            step = _ipm.step_length(max(0.0, ts, tz, tt, tk), i)
-            if i == 0:
-                sigma = (1.0 - step) ** _ipm.EXPON
-
-        # update (coneprog.py:1336-1436)
-        dg *= math.sqrt(1.0 - step * tk) / math.sqrt(1.0 - step * tt)
-        dgi = 1.0 / dg
-        lmbda_g *= math.sqrt(1.0 - step * tt) * math.sqrt(1.0 - step * tk)
-        kappa, tau = lmbda_g / dgi, lmbda_g * dgi
-        engine.update(step, tau)
-    raise AssertionError("unreachable")
-
-
-class _Engine:
+class _Engine(_Orthant):
     """The device vectors of one conelp run and what the schedules below have in common.  Each schedule is one subclass, to be read
     top to bottom as its launch order; all four do the same arithmetic with the same roundings."""
 
     def __init__(self, kkt, pb):
+        super().__init__(kkt, pb)
         ml, n, p = pb.cdim, pb.n, pb.p
-        self.kkt, self.ml, self.n, self.p = kkt, ml, n, p
-        self.xz = isinstance(kkt, KKTChol2Dev)           # p = 0 on the device: its solves take (x, z)
-        self.G = kkt.G
-        self.Af = _ipm.operators(kkt.G, kkt.A if p else None)[1]
         self.cv, self.hv = DVec(n, pb.c), DVec(ml, pb.h)
         self.x, self.dx, self.x1, self.rx, self.hrx = (DVec(n) for _ in range(5))
         self.bv = DVec(p, pb.b) if p else _ipm.NoVec()   # p = 0: the y-blocks of the algorithm are empty
         self.y, self.dy, self.y1, self.ry, self.hry = (DVec(p) for _ in range(5)) if p else [self.bv] * 5
         self.s, self.z, self.ds, self.dz, self.z1, self.rz, self.hrz, self.th, self.ws3, self.lmbda = (DVec(ml) for _ in range(10))
-        self.d, self.di = DVec(ml), DVec(ml)
         self.out4 = (ctypes.c_double * 4)()              # dtau, z1'z1, max_step(ds), max_step(dz) of the last direction
-
-    def ksolve(self, x, y, z):
-        self.kkt.solve(*((x, z) if self.xz else (x, y, z)))
 
     def reduce(self):
         e = self
@@ -695,7 +631,7 @@ class _Engine:
         if dual is not None:
             self.y.scal(dual); self.z.scal(dual)
 
-    def begin(self, i, sigma, mu, rt, dgi, lmbda_g, wkappa3):
+    def begin(self, i, sigma, mu, rt, dg, dgi, lmbda_g, wkappa3):
         """The tau and kappa entries of the right-hand side of direction i (coneprog.py:1250-1298), the same after the first half of
         f6_no_ir (:1130-1160), and the scalars its launches take."""
         self.sigma, self.smu, self.dgi, self.lmbda_g = sigma, (sigma * mu if i == 1 else 0.0), dgi, lmbda_g
@@ -879,7 +815,7 @@ class _Refined(_PerOperation):
         bkappa[0] -= btau[0]
 
     def res(self, ux, uy, uz, utau, us, ukappa, vx, vy, vz, vtau, vs, vkappa):
-        e, dg = self, 1.0 / self.dgi
+        e, dg = self, 1.0 / self.dgi                     # (not the loop's dg: the rounding this engine has always had)
         e.Af(uy, vx, trans="T", alpha=-1.0, beta=1.0)
         e.rz3.copy_from(uz).mul(e.di)                    # W^{-1} uz
         e.G.gemv(e.rz3, vx, trans="T", alpha=-1.0, beta=1.0)
@@ -921,61 +857,6 @@ class _Refined(_PerOperation):
         return dtau[0], dkappa[0], e.ds.max_step(), e.dz.max_step()
 
 
-def _start(e, opt, primalstart, dualstart, res0):
-    """The starting point (coneprog.py:662-842) in the vectors of engine `e`: the KKT system with W = I, or what the caller gives.
-    Returns s'z, or the Outcome if the computed point is optimal already."""
-    x, y, s, z, cv, bv, hv, Af = e.x, e.y, e.s, e.z, e.cv, e.bv, e.hv, e.Af
-    e.d.fill(1.0); e.di.fill(1.0)
-    try:
-        e.kkt.factor(e.di)
-    except ArithmeticError:
-        raise ValueError("Rank(A) < p or Rank([G; A]) < n")
-    if primalstart is None:
-        x.fill(0.0); e.dy.copy_from(bv); s.copy_from(hv)
-        e.ksolve(x, e.dy, s)
-        s.scal(-1.0)
-    else:                                                        # coneprog.py:703-705
-        x.set(_ipm.vector(primalstart["x"], "primalstart['x']", e.n)); s.set(_ipm.vector(primalstart["s"], "primalstart['s']", e.ml))
-    ts = s.max_step()
-    if ts >= 0 and primalstart is not None:
-        raise ValueError("initial s is not positive")
-    if dualstart is None:
-        e.dx.copy_from(cv).scal(-1.0); y.fill(0.0); z.fill(0.0)
-        e.ksolve(e.dx, y, z)
-    else:                                                        # coneprog.py:731-733
-        if e.p and "y" in dualstart:
-            y.set(_ipm.vector(dualstart["y"], "dualstart['y']", e.p))
-        elif e.p:
-            y.fill(0.0)
-        z.set(_ipm.vector(dualstart["z"], "dualstart['z']", e.ml))
-    tz = z.max_step()
-    if tz >= 0 and dualstart is not None:
-        raise ValueError("initial z is not positive")
-    nrms, nrmz = s.nrm2(), z.nrm2()
-    if primalstart is None and dualstart is None:
-        gap = s.dot(z)
-        pcost = cv.dot(x)
-        dcost = -bv.dot(y) - hv.dot(z)
-        relgap = _ipm.relgap(gap, pcost, dcost)
-        if ts <= 0 and tz <= 0 and (gap <= opt.abstol or (relgap is not None and relgap <= opt.reltol)):
-            rx, ry, rz = e.rx, e.ry, e.rz
-            rx.copy_from(cv); Af(y, rx, trans="T", alpha=1.0, beta=1.0); e.G.gemv(z, rx, trans="T", alpha=1.0, beta=1.0)
-            resx = rx.nrm2()
-            ry.copy_from(bv); Af(x, ry, trans="N", alpha=1.0, beta=-1.0)
-            resy = ry.nrm2()
-            e.G.gemv(x, rz, trans="N"); rz.axpy(s); rz.axpy(hv, -1.0)
-            resz = rz.nrm2()
-            return Outcome("optimal", 0, (gap, relgap, pcost, dcost, max(resy / res0[1], resz / res0[2]), resx / res0[0], None, None),
-                           None, [0.0, 0.0, 0.0])
-    # (coneprog.py:806-842: a computed start is pushed into the cone, a given one is taken as it is)
-    if primalstart is None and ts >= -1e-8 * max(nrms, 1.0):
-        s.addc(1.0 + ts)
-    if dualstart is None and tz >= -1e-8 * max(nrmz, 1.0):
-        z.addc(1.0 + tz)
-    e.lmbda.fill(0.0)
-    return s.dot(z)
-
-
 def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, primalstart=None, dualstart=None, kktsolver=None):
     """Solve the LP  minimize c'x  s.t.  Gx <= h, Ax = b  on the GPU.  c: (n,), h: (ml,), G: spmatrix-like
     (ml x n, sparse); A (p x n, sparse), b (p,) optional -- with equality constraints either G has at most one entry per
@@ -1012,10 +893,10 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
         engine = (_PythonIssued if _PYCALLS else _CIssued)(kkt, pb)
     res0 = (max(1.0, engine.cv.nrm2()), max(1.0, engine.bv.nrm2()), max(1.0, engine.hv.nrm2()))
 
-    out, t_loop = _start(engine, opt, primalstart, dualstart, res0), time.perf_counter()
-    looped = not isinstance(out, Outcome)
+    out, t_loop = _ipm.conelp_start(engine, opt, primalstart, dualstart, res0), time.perf_counter()
+    looped = not isinstance(out, _ipm.Outcome)
     if looped:
-        out = _iterate(engine, opt, ml, out, res0)
+        out = _ipm.conelp_loop(engine, opt, ml, out, res0)
     e, xs, zs = engine, out.status != "primal infeasible", out.status != "dual infeasible"      # a certificate comes without the other half
     return _ipm.conelp_result(
         opt.show, out.status, e.x.get() if xs else None, e.y.get() if zs else None, e.s.get() if xs else None, e.z.get() if zs else None,
@@ -1026,15 +907,110 @@ def conelp(c, G, h, dims=None, A=None, b=None, options=None, chol_opts=None, pri
             "phase seconds": list(out.phase_seconds)})
 
 
+class _QpEngine(_Orthant):
+    """The device vectors and launches of one coneqp run (the protocol of _ipm.coneqp_loop), for p = 0 and p > 0 and any of
+    KKTChol2Dev, KKTGenEqDev and KKTUserHost; to be read top to bottom as the launch order of an iteration."""
+
+    def __init__(self, kkt, pb, nref):
+        super().__init__(kkt, pb)
+        ml, n, p = pb.cdim, pb.n, pb.p
+        self.P = SymSpMatDev(n, *pb.P)
+        self.qv, self.hv = DVec(n, pb.c), DVec(ml, pb.h)
+        self.bv = DVec(p, pb.b) if p else _ipm.NoVec()   # p = 0: the y-blocks of the algorithm are empty
+        self.y, self.dy, self.ry = (DVec(p) for _ in range(3)) if p else [self.bv] * 3
+        self.x, self.dx, self.rx, self.tmpx = (DVec(n) for _ in range(4))
+        self.s, self.z, self.ds, self.dz, self.rz, self.ws3, self.tmp, self.lmbda, self.lmbdasq = (DVec(ml) for _ in range(9))
+        w, w2 = ((DVec(n), DVec(p) if p else self.y, DVec(ml), DVec(ml)) for _ in range(2)) if nref else ((), ())
+        self.f4 = _ipm.f4(self.f4_no_ir, self.res, nref, w, w2)
+
+    def start_solve(self, x, y, z):
+        self.ksolve(x, y, z)
+        if self.p:
+            self.kkt.check()
+
+    def f4_no_ir(self, bx, by, bz, bs):
+        # [P A' G'; A 0 0; G 0 -W'W][ux; uy; W^-1 uz] = [bx; by; bz - W'(lmbda o\ bs)],  us = lmbda o\ bs - uz   (coneprog.py:2283-2313)
+        bs.div(self.lmbda)
+        self.tmp.xmy(1.0, bs, self.d)
+        bz.axpy(self.tmp, -1.0)
+        self.ksolve(bx, by, bz)
+        bs.axpy(bz, -1.0)
+
+    def res(self, ux, uy, uz, us, vx, vy, vz, vs):
+        # residual of the Newton equations (coneprog.py:1929-1960)
+        e, tmp = self, self.tmp
+        e.P.symv(ux, vx, alpha=-1.0, beta=1.0)
+        e.Af(uy, vx, trans="T", alpha=-1.0, beta=1.0)
+        e.Af(ux, vy, trans="N", alpha=-1.0, beta=1.0)
+        tmp.xmy(1.0, uz, e.di)
+        e.G.gemv(tmp, vx, trans="T", alpha=-1.0, beta=1.0)
+        e.G.gemv(ux, vz, trans="N", alpha=-1.0, beta=1.0)
+        tmp.xmy(1.0, us, e.d)
+        vz.axpy(tmp, -1.0)
+        tmp.lincomb(1.0, us, 1.0, uz)
+        tmp.mul(e.lmbda)
+        vs.axpy(tmp, -1.0)
+
+    def stats(self):
+        # rx = P x + q + A'y + G'z, ry = A x - b, rz = s + G x - h; ONE reduction call for the seven inner products
+        e, x, y, z, rx, ry, rz = self, self.x, self.y, self.z, self.rx, self.ry, self.rz
+        rx.copy_from(e.qv)
+        e.P.symv(x, rx, alpha=1.0, beta=1.0)
+        e.tmpx.copy_from(rx)                             # P x + q, for f0
+        e.Af(y, rx, trans="T", alpha=1.0, beta=1.0)
+        ry.copy_from(e.bv)
+        e.Af(x, ry, trans="N", alpha=1.0, beta=-1.0)
+        e.G.gemv(z, rx, trans="T", alpha=1.0, beta=1.0)
+        rz.lincomb(1.0, e.s, -1.0, e.hv)
+        e.G.gemv(x, rz, trans="N", alpha=1.0, beta=1.0)
+        xPq, xq, v_rx, v_rz, zrz, v_ry, yry = reduce_multi([("dot", x, e.tmpx), ("dot", x, e.qv), ("dot", rx, rx), ("dot", rz, rz),
+                                                             ("dot", z, rz), ("dot", ry, ry), ("dot", y, ry)])
+        return xPq, xq, v_rx, v_ry, v_rz, yry, zrz
+
+    def scaling(self):
+        raise_for(lib().kvx_nt_compute_scaling_dev(self.ml, self.s.ptr, self.z.ptr, self.d.ptr, self.di.ptr, self.lmbda.ptr))
+
+    def factor(self):
+        self.lmbdasq.sqr_of(self.lmbda)
+        self.kkt.factor(self.di)
+        if self.p:
+            self.kkt.check()
+
+    def direction(self, i, sigma_mu, eta, correction):
+        e, ds, dz = self, self.ds, self.dz               # right-hand sides (coneprog.py:2367-2390)
+        ds.fill(0.0)
+        if correction and i == 1:
+            ds.axpy(e.ws3, -1.0)
+        ds.axpy(e.lmbdasq, -1.0).addc(sigma_mu)
+        e.dx.lincomb(-1.0 + eta, e.rx)
+        e.dy.lincomb(-1.0 + eta, e.ry)
+        dz.lincomb(-1.0 + eta, e.rz)
+        e.f4(e.dx, e.dy, dz, ds)
+        dsdz = ds.dot(dz)
+        if correction and i == 0:
+            e.ws3.xmy(1.0, ds, dz)
+        ds.div(e.lmbda); dz.div(e.lmbda)                 # misc.scale2(lmbda, .) on the orthant (coneprog.py:2431-2451)
+        return (dsdz,) + tuple(reduce_multi([("max", ds), ("max", dz)]))
+
+    def update(self, step):
+        e, ds, dz = self, self.ds, self.dz               # iterates and scaling (coneprog.py:2454-2545)
+        e.x.axpy(e.dx, step)
+        e.y.axpy(e.dy, step)
+        ds.scal(step).addc(1.0); dz.scal(step).addc(1.0)
+        ds.mul(e.lmbda); dz.mul(e.lmbda)
+        raise_for(lib().kvx_nt_update_scaling_dev(e.ml, ds.ptr, dz.ptr, e.d.ptr, e.di.ptr, e.lmbda.ptr))
+        e.s.xmy(1.0, e.lmbda, e.d)
+        e.z.xmy(1.0, e.lmbda, e.di)
+        return e.lmbda.dot(e.lmbda)
+
+
 def coneqp(P, q, G, h, options=None, chol_opts=None, A=None, b=None, initvals=None, kktsolver=None):
     """Solve the convex QP  minimize (1/2) x'Px + q'x  s.t.  Gx <= h, Ax = b  on the GPU (orthant cone): the reference's coneqp (coneprog.py:1440-2547) with its default KKT solver for sparse G,
     misc.kkt_chol2 with H = P.  P: spmatrix-like, its lower triangle is used.  Returns the reference's result
     dictionary (coneprog.py:2216-2221) with numpy arrays, plus "factorizations"."""
     opt = _ipm.options(options, {}, qp=True)                                    # coneprog.py:1768-1781, 1862-1865
-    MAXITERS, ABSTOL, RELTOL, FEASTOL, refinement, show = opt.maxiters, opt.abstol, opt.reltol, opt.feastol, opt.refinement, opt.show
-    correction = opt.correction
     pb = _ipm.problem(q, G, h, None, A, b, P, qp=True)
-    n, p, ml, q_h, h_h, b_h = pb.n, pb.p, pb.cdim, pb.c, pb.h, pb.b
+    n, p, ml = pb.n, pb.p, pb.cdim
     (Gp, Gi, Gx), (Ap, Ai, Ax), (Pp, Pi, Px) = pb.G, pb.A, pb.P
     if ml == 0:
         raise ValueError("coneqp on the GPU needs at least one inequality (dims['l'] > 0)")
@@ -1052,180 +1028,8 @@ def coneqp(P, q, G, h, options=None, chol_opts=None, A=None, b=None, initvals=No
     else:
         kkt = _kkt_for("KKTChol2Dev+P", (ml, n, 0), (Gp, Gi, Pp, Pi), chol_opts,
                        lambda: KKTChol2Dev(ml, n, Gp, Gi, Gx, chol_opts, Pp, Pi, Px), lambda k: k.reset(Gx, Px))
-    if p > 0:
-        Ad = kkt.A
-        bv = DVec(p, b_h)
-        y, dy, ry = DVec(p), DVec(p), DVec(p)
-        if refinement:
-            wy, wy2 = DVec(p), DVec(p)
-        resy0 = max(1.0, bv.nrm2())
-        ksolve = kkt.solve
-    else:
-        y = dy = ry = wy = wy2 = _ipm.NoVec()
-        resy0 = 1.0
-        if kktsolver is not None:
-            ksolve = kkt.solve
-        else:
-            def ksolve(xx, yy, zz):
-                kkt.solve(xx, zz)
-    Gd, Pd = kkt.G, SymSpMatDev(n, Pp, Pi, Px)
-    qv, hv = DVec(n, q_h), DVec(ml, h_h)
-    x, dx, rx, tmpx = (DVec(n) for _ in range(4))
-    s, z, ds, dz, rz, ws3, tmp, lmbda, lmbdasq, d, di = (DVec(ml) for _ in range(11))
-    if refinement:
-        wx, wx2 = DVec(n), DVec(n)
-        wz, ws, wz2, ws2 = (DVec(ml) for _ in range(4))
-    resx0 = max(1.0, qv.nrm2())
-    resz0 = max(1.0, hv.nrm2())
-
-    def result(status, iters, gap, relgap, pcost, dcost, pres, dres, msg=None):
-        return _ipm.coneqp_result(show, status, x.get(), y.get() if p else np.zeros(0), s.get(), z.get(),
-                                  (gap, relgap, pcost, dcost, pres, dres), s.max_step(), z.max_step(), iters, kkt.nfactor, msg)
-
-    # ---- starting point (coneprog.py:2044-2150)
-    if initvals is None:
-        # factor with W = I, solve [P A' G'; A 0 0; G 0 -I][x; y; z] = [-q; b; h], s = -z, push s and z into the cone
-        d.fill(1.0); di.fill(1.0)
-        try:
-            kkt.factor(di)
-        except ArithmeticError:
-            raise ValueError("Rank(A) < p or Rank([P; A; G]) < n")
-        x.copy_from(qv).scal(-1.0)
-        if p:
-            y.copy_from(bv)
-        z.copy_from(hv)
-        try:
-            ksolve(x, y, z)
-            if p:
-                kkt.check()
-        except ArithmeticError:
-            raise ValueError("Rank(A) < p or Rank([P; G; A]) < n")
-        s.copy_from(z).scal(-1.0)
-        ts = s.max_step()
-        if ts >= -1e-8 * max(s.nrm2(), 1.0):
-            s.addc(1.0 + ts)
-        tz = z.max_step()
-        if tz >= -1e-8 * max(z.nrm2(), 1.0):
-            z.addc(1.0 + tz)
-    else:
-        # user-supplied values (coneprog.py:2108-2150): missing x, y default to 0, missing s, z to the cone's identity
-        def _vec(v, length):
-            return _ipm.vector(v, "initvals", length)
-        x.set(_vec(initvals["x"], n)) if "x" in initvals else x.fill(0.0)
-        if "s" in initvals:
-            s.set(_vec(initvals["s"], ml))
-            if s.max_step() >= 0:
-                raise ValueError("initial s is not positive")
-        else:
-            s.fill(1.0)
-        if p:
-            y.set(_vec(initvals["y"], p)) if "y" in initvals else y.fill(0.0)
-        if "z" in initvals:
-            z.set(_vec(initvals["z"], ml))
-            if z.max_step() >= 0:
-                raise ValueError("initial z is not positive")
-        else:
-            z.fill(1.0)
-    gap = s.dot(z)
-
-    def f4_no_ir(bx, by, bz, bs):
-        # [P A' G'; A 0 0; G 0 -W'W][ux; uy; W^-1 uz] = [bx; by; bz - W'(lmbda o\ bs)],  us = lmbda o\ bs - uz   (coneprog.py:2283-2313)
-        bs.div(lmbda)
-        tmp.xmy(1.0, bs, d)
-        bz.axpy(tmp, -1.0)
-        ksolve(bx, by, bz)
-        bs.axpy(bz, -1.0)
-
-    def res(ux, uy, uz, us, vx, vy, vz, vs):
-        # residual of the Newton equations (coneprog.py:1929-1960)
-        Pd.symv(ux, vx, alpha=-1.0, beta=1.0)
-        if p:
-            Ad.gemv(uy, vx, trans="T", alpha=-1.0, beta=1.0)
-            Ad.gemv(ux, vy, trans="N", alpha=-1.0, beta=1.0)
-        tmp.xmy(1.0, uz, di)
-        Gd.gemv(tmp, vx, trans="T", alpha=-1.0, beta=1.0)
-        Gd.gemv(ux, vz, trans="N", alpha=-1.0, beta=1.0)
-        tmp.xmy(1.0, us, d)
-        vz.axpy(tmp, -1.0)
-        tmp.lincomb(1.0, us, 1.0, uz)
-        tmp.mul(lmbda)
-        vs.axpy(tmp, -1.0)
-
-    f4 = _ipm.f4(f4_no_ir, res, refinement, (wx, wy, wz, ws) if refinement else (), (wx2, wy2, wz2, ws2) if refinement else ())
-
-    for iters in range(MAXITERS + 1):
-        # residuals and objectives (coneprog.py:2167-2203): one reduction call for the five inner products
-        rx.copy_from(qv)
-        Pd.symv(x, rx, alpha=1.0, beta=1.0)
-        tmpx.copy_from(rx)                               # P x + q, for f0
-        if p:
-            Ad.gemv(y, rx, trans="T", alpha=1.0, beta=1.0)
-            ry.copy_from(bv)
-            Ad.gemv(x, ry, trans="N", alpha=1.0, beta=-1.0)      # ry = A x - b
-        Gd.gemv(z, rx, trans="T", alpha=1.0, beta=1.0)
-        rz.lincomb(1.0, s, -1.0, hv)
-        Gd.gemv(x, rz, trans="N", alpha=1.0, beta=1.0)
-        xPq, xq, v_rx, v_rz, zrz, v_ry, yry = reduce_multi([("dot", x, tmpx), ("dot", x, qv), ("dot", rx, rx), ("dot", rz, rz),
-                                                             ("dot", z, rz), ("dot", ry, ry), ("dot", y, ry)])
-        f0 = 0.5 * (xPq + xq)
-        resx, resz, resy = math.sqrt(v_rx), math.sqrt(v_rz), math.sqrt(v_ry)
-        pcost = f0
-        dcost = f0 + yry + zrz - gap
-        relgap = _ipm.relgap(gap, pcost, dcost)
-        pres, dres = max(resy / resy0, resz / resz0), resx / resx0
-        if show:
-            _ipm.progress(iters, pcost, dcost, gap, pres, dres)
-        if (pres <= FEASTOL and dres <= FEASTOL and (gap <= ABSTOL or (relgap is not None and relgap <= RELTOL))) \
-                or iters == MAXITERS:
-            if iters == MAXITERS:
-                return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, msg=_ipm.MAXITERS_MSG)
-            return result("optimal", iters, gap, relgap, pcost, dcost, pres, dres)
-
-        # scaling (coneprog.py:2230-2231) and KKT factorisation
-        if iters == 0:
-            raise_for(lib().kvx_nt_compute_scaling_dev(ml, s.ptr, z.ptr, d.ptr, di.ptr, lmbda.ptr))
-        lmbdasq.sqr_of(lmbda)
-        try:
-            kkt.factor(di)
-            if p:
-                kkt.check()
-        except ArithmeticError:
-            if iters == 0:
-                raise ValueError("Rank(A) < p or Rank([P; A; G]) < n")
-            return result("unknown", iters, gap, relgap, pcost, dcost, pres, dres, msg=_ipm.SINGULAR_MSG)
-
-        mu = gap / ml
-        sigma, eta = 0.0, 0.0
-        for i in (0, 1):
-            # right-hand sides (coneprog.py:2367-2390)
-            ds.fill(0.0)
-            if correction and i == 1:
-                ds.axpy(ws3, -1.0)
-            ds.axpy(lmbdasq, -1.0).addc(sigma * mu)
-            dx.lincomb(-1.0 + eta, rx)
-            if p:
-                dy.lincomb(-1.0 + eta, ry)
-            dz.lincomb(-1.0 + eta, rz)
-            f4(dx, dy, dz, ds)
-            dsdz = ds.dot(dz)
-            if correction and i == 0:
-                ws3.xmy(1.0, ds, dz)
-            # step to the boundary (coneprog.py:2431-2451)
-            ds.div(lmbda); dz.div(lmbda)
-            t = max(0.0, *reduce_multi([("max", ds), ("max", dz)]))
-            step = _ipm.step_length(t, i)
-            if i == 0:
-                sigma = min(1.0, max(0.0, 1.0 - step + dsdz / gap * step ** 2)) ** _ipm.EXPON
-                eta = 0.0
-
-        # update iterates and scaling (coneprog.py:2454-2545)
-        x.axpy(dx, step)
-        if p:
-            y.axpy(dy, step)
-        ds.scal(step).addc(1.0); dz.scal(step).addc(1.0)
-        ds.mul(lmbda); dz.mul(lmbda)
-        raise_for(lib().kvx_nt_update_scaling_dev(ml, ds.ptr, dz.ptr, d.ptr, di.ptr, lmbda.ptr))
-        s.xmy(1.0, lmbda, d)
-        z.xmy(1.0, lmbda, di)
-        gap = lmbda.dot(lmbda)
-    raise AssertionError("unreachable")
+    e = _QpEngine(kkt, pb, opt.refinement)
+    res0 = (max(1.0, e.qv.nrm2()), max(1.0, e.bv.nrm2()), max(1.0, e.hv.nrm2()))
+    out = _ipm.coneqp_loop(e, opt, ml, _ipm.coneqp_start(e, initvals, "initvals"), res0)
+    return _ipm.coneqp_result(opt.show, out.status, e.x.get(), e.y.get(), e.s.get(), e.z.get(), out.stats, e.s.max_step(), e.z.max_step(),
+                              out.iterations, kkt.nfactor, out.msg)

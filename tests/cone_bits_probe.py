@@ -1,5 +1,7 @@
 """Bit-for-bit probe of the general-cone drivers and the host-array cone operations: prints SHA-256 digests of x, y, s, z, the
-status and the iteration count of every case of the goldens G19 (cone.conelp) and G21 (cone.coneqp), and of every output of each
+status and the iteration count of every case of the goldens G19 (cone.conelp) and G21 (cone.coneqp) -- which hold both
+infeasibility certificates, both starting points given, a dualstart alone, initvals, use_correction False and refinement 0, 1, 2 --
+of G19's 'starts' with either starting point alone and of both doc problems stopped by maxiters = 2, and of every output of each
 `misc` operation on the inputs stored in G1, G15 and G16.  Two builds of the package compute the same thing exactly when their
 outputs are equal; run it in each and compare."""
 import hashlib
@@ -52,6 +54,13 @@ for name, d, meta in cases("g19_cone_programs"):
     if "dualstart_z" in d:
         kw["dualstart"] = {k: matrix(d["dualstart_" + k]) for k in ("y", "z") if "dualstart_" + k in d}
     res["g19." + name] = sol_digest(cone.conelp(matrix(d["c"]), dense(d["G"]), matrix(d["h"]), meta["dims"], options=QUIET, **kw))
+    if name == "starts":                                # either starting point alone: the other half comes from the W = I system
+        for half in ("primalstart", "dualstart"):
+            one = {k: v for k, v in kw.items() if k in ("A", "b", half)}
+            res["g19.starts." + half] = sol_digest(cone.conelp(matrix(d["c"]), dense(d["G"]), matrix(d["h"]), meta["dims"], options=QUIET, **one))
+    if name == "doc_conelp":
+        res["g19.doc_conelp.maxiters2"] = sol_digest(cone.conelp(matrix(d["c"]), dense(d["G"]), matrix(d["h"]), meta["dims"],
+                                                                 options=dict(QUIET, maxiters=2)))
 for name, d, meta in cases("g21_coneqp_cones"):
     kw = {}
     if "A" in d:
@@ -62,6 +71,9 @@ for name, d, meta in cases("g21_coneqp_cones"):
     opts.update(meta["options"])
     res["g21." + name] = sol_digest(cone.coneqp(dense(d["P"]), matrix(d["q"]), dense(d["G"]), matrix(d["h"]), meta["dims"],
                                                 options=opts, **kw))
+    if name == "doc_coneqp":
+        res["g21.doc_coneqp.maxiters2"] = sol_digest(cone.coneqp(dense(d["P"]), matrix(d["q"]), dense(d["G"]), matrix(d["h"]), meta["dims"],
+                                                                 options=dict(QUIET, maxiters=2)))
 
 
 def w_digest(W):

@@ -1,5 +1,6 @@
 """Helper of test_kkt_gpu.py::test_fused_iteration_is_bitwise: solves a few problems with the device-resident interior-point
-drivers and prints a digest of every returned array (run once with KVX_LP_UNFUSED=1, once without)."""
+drivers and prints a digest of every returned array (run once with KVX_LP_UNFUSED=1, once without).  Two builds of the package
+compute the same thing exactly when their outputs are equal under every switch."""
 import hashlib
 import json
 import os
@@ -69,4 +70,37 @@ P = workloads.lp_grid(6, 5)
 G = spmatrix.from_ccs(P["ml"], P["n"], P["Gp"], P["Gi"], P["Gx"])
 for r in (1, 2):
     res["grid6x5_r%d" % r] = digest(kvx_lp.conelp(P["c"], G, P["h"], options={"refinement": r}))
+
+# lp.coneqp on the 6x5 grid past its default path: equality constraints (KKTGenEqDev with H = P), iterative refinement, initvals
+# (x, s, z and x, s only), no Mehrotra correction, and a caller's kktsolver (a dense host solve of the whole KKT matrix)
+Q = workloads.qp_grid(6, 5)
+L = workloads.lp_grid_eq(6, 5, 4)
+n, ml = Q["n"], Q["ml"]
+G = spmatrix.from_ccs(ml, n, Q["Gp"], Q["Gi"], Q["Gx"])
+H = spmatrix.from_ccs(n, n, Q["Pp"], Q["Pi"], Q["Px"])
+A = spmatrix.from_ccs(L["p"], n, L["Ap"], L["Ai"], L["Ax"])
+K0 = np.zeros((n + ml, n + ml))
+K0[Q["Pi"], np.repeat(np.arange(n), np.diff(Q["Pp"]))] = Q["Px"]
+K0[n + Q["Gi"], np.repeat(np.arange(n), np.diff(Q["Gp"]))] = Q["Gx"]
+K0 = K0 + np.tril(K0, -1).T
+
+
+def dense_kkt(W):
+    d = W["d"]._a.ravel()
+    Ki = np.linalg.inv(K0 - np.diag(np.concatenate([np.zeros(n), d * d])))
+
+    def f(x, y, z):
+        u = Ki @ np.concatenate([x._a.ravel(), z._a.ravel()])
+        x._a[:] = u[:n].reshape(x._a.shape)
+        z._a[:] = (d * u[n:]).reshape(z._a.shape)
+    return f
+
+
+res["qpeq6x5p4"] = digest(kvx_lp.coneqp(H, Q["q"], G, Q["h"], A=A, b=L["b"]))
+res["qpeq6x5p4_r1"] = digest(kvx_lp.coneqp(H, Q["q"], G, Q["h"], {"refinement": 1}, A=A, b=L["b"]))
+res["qp6x5_r1"] = digest(kvx_lp.coneqp(H, Q["q"], G, Q["h"], {"refinement": 1}))
+res["qp6x5_init_xsz"] = digest(kvx_lp.coneqp(H, Q["q"], G, Q["h"], initvals={"x": Q["x0"], "s": Q["s0"], "z": Q["z0"]}))
+res["qp6x5_init_xs"] = digest(kvx_lp.coneqp(H, Q["q"], G, Q["h"], initvals={"x": Q["x0"], "s": Q["s0"]}))
+res["qp6x5_nocorr"] = digest(kvx_lp.coneqp(H, Q["q"], G, Q["h"], {"use_correction": False}))
+res["qp6x5_user_kkt"] = digest(kvx_lp.coneqp(H, Q["q"], G, Q["h"], kktsolver=dense_kkt))
 print(json.dumps(res))

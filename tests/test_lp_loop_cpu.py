@@ -1,4 +1,4 @@
-"""The interior-point loop of lp.conelp (lp._iterate) on the host: a numpy engine with dense G and the p = 0 KKT solve stands in for
+"""The interior-point loop of conelp (_ipm.conelp_loop) on the host: a numpy engine with dense G and the p = 0 KKT solve stands in for
 the device engines, so the host logic that picks "optimal", "primal infeasible", "dual infeasible" or "unknown" runs without a GPU.
 Compared with the reference's own runs in tests/golden/g4_conelp.* to 1e-10 relative (a numpy restatement of the loop differs from
 them by 1e-16 to 1.1e-15)."""
@@ -8,13 +8,13 @@ import os
 import numpy as np
 import pytest
 
-from kvxopt_amd import _ipm, lp, workloads
+from kvxopt_amd import _ipm, workloads
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 class NumpyEngine:
-    """lp._iterate's engine protocol in numpy.  KKT solve (misc.py:1489-1563 with p = 0): x += G' di^2 z; x = S^-1 x; z = di (G x) - di z."""
+    """_ipm.conelp_loop's engine protocol in numpy.  KKT solve (misc.py:1489-1563 with p = 0): x += G' di^2 z; x = S^-1 x; z = di (G x) - di z."""
 
     def __init__(self, c, G, h):
         self.c, self.G, self.h = (np.asarray(a, dtype=float) for a in (c, G, h))
@@ -45,7 +45,7 @@ class NumpyEngine:
         self.lmbda = np.sqrt(self.s * self.z)
         return self.lmbda @ self.lmbda
 
-    def direction(self, i, sigma, mu, rt, dgi, lmbda_g, wkappa3):
+    def direction(self, i, sigma, mu, rt, dg, dgi, lmbda_g, wkappa3):
         if i == 0:
             self.S = self.G.T @ ((self.di ** 2)[:, None] * self.G)
             self.x1, self.z1 = (dgi * v for v in self.ksolve(-self.c, self.h))
@@ -87,7 +87,7 @@ class NumpyEngine:
 def run(c, G, h, options=None, engine=NumpyEngine):
     e = engine(c, G, h)
     res0 = (max(1.0, np.linalg.norm(e.c)), 1.0, max(1.0, np.linalg.norm(e.h)))
-    return e, lp._iterate(e, _ipm.options(options, {}), len(e.h), e.s @ e.z, res0)
+    return e, _ipm.conelp_loop(e, _ipm.options(options, {}), len(e.h), e.s @ e.z, res0)
 
 
 def rel(a, b):
