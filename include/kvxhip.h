@@ -146,7 +146,10 @@ typedef struct {
     int64_t dev_bytes;       /* bytes of the large device buffers of this handle (panels, inverted diagonal blocks, update
                               * matrices, values); 0 before the first device use.  Sharded mode: THIS rank's share          */
     int64_t lsize_local;     /* panel doubles resident on this rank (= lsize except in sharded mode: own + shared fronts)   */
-    int64_t reserved[2];
+    int64_t reserved[2];     /* [0] leaf subtrees the triangular sweeps walk with one wavefront each, [1] fronts inside them: as the
+                              * device set-up of this handle cut them (0 / 0 under KVX_NO_SUBTREES=1); before the first device
+                              * use, as it would cut them with the environment of the first such query (KVX_SUB_MAXF,
+                              * KVX_NO_SUBTREES); computed once and kept on the handle                                       */
 } kvx_chol_info;
 int kvx_chol_get_info(kvx_chol *F, kvx_chol_info *info);
 int kvx_chol_get_perm(kvx_chol *F, int64_t *perm);     /* final permutation (ordering o postorder) */
@@ -191,6 +194,13 @@ int kvx_dbg_syrk_counts(int64_t *out, int reset);
  * out (refactorisation, block without interchanges), k_lub_gemm, forward sweep small / big, backward sweep small / big (per
  * launcher call with fronts).  A graph replay enqueues nothing and is not counted. */
 int kvx_dbg_lu_counts(int64_t *out, int reset);
+/* kvx_dbg_chol_small_counts: launches of the small-front kernels of the Cholesky path (m <= 128, k <= 64) enqueued by this process,
+ * one counter per routing outcome of their launchers (out may be NULL; reset = 1 zeroes them); returns the number of counters, 32.
+ * Order: k_front_wave at 2 * i + j (i: LDS image 32 / 48 / 64, j: <16> / <32>), from 6 k_front_lds image 96 <32>, 96 <64>, 128 <32>,
+ * 128 <64>, from 10 k_factor_subtree by LDS image 32 / 48 / 64, 13 k_fwd_wave<16>, <32>, 15 k_bwd_wave<32, 32>, <32, 48>, <32, 64>,
+ * 18 k_fwd_lds<32>, <64>, 20 k_bwd_lds, 21 k_fwd_subtree, 22 k_bwd_subtree<32>, <48>, <64>, 25 k_fwd_subtree_mr, 26 k_bwd_subtree_mr<32>,
+ * <64>, 28 k_wide_fwd_small<32>, <64>, 30 k_wide_bwd_small<32>, <64>.  A graph replay enqueues nothing and is not counted. */
+int kvx_dbg_chol_small_counts(int64_t *out, int reset);
 /* kvx_dbg_lu_schedule: the factor-side launch schedule of a numeric pass over the plan that the analysis S gives in its current
  * merge state (no device needed).  Returns the number of entries of the record, -1 for bad arguments or a plan that cannot be
  * built; the record is written only if cap entries hold it (call with cap = 0 for the length).  Record: nlevels, then per level

@@ -70,7 +70,7 @@ class LpCtx(ctypes.Structure):
 class CholInfo(ctypes.Structure):
     _fields_ = [("n", i64), ("nnz_a", i64), ("lnz", i64), ("flops", f64), ("nsuper", i64), ("lsize", i64),
                 ("nlevels", i64), ("max_front", i64), ("upd_size", i64), ("is_numeric", i64), ("minor", i64),
-                ("solve_rowidx", i64), ("is_ll", i64), ("dev_bytes", i64), ("lsize_local", i64), ("reserved", i64 * 2)]
+                ("solve_rowidx", i64), ("is_ll", i64), ("dev_bytes", i64), ("lsize_local", i64), ("solve_subtrees", i64), ("subtree_fronts", i64)]
 
 
 _SIGS = {
@@ -108,6 +108,7 @@ _SIGS = {
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), i64p]),
     "kvx_dbg_syrk_counts": (ctypes.c_int, [i64p, ctypes.c_int]),
     "kvx_dbg_lu_counts": (ctypes.c_int, [i64p, ctypes.c_int]),
+    "kvx_dbg_chol_small_counts": (ctypes.c_int, [i64p, ctypes.c_int]),
     "kvx_dbg_lu_schedule": (i64, [vp, i64p, i64]),
     "kvx_chol_dist_map": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8), f64p, f64p, f64p]),

@@ -435,6 +435,7 @@ int kvx_chol_get_info(kvx_chol *F, kvx_chol_info *info)
     info->minor = F->minor;
     info->solve_rowidx = S.sum_m;
     info->is_ll = F->is_ll ? 1 : 0;
+    subtree_counts(F, info->reserved);
     return KVX_OK;
 }
 

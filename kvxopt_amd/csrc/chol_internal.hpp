@@ -210,12 +210,14 @@ struct kvx_chol {
     int32_t *d_cd_woff = nullptr, *d_depth = nullptr, *d_lists_sw = nullptr;
     int nsub = 0, nsub32 = 0, nsub48 = 0;      // subtrees; the first nsub32 hold only fronts of order <= 32, the next nsub48 - nsub32 of order <= 48
     std::vector<SubDesc> subs_host;
+    int64_t sub_info[2] = {0, 0};              // kvx_chol_get_info: subtrees the sweeps walk and the fronts inside them (subtree_counts)
+    bool sub_info_set = false;
     std::vector<int32_t> cd_woff_host;
     std::vector<uint8_t> in_sub;
     std::vector<int32_t> lsw_host;             // host copy of d_lists_sw
     std::vector<int32_t> col2sn, sub_of;       // sparse right-hand sides (spsolve): front of a permuted column, subtree of a front (-1: none)
     std::vector<int64_t> sw_off;               // per level: the wave-class fronts NOT in a subtree (offset, count into d_lists_sw)
-    std::vector<int> sw_cnt, sw_kmax;
+    std::vector<int> sw_cnt, sw_kmax, sw_maxm;     // ... their number, largest pivot count and largest order
     // many right-hand sides (kernels_wide.hip): per front row, the children's update rows that land on it (built at the first such solve)
     int32_t *d_inv_ptr = nullptr, *d_inv_src = nullptr, *d_iperm = nullptr;   // d_iperm: position of every caller row in the permuted order
     int wide_state = 0;                        // 0 = not built yet, 1 = ready, -1 = not available for this factor (sharded mode, index range)
@@ -283,6 +285,7 @@ inline void prof_collect(kvx_chol *F)
 void build_plan_from(const Symbolic &S, const std::vector<int32_t> &lists, const std::vector<int64_t> &lptr, std::vector<LevelPlan> &plan);
 void build_plan(kvx_chol *F);
 int build_subtrees(kvx_chol *F);
+void subtree_counts(kvx_chol *F, int64_t out[2]);   // solve subtrees and the fronts inside them (kvx_chol_get_info)
 int build_chain_lists(kvx_chol *F);
 int ensure_device(kvx_chol *F);
 int ensure_solve_ws(kvx_chol *F, int64_t nrhs);

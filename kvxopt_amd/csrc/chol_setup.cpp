@@ -78,23 +78,22 @@ void destroy_graphs(kvx_chol *F)
 }
 
 // Leaf subtrees for the solves: maximal subtrees made of wave-class fronts only, small enough for one wavefront
-// (front count, pivot columns, LDS stack of update vectors).  Host analysis, once: the update vector of a subtree
-// root is written long before its parent's level runs, so it gets a slot of its own behind the recycled part of
-// its parity buffer (S.wx / S.wrk_size are adjusted before anything is uploaded).
-void analyze_subtrees(kvx_chol *F)
+// (front count, pivot columns, LDS stack of update vectors).
+// fronts per subtree: longer walks serialise more fronts in one wavefront, shorter ones leave more to the level loop (flat
+// optimum 8..16 on the 1e6-unknown systems).  Round 4: a small system has a few hundred subtrees on an idle machine and its
+// sweeps are chains of dependent launches -- a walk of 12 fronts is then the longest link (41 / 56 us of config 4b's 440 us
+// solve); with 4 fronts per walk the loop of config 4b runs at 587-599 it/s against 548-575 (2: 560-598, 3: 513-601, 5: 557-588).
+static int subtree_maxf(const Symbolic &S, const CholKnobs &K) { return K.sub_maxf > 0 ? K.sub_maxf : (S.n <= 150000 ? 4 : 12); }
+
+// The choice alone, nothing written: take(lo, hi, woff) is called for every subtree [lo, hi], roots descending; woff (one buffer,
+// reused) = the LDS stack offsets of its fronts.
+template <class Take>
+static void pick_subtrees(const Symbolic &S, int maxf, Take take)
 {
-    Symbolic &S = F->S;
     const int64_t ns = S.nsuper;
     std::vector<int32_t> cnt((size_t)ns, 1), minidx((size_t)ns);
-    std::vector<uint8_t> ok((size_t)ns, 0);
-    // fronts per subtree: longer walks serialise more fronts in one wavefront, shorter ones leave more to the level loop (flat
-    // optimum 8..16 on the 1e6-unknown systems).  Round 4: a small system has a few hundred subtrees on an idle machine and its
-    // sweeps are chains of dependent launches -- a walk of 12 fronts is then the longest link (41 / 56 us of config 4b's 440 us
-    // solve); with 4 fronts per walk the loop of config 4b runs at 587-599 it/s against 548-575 (2: 560-598, 3: 513-601, 5: 557-588).
-    const int maxf = F->K.sub_maxf > 0 ? F->K.sub_maxf : (S.n <= 150000 ? 4 : 12);
-    F->in_sub.assign((size_t)ns, 0);
-    F->subs_host.clear();
-    F->cd_woff_host.assign(S.children.size(), 0);
+    std::vector<uint8_t> ok((size_t)ns, 0), in_sub((size_t)ns, 0);
+    std::vector<int64_t> woff;
     for (int64_t s = 0; s < ns; s++) {
         minidx[s] = (int32_t)s;
         bool good = front_class(S.sn_m[s], S.sn_k[s]) >= KVX_CLS_WAVE0;
@@ -109,22 +108,13 @@ void analyze_subtrees(kvx_chol *F)
                (S.super[s + 1] - S.super[lo]) <= KVX_SUB_MAXCOLS;
         ok[s] = good;
     }
-    int64_t extra[2] = {0, 0};
-    const int64_t base[2] = {S.wrk_size[0], S.wrk_size[1]};
-    // factorisation: every front of a subtree gets a slot of its parity buffer that no other front reuses (the level schedule
-    // recycles the buffers level by level; subtrees are factored before the level loop, at all depths at once)
-    int64_t uextra[2] = {0, 0};
-    const int64_t ubase[2] = {S.upd_size[0], S.upd_size[1]};
-    // (opt-in, KVX_FACTOR_SUBTREES=1 -- measured slower than the level schedule, see build_subtrees: the slots cost
-    // sum u^2 doubles over the subtree fronts, 270 MB on config 2)
-    const bool uniq = F->K.factor_subtrees;
     for (int64_t s = ns - 1; s >= 0; s--) {
-        if (!ok[s] || F->in_sub[s]) continue;
+        if (!ok[s] || in_sub[s]) continue;
         if (S.sparent[s] >= 0 && ok[S.sparent[s]]) continue;      // not maximal
         const int64_t lo = s - cnt[s] + 1;
         // LDS stack of update vectors in postorder: a front pops its children, then pushes its own
         int64_t sp = 0, top = 0;
-        std::vector<int64_t> woff((size_t)cnt[s], 0);
+        woff.assign((size_t)cnt[s], 0);
         bool fits = true;
         for (int64_t q = lo; q <= s; q++) {
             for (int64_t c = S.childptr[q]; c < S.childptr[q + 1]; c++) sp -= S.sn_m[S.children[c]] - S.sn_k[S.children[c]];
@@ -134,6 +124,49 @@ void analyze_subtrees(kvx_chol *F)
             if (sp < 0) fits = false;
         }
         if (!fits || top > KVX_SUB_STACK) continue;               // stays in the level lists
+        for (int64_t q = lo; q <= s; q++) in_sub[q] = 1;
+        take(lo, s, woff);
+    }
+}
+
+// kvx_chol_get_info: the solve subtrees of this factor and the fronts inside them.  Two stored numbers: build_subtrees sets them
+// at the device set-up; a query before that computes them once, as the set-up would cut the tree with the environment of that
+// first query (no device needed).
+void subtree_counts(kvx_chol *F, int64_t out[2])
+{
+    if (!F->sub_info_set) {
+        F->sub_info[0] = F->sub_info[1] = 0;
+        const CholKnobs K = read_chol_knobs();
+        if (K.use_subtrees && F->dist_nranks == 1 && (int64_t)F->S.rel.size() < INT32_MAX)
+            pick_subtrees(F->S, subtree_maxf(F->S, K), [&](int64_t lo, int64_t hi, const std::vector<int64_t> &) {
+                F->sub_info[0]++;
+                F->sub_info[1] += hi - lo + 1;
+            });
+        F->sub_info_set = true;
+    }
+    out[0] = F->sub_info[0];
+    out[1] = F->sub_info[1];
+}
+
+// Host analysis, once per factor: the update vector of a subtree root is written long before its parent's level runs, so it
+// gets a slot of its own behind the recycled part of its parity buffer (S.wx / S.wrk_size are adjusted before anything is uploaded).
+void analyze_subtrees(kvx_chol *F)
+{
+    Symbolic &S = F->S;
+    const int64_t ns = S.nsuper;
+    F->in_sub.assign((size_t)ns, 0);
+    F->subs_host.clear();
+    F->cd_woff_host.assign(S.children.size(), 0);
+    int64_t extra[2] = {0, 0};
+    const int64_t base[2] = {S.wrk_size[0], S.wrk_size[1]};
+    // factorisation: every front of a subtree gets a slot of its parity buffer that no other front reuses (the level schedule
+    // recycles the buffers level by level; subtrees are factored before the level loop, at all depths at once)
+    int64_t uextra[2] = {0, 0};
+    const int64_t ubase[2] = {S.upd_size[0], S.upd_size[1]};
+    // (opt-in, KVX_FACTOR_SUBTREES=1 -- measured slower than the level schedule, see build_subtrees: the slots cost
+    // sum u^2 doubles over the subtree fronts, 270 MB on config 2)
+    const bool uniq = F->K.factor_subtrees;
+    pick_subtrees(S, subtree_maxf(S, F->K), [&](int64_t lo, int64_t s, const std::vector<int64_t> &woff) {
         for (int64_t q = lo; q <= s; q++) {
             F->in_sub[q] = 1;
             for (int64_t c = S.childptr[q]; c < S.childptr[q + 1]; c++) F->cd_woff_host[c] = (int32_t)woff[S.children[c] - lo];
@@ -148,7 +181,7 @@ void analyze_subtrees(kvx_chol *F)
         const int p = S.depth[s] & 1;
         S.wx[s] = base[p] + extra[p];
         extra[p] += S.sn_m[s] - S.sn_k[s];
-    }
+    });
     S.wrk_size[0] = base[0] + extra[0];
     S.wrk_size[1] = base[1] + extra[1];
     S.upd_size[0] = ubase[0] + uextra[0];
@@ -205,10 +238,11 @@ int build_subtrees(kvx_chol *F)
     F->sw_off.assign((size_t)S.nlevels, 0);
     F->sw_cnt.assign((size_t)S.nlevels, 0);
     F->sw_kmax.assign((size_t)S.nlevels, 0);
+    F->sw_maxm.assign((size_t)S.nlevels, 0);
     for (int l = 0; l < S.nlevels; l++) {
         F->sw_off[l] = (int64_t)lsw.size();
         // the LDS-class fronts and the wave-class fronts left outside the subtrees share one launch per level and sweep
-        int kmax = 0;
+        int kmax = 0, maxm = 0;
         for (int64_t q = F->lptr_host[l]; q < F->lptr_host[l + 1]; q++) {
             const int32_t f = F->lists_host[q];
             const int c = front_class(S.sn_m[f], S.sn_k[f]);
@@ -216,9 +250,11 @@ int build_subtrees(kvx_chol *F)
             if (!enabled && c < KVX_CLS_WAVE0) continue;           // without subtrees: wave fronts only, their own launch
             lsw.push_back(f);
             kmax = std::max(kmax, (int)S.sn_k[f]);
+            maxm = std::max(maxm, (int)S.sn_m[f]);
         }
         F->sw_cnt[l] = (int)((int64_t)lsw.size() - F->sw_off[l]);
         F->sw_kmax[l] = kmax;
+        F->sw_maxm[l] = maxm;
     }
     if (lsw.empty()) lsw.push_back(0);
     std::vector<SubDesc> subs;
@@ -232,6 +268,11 @@ int build_subtrees(kvx_chol *F)
             if (pass <= 1) F->nsub48++;
         }
     F->nsub = enabled ? (int)subs.size() : 0;
+    F->sub_info[0] = F->nsub;
+    F->sub_info[1] = 0;
+    if (enabled)
+        for (const SubDesc &d : subs) F->sub_info[1] += d.hi - d.lo + 1;
+    F->sub_info_set = true;
     F->solve_merged = enabled;
     if (!enabled) { F->nsub32 = 0; F->nsub48 = 0; }
     if (subs.empty()) subs.push_back(SubDesc{0, -1, 0, 0});

@@ -78,7 +78,7 @@ void enqueue_fwd(kvx_chol *F, double *X, int64_t ldx, int nrhs, int lfrom, int l
                 launch_fwd_lds(ls.lds, F->ds, F->d_lists_sw + woff, wcnt, F->sw_kmax[l], F->d_Lx, X, ldx, nrhs, Wch, Wout, wstride);
             } else {
                 ProfScope ps(F, FAM_FWD, ls.wave);
-                launch_fwd_wave(ls.wave, F->ds, F->d_lists_sw + woff, wcnt, 32, F->d_Lx, X, ldx, nrhs, Wch, Wout, wstride);
+                launch_fwd_wave(ls.wave, F->ds, F->d_lists_sw + woff, wcnt, F->sw_kmax[l], F->d_Lx, X, ldx, nrhs, Wch, Wout, wstride);
             }
         }
         if (nlds > 0) {
@@ -112,7 +112,7 @@ void enqueue_bwd(kvx_chol *F, double *X, int64_t ldx, int nrhs, int lfrom, int l
                 launch_bwd_lds(ls.lds, F->ds, F->d_lists_sw + woff, wcnt, F->d_Lx, X, ldx, nrhs);
             } else {
                 ProfScope ps(F, FAM_BWD, ls.wave);
-                launch_bwd_wave(ls.wave, F->ds, F->d_lists_sw + woff, wcnt, 64, 32, F->d_Lx, X, ldx, nrhs);
+                launch_bwd_wave(ls.wave, F->ds, F->d_lists_sw + woff, wcnt, F->sw_maxm[l], 32, F->d_Lx, X, ldx, nrhs);
             }
         }
         if (nlds > 0) {
@@ -597,7 +597,7 @@ int spsolve_forward_reach(kvx_chol *F, int sys, int64_t ncol, const int64_t *Bp,
                 launch_zero_slots(st, d_slots + 2 * v.zs, v.nz, nc, Wch, wstride);
                 if (v.nsw > 0) {
                     if (F->solve_merged) launch_fwd_lds(st, F->ds, d_l + v.sw, v.nsw, F->sw_kmax[l], F->d_Lx, F->d_X, n, nc, Wch, Wout, wstride);
-                    else launch_fwd_wave(st, F->ds, d_l + v.sw, v.nsw, 32, F->d_Lx, F->d_X, n, nc, Wch, Wout, wstride);
+                    else launch_fwd_wave(st, F->ds, d_l + v.sw, v.nsw, F->sw_kmax[l], F->d_Lx, F->d_X, n, nc, Wch, Wout, wstride);
                 }
                 if (v.nlds > 0)
                     launch_fwd_lds(st, F->ds, d_l + v.lds, v.nlds, std::max(P.maxk[KVX_CLS_LDS128], P.maxk[KVX_CLS_LDS96]), F->d_Lx, F->d_X,

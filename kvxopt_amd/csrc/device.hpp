@@ -245,6 +245,26 @@ enum SyrkVariant {
     SYRK_NVAR
 };
 void syrk_count(SyrkVariant v);
+// Host-side count of the small-front launches enqueued (m <= 128, k <= 64: factorisation and sweeps), one counter per routing
+// outcome of the launchers of kernels_wave.hip and kernels_wide.hip (process-wide; kvx_dbg_chol_small_counts reads them in this
+// order).  A graph replay enqueues nothing and counts nothing.
+enum CholSmallCount {
+    CS_FRONT_WAVE = 0,        // k_front_wave: + 2 * (LDS image 32 / 48 / 64 -> 0 / 1 / 2) + (<32> ? 1 : 0)
+    CS_FRONT_LDS = 6,         // k_front_lds: + 2 * (image 128 ? 1 : 0) + (<64> ? 1 : 0)
+    CS_FACTOR_SUBTREE = 10,   // k_factor_subtree: + (LDS image 32 / 48 / 64 -> 0 / 1 / 2)
+    CS_FWD_WAVE = 13,         // k_fwd_wave<16>, <32>
+    CS_BWD_WAVE = 15,         // k_bwd_wave<32, 32>, <32, 48>, <32, 64>
+    CS_FWD_LDS = 18,          // k_fwd_lds<32>, <64>
+    CS_BWD_LDS = 20,          // k_bwd_lds
+    CS_FWD_SUBTREE = 21,      // k_fwd_subtree<32>
+    CS_BWD_SUBTREE = 22,      // k_bwd_subtree<32>, <48>, <64>
+    CS_FWD_SUBTREE_MR = 25,   // k_fwd_subtree_mr<32, 4>
+    CS_BWD_SUBTREE_MR = 26,   // k_bwd_subtree_mr<32, 4>, <64, 4>
+    CS_WIDE_FWD = 28,         // k_wide_fwd_small<32>, <64>
+    CS_WIDE_BWD = 30,         // k_wide_bwd_small<32>, <64>
+    CS_NCOUNT = 32
+};
+void chol_small_count(int c);
 // sharded mode: rank-ob_len update with the panel [ob, ob + ob_len) of the columns in [c_from, c_to) that rank own_r owns
 void launch_syrk_outer_dist(hipStream_t st, const DevSym &ds, const int32_t *list, int max_m, int ob, int ob_len,
                             int own_ob, int own_g, int own_r, int c_from, int c_to, double *Lx, double *Uout);

@@ -19,6 +19,7 @@
 // Reference role: cholmod_l_factorize (src/C/cholmod.c:362) for these supernodes.
 #include "device.hpp"
 
+#include <atomic>
 #include <cstdlib>
 #include <utility>
 
@@ -491,10 +492,13 @@ void launch_fwd_lds(hipStream_t st, const DevSym &ds, const int32_t *list, int c
 {
     if (count <= 0 || nrhs <= 0) return;
     dim3 grid((unsigned)count, (unsigned)nrhs);
-    if (kmax <= 32)
+    if (kmax <= 32) {
+        chol_small_count(CS_FWD_LDS);
         hipLaunchKernelGGL(k_fwd_lds<32>, grid, dim3(128), 0, st, ds, list, Lx, X, ldx, Wchild, Wout, wstride);
-    else
+    } else {
+        chol_small_count(CS_FWD_LDS + 1);
         hipLaunchKernelGGL(k_fwd_lds<64>, grid, dim3(128), 0, st, ds, list, Lx, X, ldx, Wchild, Wout, wstride);
+    }
 }
 
 void launch_bwd_lds(hipStream_t st, const DevSym &ds, const int32_t *list, int count,
@@ -502,6 +506,7 @@ void launch_bwd_lds(hipStream_t st, const DevSym &ds, const int32_t *list, int c
 {
     if (count <= 0 || nrhs <= 0) return;
     dim3 grid((unsigned)count, (unsigned)nrhs);
+    chol_small_count(CS_BWD_LDS);
     hipLaunchKernelGGL(k_bwd_lds, grid, dim3(128), 0, st, ds, list, Lx, X, ldx);
 }
 
@@ -864,10 +869,12 @@ void launch_fwd_subtree(hipStream_t st, const DevSym &ds, const SubDesc *subs, i
 {
     if (nsub <= 0 || nrhs <= 0) return;
     if (nrhs >= KVX_SUB_MR_FROM) {
+        chol_small_count(CS_FWD_SUBTREE_MR);
         hipLaunchKernelGGL((k_fwd_subtree_mr<32, KVX_SUB_RB>), dim3((unsigned)nsub, (unsigned)((nrhs + KVX_SUB_RB - 1) / KVX_SUB_RB)), dim3(64), 0, st,
                            ds, subs, edges, Lx, X, ldx, nrhs, W0, W1, wstride, depth);
         return;
     }
+    chol_small_count(CS_FWD_SUBTREE);
     hipLaunchKernelGGL(k_fwd_subtree<32>, dim3((unsigned)nsub, (unsigned)nrhs), dim3(64), 0, st, ds, subs, edges, Lx, X, ldx,
                        W0, W1, wstride, depth);
 }
@@ -878,9 +885,16 @@ void launch_bwd_subtree_group(hipStream_t st, int mcap, const DevSym &ds, const 
                               int64_t ldx)
 {
     if (count <= 0) return;
-    if (mcap <= 32) hipLaunchKernelGGL(k_bwd_subtree<32>, dim3((unsigned)count, 1u), dim3(64), 0, st, ds, subs, Lx, X, ldx);
-    else if (mcap <= 48) hipLaunchKernelGGL(k_bwd_subtree<48>, dim3((unsigned)count, 1u), dim3(64), 0, st, ds, subs, Lx, X, ldx);
-    else hipLaunchKernelGGL(k_bwd_subtree<64>, dim3((unsigned)count, 1u), dim3(64), 0, st, ds, subs, Lx, X, ldx);
+    if (mcap <= 32) {
+        chol_small_count(CS_BWD_SUBTREE);
+        hipLaunchKernelGGL(k_bwd_subtree<32>, dim3((unsigned)count, 1u), dim3(64), 0, st, ds, subs, Lx, X, ldx);
+    } else if (mcap <= 48) {
+        chol_small_count(CS_BWD_SUBTREE + 1);
+        hipLaunchKernelGGL(k_bwd_subtree<48>, dim3((unsigned)count, 1u), dim3(64), 0, st, ds, subs, Lx, X, ldx);
+    } else {
+        chol_small_count(CS_BWD_SUBTREE + 2);
+        hipLaunchKernelGGL(k_bwd_subtree<64>, dim3((unsigned)count, 1u), dim3(64), 0, st, ds, subs, Lx, X, ldx);
+    }
 }
 
 // the subtree table holds the subtrees whose fronts all have order <= 32 first (nsub32 of them): half the registers
@@ -890,16 +904,24 @@ void launch_bwd_subtree(hipStream_t st, const DevSym &ds, const SubDesc *subs, i
     if (nsub <= 0 || nrhs <= 0) return;
     if (nrhs >= KVX_SUB_MR_FROM) {
         const unsigned gy = (unsigned)((nrhs + KVX_SUB_RB - 1) / KVX_SUB_RB);
-        if (nsub32 > 0)
+        if (nsub32 > 0) {
+            chol_small_count(CS_BWD_SUBTREE_MR);
             hipLaunchKernelGGL((k_bwd_subtree_mr<32, KVX_SUB_RB>), dim3((unsigned)nsub32, gy), dim3(64), 0, st, ds, subs, Lx, X, ldx, nrhs);
-        if (nsub > nsub32)
+        }
+        if (nsub > nsub32) {
+            chol_small_count(CS_BWD_SUBTREE_MR + 1);
             hipLaunchKernelGGL((k_bwd_subtree_mr<64, KVX_SUB_RB>), dim3((unsigned)(nsub - nsub32), gy), dim3(64), 0, st, ds, subs + nsub32, Lx, X, ldx, nrhs);
+        }
         return;
     }
-    if (nsub32 > 0)
+    if (nsub32 > 0) {
+        chol_small_count(CS_BWD_SUBTREE);
         hipLaunchKernelGGL(k_bwd_subtree<32>, dim3((unsigned)nsub32, (unsigned)nrhs), dim3(64), 0, st, ds, subs, Lx, X, ldx);
-    if (nsub > nsub32)
+    }
+    if (nsub > nsub32) {
+        chol_small_count(CS_BWD_SUBTREE + 2);
         hipLaunchKernelGGL(k_bwd_subtree<64>, dim3((unsigned)(nsub - nsub32), (unsigned)nrhs), dim3(64), 0, st, ds, subs + nsub32, Lx, X, ldx);
+    }
 }
 
 void launch_fwd_wave(hipStream_t st, const DevSym &ds, const int32_t *list, int count, int kmax,
@@ -907,10 +929,13 @@ void launch_fwd_wave(hipStream_t st, const DevSym &ds, const int32_t *list, int 
 {
     if (count <= 0 || nrhs <= 0) return;
     dim3 grid((unsigned)count, (unsigned)nrhs);
-    if (kmax <= 16)
+    if (kmax <= 16) {
+        chol_small_count(CS_FWD_WAVE);
         hipLaunchKernelGGL(k_fwd_wave<16>, grid, dim3(64), 0, st, ds, list, Lx, X, ldx, Wchild, Wout, wstride);
-    else
+    } else {
+        chol_small_count(CS_FWD_WAVE + 1);
         hipLaunchKernelGGL(k_fwd_wave<32>, grid, dim3(64), 0, st, ds, list, Lx, X, ldx, Wchild, Wout, wstride);
+    }
 }
 
 void launch_bwd_wave(hipStream_t st, const DevSym &ds, const int32_t *list, int count, int mcap, int kmax,
@@ -919,13 +944,20 @@ void launch_bwd_wave(hipStream_t st, const DevSym &ds, const int32_t *list, int 
     if (count <= 0 || nrhs <= 0) return;
     (void)kmax;
     dim3 grid((unsigned)count, (unsigned)nrhs);
-    if (mcap <= 32)
+    if (mcap <= 32) {
+        chol_small_count(CS_BWD_WAVE);
         hipLaunchKernelGGL((k_bwd_wave<32, 32>), grid, dim3(64), 0, st, ds, list, Lx, X, ldx);
-    else if (mcap <= 48)
+    } else if (mcap <= 48) {
+        chol_small_count(CS_BWD_WAVE + 1);
         hipLaunchKernelGGL((k_bwd_wave<32, 48>), grid, dim3(64), 0, st, ds, list, Lx, X, ldx);
-    else
+    } else {
+        chol_small_count(CS_BWD_WAVE + 2);
         hipLaunchKernelGGL((k_bwd_wave<32, 64>), grid, dim3(64), 0, st, ds, list, Lx, X, ldx);
+    }
 }
+
+// index of the LDS image size a wave launch is given (32 / 48 / 64 rows): an argument of the kernel, not a choice between kernels
+static int wave_image_index(int mcap) { return mcap <= 32 ? 0 : (mcap <= 48 ? 1 : 2); }
 
 // wave kernel: mcap = LDS image capacity (32 / 48 / 64); kmax: 16 or 32
 void launch_front_wave(hipStream_t st, int mcap, int kmax, const DevSym &ds, const int32_t *list, int count,
@@ -935,9 +967,11 @@ void launch_front_wave(hipStream_t st, int mcap, int kmax, const DevSym &ds, con
     const size_t lds = (size_t)mcap * (mcap + 1) / 2 * sizeof(double) + 128 * sizeof(double) + 64 * sizeof(int);
     static const bool tight = [] { const char *e = getenv("KVX_WAVE_OCC"); return !(e && e[0] == '0'); }();   // KVX_WAVE_OCC=0: the compiler's own allocation
     if (kmax <= 16) {
+        chol_small_count(CS_FRONT_WAVE + 2 * wave_image_index(mcap));
         if (tight) hipLaunchKernelGGL((k_front_wave<16, 5>), dim3((unsigned)count), dim3(64), lds, st, ds, list, Lx, Uchild, Uout, status, mcap);
         else hipLaunchKernelGGL((k_front_wave<16, 1>), dim3((unsigned)count), dim3(64), lds, st, ds, list, Lx, Uchild, Uout, status, mcap);
     } else {
+        chol_small_count(CS_FRONT_WAVE + 2 * wave_image_index(mcap) + 1);
         if (tight) hipLaunchKernelGGL((k_front_wave<32, 4>), dim3((unsigned)count), dim3(64), lds, st, ds, list, Lx, Uchild, Uout, status, mcap);
         else hipLaunchKernelGGL((k_front_wave<32, 1>), dim3((unsigned)count), dim3(64), lds, st, ds, list, Lx, Uchild, Uout, status, mcap);
     }
@@ -949,6 +983,7 @@ void launch_factor_subtree(hipStream_t st, int mcap, const DevSym &ds, const Sub
 {
     if (nsub <= 0) return;
     const size_t lds = (size_t)mcap * (mcap + 1) / 2 * sizeof(double) + 128 * sizeof(double) + 64 * sizeof(int);
+    chol_small_count(CS_FACTOR_SUBTREE + wave_image_index(mcap));
     hipLaunchKernelGGL((k_factor_subtree<32, 3>), dim3((unsigned)nsub), dim3(64), lds, st, ds, subs, depth, Lx, U0, U1, status, mcap);
 }
 
@@ -964,10 +999,26 @@ void launch_front_small(hipStream_t st, int mcap, int kmax, const DevSym &ds, co
         attr_set = true;
     }
     const size_t lds = (size_t)mcap * (mcap + 1) / 2 * sizeof(double) + 256 * sizeof(double) + 128 * sizeof(int);
-    if (kmax <= 32)
+    const int image = mcap <= 96 ? 0 : 1;          // (the LDS image size is an argument of the kernel)
+    if (kmax <= 32) {
+        chol_small_count(CS_FRONT_LDS + 2 * image);
         hipLaunchKernelGGL(k_front_lds<32>, dim3((unsigned)count), dim3(256), lds, st, ds, list, Lx, Uchild, Uout, status, mcap);
-    else
+    } else {
+        chol_small_count(CS_FRONT_LDS + 2 * image + 1);
         hipLaunchKernelGGL(k_front_lds<64>, dim3((unsigned)count), dim3(256), lds, st, ds, list, Lx, Uchild, Uout, status, mcap);
+    }
 }
 
+static std::atomic<long long> g_chol_small_counts[CS_NCOUNT];
+void chol_small_count(int c) { g_chol_small_counts[c].fetch_add(1, std::memory_order_relaxed); }
+
 }  // namespace kvx
+
+extern "C" int kvx_dbg_chol_small_counts(int64_t *out, int reset)
+{
+    for (int c = 0; c < kvx::CS_NCOUNT; c++) {
+        const long long v = reset ? kvx::g_chol_small_counts[c].exchange(0) : kvx::g_chol_small_counts[c].load();
+        if (out) out[c] = (int64_t)v;
+    }
+    return kvx::CS_NCOUNT;
+}

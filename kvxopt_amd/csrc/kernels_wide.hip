@@ -694,16 +694,26 @@ void launch_wide_fwd_small(hipStream_t st, const DevSym &ds, const int32_t *list
 {
     if (count <= 0 || nchunk <= 0) return;
     const dim3 g((unsigned)count, (unsigned)nchunk);
-    if (kmax <= 32) hipLaunchKernelGGL(k_wide_fwd_small<32>, g, dim3(64), 0, st, ds, list, Lx, XT, n, Wch, Wout, wstride, inv_ptr, inv_src);
-    else hipLaunchKernelGGL(k_wide_fwd_small<64>, g, dim3(64), 0, st, ds, list, Lx, XT, n, Wch, Wout, wstride, inv_ptr, inv_src);
+    if (kmax <= 32) {
+        chol_small_count(CS_WIDE_FWD);
+        hipLaunchKernelGGL(k_wide_fwd_small<32>, g, dim3(64), 0, st, ds, list, Lx, XT, n, Wch, Wout, wstride, inv_ptr, inv_src);
+    } else {
+        chol_small_count(CS_WIDE_FWD + 1);
+        hipLaunchKernelGGL(k_wide_fwd_small<64>, g, dim3(64), 0, st, ds, list, Lx, XT, n, Wch, Wout, wstride, inv_ptr, inv_src);
+    }
 }
 void launch_wide_bwd_small(hipStream_t st, const DevSym &ds, const int32_t *list, int count, int kmax, int nchunk, const double *Lx,
                            double *XT, int64_t n)
 {
     if (count <= 0 || nchunk <= 0) return;
     const dim3 g((unsigned)count, (unsigned)nchunk);
-    if (kmax <= 32) hipLaunchKernelGGL(k_wide_bwd_small<32>, g, dim3(64), 0, st, ds, list, Lx, XT, n);
-    else hipLaunchKernelGGL(k_wide_bwd_small<64>, g, dim3(64), 0, st, ds, list, Lx, XT, n);
+    if (kmax <= 32) {
+        chol_small_count(CS_WIDE_BWD);
+        hipLaunchKernelGGL(k_wide_bwd_small<32>, g, dim3(64), 0, st, ds, list, Lx, XT, n);
+    } else {
+        chol_small_count(CS_WIDE_BWD + 1);
+        hipLaunchKernelGGL(k_wide_bwd_small<64>, g, dim3(64), 0, st, ds, list, Lx, XT, n);
+    }
 }
 void launch_wide_fwd_big(hipStream_t st, const DevSym &ds, const int32_t *list, int count, int max_m, int max_k, int nchunk,
                          const double *Lx, const double *Linv, double *XT, int64_t n, const double *Wch, double *Wout,
