@@ -621,6 +621,36 @@ int kvx_admm_batch_state(kvx_admm *S, double *x, double *z, double *y, double *d
 int kvx_admm_batch_solution(kvx_admm *S, const int64_t *kinds, double *X, double *Y);
 int kvx_admm_batch_end(kvx_admm *S);
 
+/* ---- B small dense QPs, each with its own matrices: replaces a loop of solvers.qp calls (coneprog.py:1762-2547 on the
+ * orthant: the starting point :2044-2105, the residuals and the stopping test :2167-2234, the scaling and the two directions
+ * :2243-2456, the step and the scaling update :2459-2547 with misc.py:444-464; the Newton systems of misc.kkt_chol2,
+ * misc.py:1436-1563, with dense Cholesky factors of S = P + G' W^-2 G and, for p > 0, of K = X'X, X = L^-1 A').
+ *     minimize (1/2) x'P_b x + q_b'x   subject to   G_b x <= h_b,  A_b x = b_b,      b = 0..B-1,
+ * in ONE launch, one workgroup per member from its starting point to its status (csrc/qp_batch.hip); refinement 0, no
+ * initial values.  1 <= n <= 64, 1 <= ml <= 512, 0 <= p <= n, 1 <= B <= 2^31 - 1.
+ * Matrices are dense and column-major per member: P n x n (only its lower triangle is read), G ml x n, A p x n (A, b, y may be
+ * NULL when p = 0).  Every datum comes with its member stride in doubles: member b starts at stride * b; 0 means one for all
+ * members, anything else must be at least the datum's size.
+ * Options as coneprog.py:1768-1801: maxiters >= 1, feastol > 0, abstol or reltol > 0, use_correction 0 / 1.
+ * Results, member b in column b: x (n x B), y (p x B), s, z (ml x B); stats (8 x B): gap, relative gap (NaN where the
+ * reference returns None), primal objective, dual objective, primal infeasibility, dual infeasibility, primal slack, dual
+ * slack; iterations and exitcode (B each).  exitcode 0: optimal; 1: maxiters reached; 2: singular KKT matrix after the first
+ * iteration (coneprog.py:2256-2275: the iterates of that iteration are returned); 3: the factorisation with W = I or the first
+ * one failed (coneprog.py:2259 raises ValueError("Rank(A) < p or Rank([P; A; G]) < n")): x, y, s, z are zero, iterations 0
+ * and the stats NaN.  A factorisation fails on a pivot that is <= 0 or not finite, in S or in K.  A member never disturbs
+ * another: its bytes depend on its own data alone, not on B or its place.  Fixed summation order, no floating-point atomics.
+ * kvx_qp_batch_solve: host pointers; uploads, launches, downloads.  kvx_qp_batch_solve_dev: device pointers, results complete
+ * on return.  KVX_EINVAL for bad sizes, limits, strides, options or NULL pointers on any box, before a device is asked for;
+ * KVX_EDEVICE without a GPU (never a CPU fallback). */
+int kvx_qp_batch_solve(int64_t B, int64_t n, int64_t ml, int64_t p, const double *P, int64_t sP, const double *q, int64_t sq,
+                       const double *G, int64_t sG, const double *h, int64_t sh, const double *A, int64_t sA, const double *b, int64_t sb,
+                       int64_t maxiters, double abstol, double reltol, double feastol, int use_correction, double *x, double *y, double *s,
+                       double *z, double *stats, int64_t *iterations, int64_t *exitcode);
+int kvx_qp_batch_solve_dev(int64_t B, int64_t n, int64_t ml, int64_t p, const double *P, int64_t sP, const double *q, int64_t sq,
+                           const double *G, int64_t sG, const double *h, int64_t sh, const double *A, int64_t sA, const double *b,
+                           int64_t sb, int64_t maxiters, double abstol, double reltol, double feastol, int use_correction, double *x,
+                           double *y, double *s, double *z, double *stats, int64_t *iterations, int64_t *exitcode);
+
 /* ---- dense helpers of the equality-constrained KKT solve with a general S (misc.py:1476-1487, 1545): K = A S^-1 A' formed
  * as a dense p x p matrix from X = S^-1 A' (kvx_chol_solve_dev with nrhs = p) when p is moderate ------------------------- */
 /* Y(j, c) = sum_i A(i, j) X(i, c) for the CCS matrix A with n columns and every column c < ncols of the dense X */

@@ -12,6 +12,8 @@
     cpl(c, F, G=None, h=None, dims=None, A=None, b=None)                             cvxprog.py:35   (-> cvx.cpl, 'l' rows only)
     cp(F, G=None, h=None, dims=None, A=None, b=None)                                 cvxprog.py:1359 (-> cvx.cp: cpl on the epigraph form)
     gp(K, F, g, G=None, h=None, A=None, b=None)                                      cvxprog.py:1967 (-> cvx.gp: kvx_gp_eval_dev, cp)
+    qp_batch(P, q, G, h, A=None, b=None, options=None)                               no counterpart: B small dense QPs in one launch
+                                                                                     (-> qpbatch.qp_batch; reads its own `options` only)
     options                                                                          the module-level dict of the reference
 
 Like the reference, algorithm parameters come from `solvers.options` ('maxiters', 'abstol', 'reltol', 'feastol',
@@ -30,6 +32,7 @@ from . import cone as _cone
 from . import cvx as _cvx
 from . import lp as _lp
 from . import osqp as _osqp
+from .qpbatch import qp_batch  # noqa: F401
 
 options = {}
 
