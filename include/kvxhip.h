@@ -651,6 +651,40 @@ int kvx_qp_batch_solve_dev(int64_t B, int64_t n, int64_t ml, int64_t p, const do
                            int64_t sb, int64_t maxiters, double abstol, double reltol, double feastol, int use_correction, double *x,
                            double *y, double *s, double *z, double *stats, int64_t *iterations, int64_t *exitcode);
 
+/* ---- B small dense LPs, each with its own matrices: replaces a loop of solvers.lp calls (coneprog.py:662-1436 on the orthant:
+ * the starting point with W = I, both pushes and the optimal-at-iteration-0 return :662-842, the residuals and the three
+ * stopping tests with their scalings :861-1024, the scaling, the constant system and f6_no_ir :1031-1195, the two directions
+ * :1248-1333, the step and the scaling update :1336-1436 with misc.py:444-464; the Newton systems of misc.kkt_chol2,
+ * misc.py:1395-1563, with dense Cholesky factors of S = G' W^-2 G and, for p > 0, of K = X'X, X = L^-1 A', and its
+ * F['singular'] repair S + A'A, misc.py:1433-1458, 1526-1527, when the first factor of S fails and p > 0).
+ *     minimize c_b'x   subject to   G_b x + s = h_b,  s >= 0,  A_b x = b_b,      b = 0..B-1,
+ * in ONE launch, one workgroup per member from its starting point to its status or certificate (csrc/lp_batch.hip);
+ * refinement 0, no starting points.  1 <= n <= 64, 1 <= ml <= 512, 0 <= p <= n, p + ml >= n, 1 <= B <= 2^31 - 1.
+ * Matrices are dense and column-major per member: G ml x n, A p x n (A, b, y may be NULL when p = 0).  Every datum comes
+ * with its member stride in doubles: member b starts at stride * b; 0 means one for all members, anything else must be at
+ * least the datum's size.  Options as coneprog.py:425-455: maxiters >= 1, feastol > 0, abstol or reltol > 0.
+ * Results, member b in column b: x (n x B), y (p x B), s, z (ml x B); stats (10 x B): gap, relative gap, primal objective,
+ * dual objective, primal infeasibility, dual infeasibility, primal slack, dual slack, residual as primal infeasibility
+ * certificate, residual as dual infeasibility certificate -- NaN where the reference returns None; iterations and exitcode
+ * (B each).  exitcode 0: optimal; 1: maxiters reached; 2: singular KKT matrix after the first iteration (coneprog.py:1078-1109:
+ * the iterates scaled by 1 / tau are returned); 3: the factorisation with W = I or the first one failed, the repair included
+ * (solvers.lp raises ValueError("Rank(A) < p or Rank([G; A]) < n")): x, y, s, z are zero, iterations 0 and the stats NaN;
+ * 4: primal infeasible, y and z are the certificate scaled to h'z + b'y = -1, x and s are NaN (coneprog.py:976-999);
+ * 5: dual infeasible, x and s are the certificate scaled to c'x = -1, y and z are NaN (coneprog.py:1000-1024).
+ * A factorisation fails on a pivot that is <= 0 or not finite, in S or in K.  A member never disturbs another: its bytes depend
+ * on its own data alone, not on B or its place.  Fixed summation order, no floating-point atomics.
+ * kvx_lp_batch_solve: host pointers; uploads, launches, downloads.  kvx_lp_batch_solve_dev: device pointers, results complete
+ * on return.  KVX_EINVAL for bad sizes, limits, strides, options or NULL pointers on any box, before a device is asked for;
+ * KVX_EDEVICE without a GPU (never a CPU fallback). */
+int kvx_lp_batch_solve(int64_t B, int64_t n, int64_t ml, int64_t p, const double *c, int64_t sc, const double *G, int64_t sG,
+                       const double *h, int64_t sh, const double *A, int64_t sA, const double *b, int64_t sb, int64_t maxiters,
+                       double abstol, double reltol, double feastol, double *x, double *y, double *s, double *z, double *stats,
+                       int64_t *iterations, int64_t *exitcode);
+int kvx_lp_batch_solve_dev(int64_t B, int64_t n, int64_t ml, int64_t p, const double *c, int64_t sc, const double *G, int64_t sG,
+                           const double *h, int64_t sh, const double *A, int64_t sA, const double *b, int64_t sb, int64_t maxiters,
+                           double abstol, double reltol, double feastol, double *x, double *y, double *s, double *z, double *stats,
+                           int64_t *iterations, int64_t *exitcode);
+
 /* ---- dense helpers of the equality-constrained KKT solve with a general S (misc.py:1476-1487, 1545): K = A S^-1 A' formed
  * as a dense p x p matrix from X = S^-1 A' (kvx_chol_solve_dev with nrhs = p) when p is moderate ------------------------- */
 /* Y(j, c) = sum_i A(i, j) X(i, c) for the CCS matrix A with n columns and every column c < ncols of the dense X */

@@ -1,28 +1,12 @@
 // kvx_qp_batch_solve / kvx_qp_batch_solve_dev (include/kvxhip.h): the argument checks, which need no device, the transfers of
 // the host entry, and the one launch of k_qp_batch (qp_batch.hip).
-#include "../../include/kvxhip.h"
-#include "abi_guard.hpp"
-#include "devpool.hpp"
+#include "batch_host.hpp"
 #include "qp_batch.hpp"
 
-#include <string>
-#include <vector>
-
 using namespace kvx;
-
-#define HIPCHK(call)                                                             \
-    do {                                                                         \
-        hipError_t e_ = (call);                                                  \
-        if (e_ != hipSuccess) return KVX_EDEVICE;                                \
-    } while (0)
+using namespace kvx::batchhost;
 
 namespace {
-
-int refuse(const char *who, const std::string &why)
-{
-    set_last_error(std::string(who) + ": " + why);
-    return KVX_EINVAL;
-}
 
 // What both entries check before a device is asked for.  size: doubles of one member; stride 0 (shared) or >= size.
 int check(const char *who, const QpBatchArgs &a)
@@ -45,48 +29,12 @@ int check(const char *who, const QpBatchArgs &a)
     return KVX_OK;
 }
 
-int need_device(const char *who)
-{
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) {
-        set_last_error(std::string(who) + ": no HIP device; the batch has no CPU fallback");
-        return KVX_EDEVICE;
-    }
-    return KVX_OK;
-}
-
 int solve_dev_impl(const QpBatchArgs &a)
 {
     int rc = check("kvx_qp_batch_solve_dev", a);
     if (rc || (rc = need_device("kvx_qp_batch_solve_dev"))) return rc;
     HIPCHK(launch_qp_batch(nullptr, a));
     HIPCHK(hipStreamSynchronize(nullptr));
-    return KVX_OK;
-}
-
-struct Buffers {                              // the device copies of one host call, given back to the pool on every path
-    std::vector<void *> own;
-    ~Buffers() { for (void *p : own) (void)pool_free(p); }
-    int get(double **d, int64_t count)
-    {
-        HIPCHK(pool_malloc((void **)d, (size_t)(count > 0 ? count : 1) * sizeof(double)));
-        own.push_back(*d);
-        return KVX_OK;
-    }
-    int up(const double **d, const double *h, int64_t count)
-    {
-        double *t = nullptr;
-        int rc = get(&t, count);
-        if (rc) return rc;
-        if (count > 0) HIPCHK(hipMemcpy(t, h, (size_t)count * sizeof(double), hipMemcpyHostToDevice));
-        *d = t;
-        return KVX_OK;
-    }
-};
-
-int down(void *h, const void *d, int64_t count)
-{
-    if (count > 0) HIPCHK(hipMemcpy(h, d, (size_t)count * 8, hipMemcpyDeviceToHost));
     return KVX_OK;
 }
 

@@ -14,7 +14,10 @@
     gp(K, F, g, G=None, h=None, A=None, b=None)                                      cvxprog.py:1967 (-> cvx.gp: kvx_gp_eval_dev, cp)
     qp_batch(P, q, G, h, A=None, b=None, options=None)                               no counterpart: B small dense QPs in one launch
                                                                                      (-> qpbatch.qp_batch; reads its own `options` only)
-    options                                                                          the module-level dict of the reference
+    lp_batch(c, G, h, A=None, b=None, options=None)                                  no counterpart: B small dense LPs in one launch,
+                                                                                     with conelp's infeasibility certificates
+                                                                                     (-> lpbatch.lp_batch; reads its own `options` only)
+    options                                                                         the module-level dict of the reference
 
 Like the reference, algorithm parameters come from `solvers.options` ('maxiters', 'abstol', 'reltol', 'feastol',
 'refinement', 'show_progress'); a keyword `options=` overrides it per call.  `conelp / lp / coneqp / qp (..., kktsolver=f)`
@@ -32,6 +35,7 @@ from . import cone as _cone
 from . import cvx as _cvx
 from . import lp as _lp
 from . import osqp as _osqp
+from .lpbatch import lp_batch  # noqa: F401
 from .qpbatch import qp_batch  # noqa: F401
 
 options = {}
