@@ -132,6 +132,14 @@ def programs():
     out["gp_random"] = dict(kind="gp", K=K, F=F, g=g, G=G, h=G @ x0 + rng.uniform(0.5, 1.5, G.shape[0]), A=A, b=A @ x0)
     # the reference stops at its iteration limit: status 'unknown'
     out["gp_doc_maxiters"] = dict(doc, options={"maxiters": 4})
+    # a gp on the edges of the evaluator's size classes: K = 257 (workgroup), 17 (wavefront), 16 (16-lane group), and 17 columns
+    # (two Gram tile rows).  g_i = -1 - log K_i on the constraint blocks: f_i(0) = -1, x = 0 is strictly feasible; the objective
+    # has 257 Gaussian rows in 17 dimensions: it grows in every direction
+    rng = np.random.default_rng(2404)
+    K, n = [257, 17, 16], 17
+    F = rng.standard_normal((sum(K), n))
+    g = np.concatenate([rng.standard_normal(K[0])] + [np.full(k, -1.0 - np.log(k)) for k in K[1:]])
+    out["gp_edges"] = dict(kind="gp", K=K, F=F, g=g)
     return out
 
 

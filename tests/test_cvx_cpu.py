@@ -10,6 +10,8 @@ import pytest
 
 from kvxopt_amd import _lib, base, cvx, solvers
 
+from gp_eval_numpy import assert_plan_patterns
+
 _GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 G23 = np.load(os.path.join(_GOLD, "g23_gp_eval.npz"))
 G23_CASES = [str(c) for c in G23["cases"]]
@@ -89,21 +91,7 @@ def test_gp_plan_patterns_equal_a_numpy_restatement(name):
     """Df: row i holds the columns met by block i; H: the lower pattern of F' blockdiag(11') F."""
     K, n, Fp, Fi, Fx = g23_ccs(name)
     ev = cvx.GPEval(K, n, Fp, Fi, Fx, G23[name + "__g"])
-    P = np.zeros((int(K.sum()), n))
-    P[Fi, np.repeat(np.arange(n), np.diff(Fp))] = 1.0
-    B = np.zeros((K.size, int(K.sum())))
-    off = np.concatenate([[0], np.cumsum(K)])
-    for i in range(K.size):
-        B[i, off[i]:off[i + 1]] = 1.0
-    want_df = (B @ P) > 0
-    want_h = np.tril((P.T @ (B.T @ B) @ P) > 0)
-    got_df, got_h = np.zeros_like(want_df), np.zeros_like(want_h)
-    got_df[ev.df_pattern] = True
-    got_h[ev.h_pattern] = True
-    assert np.array_equal(got_df, want_df) and np.array_equal(got_h, want_h)
-    assert ev.Dfi.size == want_df.sum() and ev.Hi.size == want_h.sum()          # no entry twice
-    for cp, ri in ((ev.Dfp, ev.Dfi), (ev.Hp, ev.Hi)):                           # rows ascending inside every column
-        assert all(np.all(np.diff(ri[cp[j]:cp[j + 1]]) > 0) for j in range(n))
+    assert_plan_patterns(ev, K, n, Fp, Fi)
 
 
 def test_gp_plan_argument_checks():
@@ -158,8 +146,10 @@ def test_goldens_come_from_the_reference():
     meta = json.load(open(os.path.join(_GOLD, "g24_cvx_programs.json")))
     Z = np.load(os.path.join(_GOLD, "g24_cvx_programs.npz"))
     assert "reference" in meta["via"]
-    assert set(meta["cases"]) == {"gp_doc", "cp_acent", "cp_robls", "cpl_floorplan", "gp_random", "gp_doc_maxiters"}
+    assert set(meta["cases"]) == {"gp_doc", "cp_acent", "cp_robls", "cpl_floorplan", "gp_random", "gp_doc_maxiters", "gp_edges"}
     assert meta["cases"]["gp_doc_maxiters"]["status"] == "unknown"
     assert all(m["status"] == "optimal" for k, m in meta["cases"].items() if k != "gp_doc_maxiters")
     for name in meta["cases"]:
         assert Z[name + "__sol_x"].size > 0
+    assert meta["cases"]["gp_edges"]["K"] == [257, 17, 16] and Z["gp_edges__F"].shape == (290, 17)
+    assert np.array_equal(Z["gp_edges__g"][257:], np.concatenate([np.full(k, -1.0 - np.log(k)) for k in (17, 16)]))

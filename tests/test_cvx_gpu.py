@@ -11,6 +11,8 @@ from kvxopt_amd import base, cone, cvx, solvers
 from kvxopt_amd.coneops import Dims, WDev
 from kvxopt_amd.devvec import DVec
 
+from gp_eval_numpy import as_ccs, numpy_eval as _numpy_eval
+
 pytestmark = pytest.mark.gpu
 
 _GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -23,11 +25,7 @@ POISON = -7.25e300
 
 
 def _ccs(name):
-    F = G23[name + "__F"]
-    if bool(G23[name + "__sparse"]):
-        I, J = np.nonzero(F)
-        F = base.spmatrix(F[I, J], I, J, F.shape)
-    _, n, Fp, Fi, Fx = base.ccs(F)
+    n, Fp, Fi, Fx = as_ccs(G23[name + "__F"], bool(G23[name + "__sparse"]))
     return G23[name + "__K"], n, Fp, Fi, Fx
 
 
@@ -44,30 +42,6 @@ def _evaluate(ev, x, z):
     if z is not None:
         H[ev.h_pattern] = raw_h[:ev.Hi.size]
     return f.get(), Df, H, Dfx.get(), raw_h
-
-
-def _numpy_eval(K, F, g, x, z, dtype):
-    """f, Df, tril(H) in the precision `dtype`, and for float64 the sums of absolute contributions of every entry."""
-    F, g, x, z = (np.asarray(a, dtype=dtype) for a in (F, g, x, z))
-    off = np.concatenate([[0], np.cumsum(K)])
-    m, n = len(K), F.shape[1]
-    f, Df, H = np.zeros(m, dtype=dtype), np.zeros((m, n), dtype=dtype), np.zeros((n, n), dtype=dtype)
-    sf, sDf, sH = np.zeros(m), np.zeros((m, n)), np.zeros((n, n))
-    for i in range(m):
-        Fi = F[off[i]:off[i + 1]]
-        u = Fi @ x + g[off[i]:off[i + 1]]
-        su = np.abs(Fi) @ np.abs(x) + np.abs(g[off[i]:off[i + 1]])
-        mx = u.max()
-        e = np.exp(u - mx)
-        f[i] = mx + np.log(e.sum())
-        y = e / e.sum()
-        Df[i] = y @ Fi
-        C = Fi - Df[i][None, :]
-        H += z[i] * (C.T @ (C * y[:, None]))
-        sf[i] = float(su.max()) + 1.0
-        sDf[i] = np.asarray(np.abs(y) @ np.abs(Fi), dtype=float)
-        sH += float(z[i]) * np.asarray(np.abs(C).T @ (np.abs(C) * y[:, None]), dtype=float)
-    return f, Df, np.tril(H), sf, sDf, np.tril(sH)
 
 
 @pytest.mark.parametrize("name", G23_CASES)
@@ -309,9 +283,9 @@ def test_g24_solves_against_reference(name):
         _check_optimal(sol, d, fn, x0, epigraph, opt)
 
 
-def test_gp_device_path_and_callback_path_agree():
+@pytest.mark.parametrize("name", ["gp_random", "gp_edges"])
+def test_gp_device_path_and_callback_path_agree(name):
     """The same gp through kvx_gp_eval_dev and through cp with a callback that evaluates the blocks in numpy."""
-    name = "gp_random"
     m = G24_META[name]
     d, kw, solve, fn, x0, _ = _case(name)
     K = [int(k) for k in m["K"]]
