@@ -685,6 +685,30 @@ int kvx_lp_batch_solve_dev(int64_t B, int64_t n, int64_t ml, int64_t p, const do
                            double abstol, double reltol, double feastol, double *x, double *y, double *s, double *z, double *stats,
                            int64_t *iterations, int64_t *exitcode);
 
+/* ---- B small dense second-order-cone programs, each with its own matrices: replaces a loop of solvers.socp calls
+ * (coneprog.socp -> coneprog.conelp, coneprog.py:662-1436, with the 'q' blocks of misc.compute_scaling / update_scaling,
+ * misc.py:290-352, 467-580, of misc_solvers.scale, scale2, sprod, sinv, misc_solvers.c:144-186, 301-341, 671-700, 803-835, and
+ * of max_step, misc_solvers.c:1073-1085; the Newton systems of misc.kkt_chol2, misc.py:1395-1563, on Gs = W^-T G, with its
+ * F['singular'] repair).
+ *     minimize c_b'x   subject to   G_b x + s = h_b,  s in R^ml_+ x Q^{q[0]} x ... x Q^{q[nq-1]},  A_b x = b_b,      b = 0..B-1,
+ * in ONE launch, one workgroup per member from its starting point to its status or certificate (csrc/socp_batch.hip);
+ * refinement 0 (solvers.socp defaults to 1), no starting points.  The cone is the same for every member: q is a HOST array of
+ * nq cone orders for both entries (it travels with the kernel's arguments), rows stacked as in conelp, the ml 'l' rows first.
+ * 1 <= n <= 64, ml >= 0, 0 <= nq <= 128, every q[k] >= 1, 1 <= N = ml + sum q <= 512, 0 <= p <= n, p + N >= n,
+ * 1 <= B <= 2^31 - 1.  Matrices, strides, options, results, stats, exit codes and the independence of the members are those of
+ * kvx_lp_batch_solve with N rows in G, h, s and z; primal and dual slack are -max_step over the whole cone.
+ * kvx_socp_batch_solve: host pointers; uploads, launches, downloads.  kvx_socp_batch_solve_dev: device pointers (q excepted),
+ * no workspace, results complete on return.  KVX_EINVAL for bad sizes, limits, strides, options, NULL pointers or cone orders
+ * on any box, before a device is asked for; KVX_EDEVICE without a GPU (never a CPU fallback). */
+int kvx_socp_batch_solve(int64_t B, int64_t n, int64_t ml, int64_t nq, const int64_t *q, int64_t p, const double *c, int64_t sc,
+                         const double *G, int64_t sG, const double *h, int64_t sh, const double *A, int64_t sA, const double *b,
+                         int64_t sb, int64_t maxiters, double abstol, double reltol, double feastol, double *x, double *y, double *s,
+                         double *z, double *stats, int64_t *iterations, int64_t *exitcode);
+int kvx_socp_batch_solve_dev(int64_t B, int64_t n, int64_t ml, int64_t nq, const int64_t *q, int64_t p, const double *c, int64_t sc,
+                             const double *G, int64_t sG, const double *h, int64_t sh, const double *A, int64_t sA, const double *b,
+                             int64_t sb, int64_t maxiters, double abstol, double reltol, double feastol, double *x, double *y,
+                             double *s, double *z, double *stats, int64_t *iterations, int64_t *exitcode);
+
 /* ---- dense helpers of the equality-constrained KKT solve with a general S (misc.py:1476-1487, 1545): K = A S^-1 A' formed
  * as a dense p x p matrix from X = S^-1 A' (kvx_chol_solve_dev with nrhs = p) when p is moderate ------------------------- */
 /* Y(j, c) = sum_i A(i, j) X(i, c) for the CCS matrix A with n columns and every column c < ncols of the dense X */

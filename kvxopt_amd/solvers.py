@@ -17,6 +17,9 @@
     lp_batch(c, G, h, A=None, b=None, options=None)                                  no counterpart: B small dense LPs in one launch,
                                                                                      with conelp's infeasibility certificates
                                                                                      (-> lpbatch.lp_batch; reads its own `options` only)
+    socp_batch(c, G, h, dims, A=None, b=None, options=None)                          no counterpart: B small dense SOCPs in one launch,
+                                                                                     dims = {'l': ml, 'q': [...]} shared by the members
+                                                                                     (-> socpbatch.socp_batch; reads its own `options` only)
     options                                                                         the module-level dict of the reference
 
 Like the reference, algorithm parameters come from `solvers.options` ('maxiters', 'abstol', 'reltol', 'feastol',
@@ -37,6 +40,7 @@ from . import lp as _lp
 from . import osqp as _osqp
 from .lpbatch import lp_batch  # noqa: F401
 from .qpbatch import qp_batch  # noqa: F401
+from .socpbatch import socp_batch  # noqa: F401
 
 options = {}
 
