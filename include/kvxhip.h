@@ -201,6 +201,13 @@ int kvx_dbg_lu_counts(int64_t *out, int reset);
  * 18 k_fwd_lds<32>, <64>, 20 k_bwd_lds, 21 k_fwd_subtree, 22 k_bwd_subtree<32>, <48>, <64>, 25 k_fwd_subtree_mr, 26 k_bwd_subtree_mr<32>,
  * <64>, 28 k_wide_fwd_small<32>, <64>, 30 k_wide_bwd_small<32>, <64>.  A graph replay enqueues nothing and is not counted. */
 int kvx_dbg_chol_small_counts(int64_t *out, int reset);
+/* kvx_dbg_chol_big_solve_counts: launches of the triangular sweeps over the big fronts of the Cholesky path (m > 128 or k > 64)
+ * enqueued by this process, one counter per launch site of launch_fwd_big, launch_bwd_big, launch_wide_fwd_big and
+ * launch_wide_bwd_big (out may be NULL; reset = 1 zeroes them); returns the number of counters, 17.  Order: k_fwd_big_step<true, 64>,
+ * <false, 64>, <true, 256>, <false, 256>, from 4 k_fwd_big_step_mr<true, 8, 1>, <true, 8, 2>, <false, 8, 1>, <false, 8, 2>,
+ * 8 k_bwd_big_init, 9 k_bwd_big_step, 10 k_bwd_big_init_mr, 11 k_bwd_big_step_mr<8, 1>, <8, 2>, 13 k_wide_fwd_big_asm,
+ * 14 k_wide_fwd_big_step, 15 k_wide_bwd_big_head, 16 k_wide_bwd_big_step.  A graph replay enqueues nothing and is not counted. */
+int kvx_dbg_chol_big_solve_counts(int64_t *out, int reset);
 /* kvx_dbg_lu_schedule: the factor-side launch schedule of a numeric pass over the plan that the analysis S gives in its current
  * merge state (no device needed).  Returns the number of entries of the record, -1 for bad arguments or a plan that cannot be
  * built; the record is written only if cap entries hold it (call with cap = 0 for the length).  Record: nlevels, then per level

@@ -109,6 +109,7 @@ _SIGS = {
     "kvx_dbg_syrk_counts": (ctypes.c_int, [i64p, ctypes.c_int]),
     "kvx_dbg_lu_counts": (ctypes.c_int, [i64p, ctypes.c_int]),
     "kvx_dbg_chol_small_counts": (ctypes.c_int, [i64p, ctypes.c_int]),
+    "kvx_dbg_chol_big_solve_counts": (ctypes.c_int, [i64p, ctypes.c_int]),
     "kvx_dbg_lu_schedule": (i64, [vp, i64p, i64]),
     "kvx_chol_dist_map": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8), f64p, f64p, f64p]),

@@ -265,6 +265,23 @@ enum CholSmallCount {
     CS_NCOUNT = 32
 };
 void chol_small_count(int c);
+// The same for the triangular sweeps over the big fronts (m > 128 or k > 64): one counter per hipLaunchKernelGGL of launch_fwd_big,
+// launch_bwd_big (kernels_big.hip), launch_wide_fwd_big and launch_wide_bwd_big (kernels_wide.hip); kvx_dbg_chol_big_solve_counts
+// reads them in this order.
+enum CholBigSolveCount {
+    CB_FWD = 0,               // k_fwd_big_step<true, 64>, <false, 64>, <true, 256>, <false, 256>: + 2 * (ROWS == 256) + !FIRST
+    CB_FWD_MR = 4,            // k_fwd_big_step_mr<true, 8, 1>, <true, 8, 2>, <false, 8, 1>, <false, 8, 2>: + 2 * !FIRST + (MODE - 1)
+    CB_BWD_INIT = 8,          // k_bwd_big_init
+    CB_BWD_STEP = 9,          // k_bwd_big_step
+    CB_BWD_MR_INIT = 10,      // k_bwd_big_init_mr<8>
+    CB_BWD_MR_STEP = 11,      // k_bwd_big_step_mr<8, 1>, <8, 2>
+    CB_WIDE_FWD_ASM = 13,     // k_wide_fwd_big_asm
+    CB_WIDE_FWD_STEP = 14,    // k_wide_fwd_big_step
+    CB_WIDE_BWD_HEAD = 15,    // k_wide_bwd_big_head
+    CB_WIDE_BWD_STEP = 16,    // k_wide_bwd_big_step
+    CB_NCOUNT = 17
+};
+void chol_big_solve_count(int c);
 // sharded mode: rank-ob_len update with the panel [ob, ob + ob_len) of the columns in [c_from, c_to) that rank own_r owns
 void launch_syrk_outer_dist(hipStream_t st, const DevSym &ds, const int32_t *list, int max_m, int ob, int ob_len,
                             int own_ob, int own_g, int own_r, int c_from, int c_to, double *Lx, double *Uout);

@@ -1855,6 +1855,7 @@ void launch_fwd_big(hipStream_t st, const DevSym &ds, const int32_t *list, int c
             // single-rhs kernel, one grid layer per right-hand side (round-3 advisor finding; test_solution_bits_do_not_depend_on_nrhs).
             if ((int64_t)std::max(1, (rows + 63) / 64) * std::max(level_count, count) <= narrow_wgs) {
                 dim3 grid((unsigned)std::max(1, (rows + 63) / 64), (unsigned)count, (unsigned)nrhs);
+                chol_big_solve_count(CB_FWD + (jb == 0 ? 0 : 1));
                 if (jb == 0) hipLaunchKernelGGL((k_fwd_big_step<true, 64>), grid, dim3(SOLVE_NT), 0, st, ds, list, jb, Lx, Linv, X, X0, ldx, WK, ldw, Wchild, Wout, wstride);
                 else hipLaunchKernelGGL((k_fwd_big_step<false, 64>), grid, dim3(SOLVE_NT), 0, st, ds, list, jb, Lx, Linv, X, X0, ldx, WK, ldw, Wchild, Wout, wstride);
                 continue;
@@ -1863,6 +1864,8 @@ void launch_fwd_big(hipStream_t st, const DevSym &ds, const int32_t *list, int c
             // (blocks of 1 for the diagonal launch -- more, shorter workgroups -- were measured and lost: 18.5 -> 20.4 ms at 64 rhs,
             // n = 1e6: a 1024-thread workgroup per front and right-hand side is the cost, not the length of its chain)
             dim3 g1(1, (unsigned)count, gz), g2((unsigned)std::max(1, (rows + 255) / 256), (unsigned)count, gz);
+            chol_big_solve_count(CB_FWD_MR + (jb == 0 ? 0 : 2));
+            chol_big_solve_count(CB_FWD_MR + (jb == 0 ? 0 : 2) + 1);
             if (jb == 0) {
                 hipLaunchKernelGGL((k_fwd_big_step_mr<true, KVX_BIG_RB, 1>), g1, dim3(SOLVE_NT), 0, st, ds, list, jb, Lx, Linv, X, X0, ldx, nrhs, WK, ldw, Wchild, Wout, wstride);
                 hipLaunchKernelGGL((k_fwd_big_step_mr<true, KVX_BIG_RB, 2>), g2, dim3(SOLVE_NT), 0, st, ds, list, jb, Lx, Linv, X, X0, ldx, nrhs, WK, ldw, Wchild, Wout, wstride);
@@ -1880,6 +1883,7 @@ void launch_fwd_big(hipStream_t st, const DevSym &ds, const int32_t *list, int c
         const int64_t wg64 = (int64_t)std::max(1, (rows + 63) / 64) * std::max(level_count, count);
         const bool narrow = wg64 <= narrow_wgs;
         dim3 grid((unsigned)std::max(1, narrow ? (rows + 63) / 64 : (rows + 255) / 256), (unsigned)count, (unsigned)nrhs);
+        chol_big_solve_count(CB_FWD + (narrow ? 0 : 2) + (jb == 0 ? 0 : 1));
         if (jb == 0) {
             if (narrow) hipLaunchKernelGGL((k_fwd_big_step<true, 64>), grid, dim3(SOLVE_NT), 0, st, ds, list, jb, Lx, Linv, X, X0, ldx, WK, ldw, Wchild, Wout, wstride);
             else hipLaunchKernelGGL((k_fwd_big_step<true, 256>), grid, dim3(SOLVE_NT), 0, st, ds, list, jb, Lx, Linv, X, X0, ldx, WK, ldw, Wchild, Wout, wstride);
@@ -1897,24 +1901,42 @@ void launch_bwd_big(hipStream_t st, const DevSym &ds, const int32_t *list, int c
     (void)max_m;
     if (nrhs >= KVX_BIG_MR_FROM) {
         const unsigned gz = (unsigned)((nrhs + KVX_BIG_RB - 1) / KVX_BIG_RB);
+        chol_big_solve_count(CB_BWD_MR_INIT);
         hipLaunchKernelGGL((k_bwd_big_init_mr<KVX_BIG_RB>), dim3((unsigned)((max_k + 3) / 4), (unsigned)count, gz), dim3(256), 0, st,
                            ds, list, Lx, X, ldx, nrhs, WK, ldw);
         for (int b = (max_k + SB - 1) / SB - 1; b >= 0; b--) {
+            chol_big_solve_count(CB_BWD_MR_STEP);
             hipLaunchKernelGGL((k_bwd_big_step_mr<KVX_BIG_RB, 1>), dim3(1, (unsigned)count, gz), dim3(SOLVE_NT), 0, st, ds, list, b, Lx, Linv,
                                X, ldx, nrhs, WK, ldw);
-            if (b > 0)
+            if (b > 0) {
+                chol_big_solve_count(CB_BWD_MR_STEP + 1);
                 hipLaunchKernelGGL((k_bwd_big_step_mr<KVX_BIG_RB, 2>), dim3((unsigned)(b * SB / NB), (unsigned)count, gz), dim3(SOLVE_NT), 0, st, ds, list, b, Lx, Linv,
                                    X, ldx, nrhs, WK, ldw);
+            }
         }
         return;
     }
+    chol_big_solve_count(CB_BWD_INIT);
     hipLaunchKernelGGL(k_bwd_big_init, dim3((unsigned)((max_k + 3) / 4), (unsigned)count, (unsigned)nrhs), dim3(256), 0, st,
                        ds, list, Lx, X, ldx, WK, ldw);
     for (int b = (max_k + SB - 1) / SB - 1; b >= 0; b--) {
         unsigned gx = (unsigned)std::max(1, b * SB / NB);
+        chol_big_solve_count(CB_BWD_STEP);
         hipLaunchKernelGGL(k_bwd_big_step, dim3(gx, (unsigned)count, (unsigned)nrhs), dim3(SOLVE_NT), 0, st, ds, list, b, Lx, Linv,
                            X, ldx, WK, ldw);
     }
 }
 
+static std::atomic<long long> g_chol_big_solve_counts[CB_NCOUNT];
+void chol_big_solve_count(int c) { g_chol_big_solve_counts[c].fetch_add(1, std::memory_order_relaxed); }
+
 }  // namespace kvx
+
+extern "C" int kvx_dbg_chol_big_solve_counts(int64_t *out, int reset)
+{
+    for (int c = 0; c < kvx::CB_NCOUNT; c++) {
+        const long long v = reset ? kvx::g_chol_big_solve_counts[c].exchange(0) : kvx::g_chol_big_solve_counts[c].load();
+        if (out) out[c] = (int64_t)v;
+    }
+    return kvx::CB_NCOUNT;
+}

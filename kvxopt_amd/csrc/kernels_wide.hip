@@ -720,11 +720,13 @@ void launch_wide_fwd_big(hipStream_t st, const DevSym &ds, const int32_t *list, 
                          int64_t wstride, const int32_t *inv_ptr, const int32_t *inv_src)
 {
     if (count <= 0 || nchunk <= 0) return;
+    chol_big_solve_count(CB_WIDE_FWD_ASM);
     hipLaunchKernelGGL(k_wide_fwd_big_asm, dim3((unsigned)((max_m + 63) / 64), (unsigned)count, (unsigned)nchunk), dim3(256), 0, st, ds, list,
                        Linv, XT, n, Wch, Wout, wstride, inv_ptr, inv_src);
     for (int jb = 0; jb < max_k; jb += 64) {
         const int rows = max_m - jb - 1;            // (a front whose block is shorter than 64 has more rows below: one workgroup more)
         if (rows <= 0) break;
+        chol_big_solve_count(CB_WIDE_FWD_STEP);
         hipLaunchKernelGGL(k_wide_fwd_big_step, dim3((unsigned)((rows + 63) / 64), (unsigned)count, (unsigned)nchunk), dim3(256), 0, st, ds, list,
                            jb, Lx, Linv, XT, n, Wout, wstride);
     }
@@ -734,10 +736,13 @@ void launch_wide_bwd_big(hipStream_t st, const DevSym &ds, const int32_t *list, 
 {
     if (count <= 0 || nchunk <= 0) return;
     const int nblk = (max_k + 63) / 64;
+    chol_big_solve_count(CB_WIDE_BWD_HEAD);
     hipLaunchKernelGGL(k_wide_bwd_big_head, dim3((unsigned)nblk, (unsigned)count, (unsigned)nchunk), dim3(256), 0, st, ds, list, Lx, Linv, XT, n);
-    for (int s = 0; s + 1 < nblk; s++)
+    for (int s = 0; s + 1 < nblk; s++) {
+        chol_big_solve_count(CB_WIDE_BWD_STEP);
         hipLaunchKernelGGL(k_wide_bwd_big_step, dim3((unsigned)(nblk - 1 - s), (unsigned)count, (unsigned)nchunk), dim3(256), 0, st, ds, list, s,
                            Lx, Linv, XT, n);
+    }
 }
 
 }  // namespace kvx
