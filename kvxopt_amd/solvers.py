@@ -20,6 +20,9 @@
     socp_batch(c, G, h, dims, A=None, b=None, options=None)                          no counterpart: B small dense SOCPs in one launch,
                                                                                      dims = {'l': ml, 'q': [...]} shared by the members
                                                                                      (-> socpbatch.socp_batch; reads its own `options` only)
+    sdp_batch(c, G, h, dims, A=None, b=None, options=None)                           no counterpart: B small dense SDPs in one launch,
+                                                                                     dims = {'l': ml, 's': [...]} shared by the members
+                                                                                     (-> sdpbatch.sdp_batch; reads its own `options` only)
     options                                                                         the module-level dict of the reference
 
 Like the reference, algorithm parameters come from `solvers.options` ('maxiters', 'abstol', 'reltol', 'feastol',
@@ -40,6 +43,7 @@ from . import lp as _lp
 from . import osqp as _osqp
 from .lpbatch import lp_batch  # noqa: F401
 from .qpbatch import qp_batch  # noqa: F401
+from .sdpbatch import sdp_batch  # noqa: F401
 from .socpbatch import socp_batch  # noqa: F401
 
 options = {}

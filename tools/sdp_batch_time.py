@@ -1,0 +1,143 @@
+"""Time solvers.sdp_batch against the only way to do the same work without it, a loop of this package's one-problem 's' driver
+(solvers.conelp, refinement 0), and its launch alone.
+
+    python tools/sdp_batch_time.py [--B 4096] [--n 16 --ml 4 --m 6 --ns 2 --p 4] [--loop 32] [--reps 5]
+
+B feasible members with matrices of their own, generated from a seed as the tests generate theirs (dense G with symmetric 's'
+blocks and 1 added to its diagonal, h = G x0 + s0, b = A x0, c = -G'z0 - A'y0 with s0, z0 positive definite on the blocks).  Three
+things are timed by the host clock around calls that end in a device synchronise, alternating, after one untimed pass of each:
+
+    batch       solvers.sdp_batch(c, G, h, dims, A, b): the upload of all data, the launch, the download of all results
+    launch      kvx_sdp_batch_solve_dev on buffers already on the device: the one launch alone
+    one by one  solvers.conelp (refinement 0) on each of the first --loop members
+
+Printed: the median and the spread (min - max) of each, the times per member and per iteration, the members' iteration counts, and
+how far the batch and the loop are apart in x.  The last line is the result as JSON.  Needs a GPU.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from kvxopt_amd import _lib, sdpbatch, solvers  # noqa: E402
+from tools.socp_batch_time import resident  # noqa: E402
+
+
+def blocks(ml, s):
+    o = ml
+    for m in s:
+        yield o, m
+        o += m * m
+
+
+def interior(ml, s, B, rng):
+    parts = [rng.uniform(0.5, 1.5, (B, ml))]
+    for m in s:
+        M = rng.standard_normal((B, m, m))
+        X = M @ M.transpose(0, 2, 1) / m + (0.5 + rng.random((B, 1, 1))) * np.eye(m)
+        parts.append(X.transpose(0, 2, 1).reshape(B, m * m))
+    return np.concatenate(parts, axis=1)[:, :, None]
+
+
+def members(n, ml, s, p, B, seed):
+    rng = np.random.default_rng(seed)
+    N = ml + sum(m * m for m in s)
+    G, A, x0 = rng.standard_normal((B, N, n)), rng.standard_normal((B, p, n)), rng.standard_normal((B, n, 1))
+    k = np.arange(min(N, n))
+    G[:, k, k] += 1.0
+    for o, m in blocks(ml, s):                             # symmetric coefficient blocks, from their lower triangles
+        X = G[:, o:o + m * m].reshape(B, m, m, n)          # [b, column, row, j]
+        iu = np.triu_indices(m, 1)
+        X[:, iu[1], iu[0]] = X[:, iu[0], iu[1]]
+        G[:, o:o + m * m] = X.reshape(B, m * m, n)
+    s0, z0, y0 = interior(ml, s, B, rng), interior(ml, s, B, rng), rng.standard_normal((B, p, 1))
+    h = (G @ x0 + s0)[:, :, 0]
+    c = -(G.transpose(0, 2, 1) @ z0 + A.transpose(0, 2, 1) @ y0)[:, :, 0]
+    return np.asfortranarray(c.T), G, np.asfortranarray(h.T), A, np.asfortranarray((A @ x0)[:, :, 0].T)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=4096)
+    ap.add_argument("--n", type=int, default=16)
+    ap.add_argument("--ml", type=int, default=4)
+    ap.add_argument("--m", type=int, default=6)
+    ap.add_argument("--ns", type=int, default=2)
+    ap.add_argument("--p", type=int, default=4)
+    ap.add_argument("--loop", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--seed", type=int, default=41)
+    a = ap.parse_args()
+    _lib.require_device()
+    B, n, ml, p, s = a.B, a.n, a.ml, a.p, [a.m] * a.ns
+    N = ml + sum(m * m for m in s)
+    dims = {"l": ml, "q": [], "s": s}
+    c, G, h, A, b = members(n, ml, s, p, B, a.seed)
+    if not p:
+        A = b = None
+    quiet = {"show_progress": False, "refinement": 0}
+
+    def batch():
+        t0 = time.perf_counter()
+        sol = solvers.sdp_batch(c, G, h, dims, A, b)
+        return time.perf_counter() - t0, sol
+
+    opt, _, data = sdpbatch._prepare(c, G, h, dims, A, b, None)
+    keep, out, dargs = resident(data, B, (n, p, N, N, 10, 1, 1))
+    mv = np.asarray(s, dtype=np.int64)
+    args = [B, n, ml, len(s), _lib.pi(mv) if s else None, p] + dargs + [opt.maxiters, opt.abstol, opt.reltol, opt.feastol] + [o.ptr for o in out]
+
+    def launch():
+        t0 = time.perf_counter()
+        _lib.raise_for(_lib.lib().kvx_sdp_batch_solve_dev(*args), "kvx_sdp_batch_solve_dev")
+        return time.perf_counter() - t0
+
+    def one_by_one():
+        t0 = time.perf_counter()
+        sols = [solvers.conelp(c[:, k], G[k], h[:, k], dims, None if A is None else A[k], None if b is None else b[:, k], options=quiet)
+                for k in range(a.loop)]
+        return time.perf_counter() - t0, sols
+
+    _, sol = batch()                                       # untimed: code objects, the pool's buffers, the symbolic caches
+    launch()
+    _, sols = one_by_one()
+    x_dev = out[0].download(np.float64, n * B).reshape(B, n).T
+    same = bool(np.array_equal(x_dev, sol["x"], equal_nan=True))
+    diff = max(float(np.linalg.norm(np.asarray(o["x"]).reshape(-1) - sol["x"][:, k]) / max(1.0, np.linalg.norm(o["x"]))) for k, o in enumerate(sols)
+               if o["x"] is not None)
+    apart = [(k, o["status"], o["iterations"], sol["status"][k], int(sol["iterations"][k])) for k, o in enumerate(sols)
+             if o["status"] != sol["status"][k] or o["iterations"] != sol["iterations"][k]]
+    agree = not apart
+    tb, tl, to = [], [], []
+    for _ in range(a.reps):
+        tb.append(batch()[0] * 1e3)
+        tl.append(launch() * 1e3)
+        to.append(one_by_one()[0] * 1e3)
+    mb, mlch, mo = (statistics.median(t) for t in (tb, tl, to))
+    its = sol["iterations"]
+    print("B = %d members at (n, ml, s, p) = (%d, %d, [%d] x %d, %d), N = %d: %d optimal, iterations %d - %d (mean %.2f)"
+          % (B, n, ml, a.m, a.ns, p, N, sol["status"].count("optimal"), its.min(), its.max(), its.mean()))
+    print("batch       %10.2f ms (%.2f - %.2f)   %8.2f us per member" % (mb, min(tb), max(tb), 1e3 * mb / B))
+    print("launch      %10.2f ms (%.2f - %.2f)   %8.2f us per member, %.3f us per member and iteration"
+          % (mlch, min(tl), max(tl), 1e3 * mlch / B, 1e3 * mlch / its.sum()))
+    print("one by one  %10.2f ms (%.2f - %.2f) for %d members: %.2f ms per solvers.conelp call" % (mo, min(to), max(to), a.loop, mo / a.loop))
+    print("the launch gives the bytes of the batch: %s; solvers.conelp and the batch agree on status and count: %s; max |x - x_conelp| / max(1, |x_conelp|) = %.2e"
+          % (same, agree, diff))
+    for k, st, it, bst, bit in apart:
+        print("member %d: solvers.conelp %s after %d, the batch %s after %d" % (k, st, it, bst, bit))
+    print(json.dumps({"B": B, "n": n, "ml": ml, "s": s, "p": p, "N": N, "reps": a.reps, "optimal": sol["status"].count("optimal"),
+                      "iterations_min": int(its.min()), "iterations_max": int(its.max()), "iterations_mean": float(its.mean()),
+                      "batch_ms": mb, "batch_ms_min": min(tb), "batch_ms_max": max(tb),
+                      "launch_ms": mlch, "launch_ms_min": min(tl), "launch_ms_max": max(tl), "launch_us_per_member": 1e3 * mlch / B,
+                      "launch_us_per_member_iteration": 1e3 * mlch / float(its.sum()),
+                      "loop_members": a.loop, "one_by_one_ms": mo, "one_by_one_ms_min": min(to), "one_by_one_ms_max": max(to),
+                      "conelp_ms_per_call": mo / a.loop, "launch_bytes_equal_batch": same, "status_and_count_agree": agree, "max_rel_diff_x": diff}))
+
+
+if __name__ == "__main__":
+    main()
