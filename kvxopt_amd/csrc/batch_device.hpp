@@ -1,7 +1,8 @@
-// Device helpers shared by the one-workgroup-per-member kernels k_qp_batch (qp_batch.hip) and k_lp_batch (lp_batch.hip): the
+// Device helpers shared by the four one-workgroup-per-member kernels k_qp_batch, k_lp_batch, k_socp_batch and k_sdp_batch: the
 // fixed-order wavefront and workgroup reductions, the triangle map of the assembly of S and K, the products with the
 // column-major matrices of a member in HBM, the Cholesky factor of an order <= 64 matrix in LDS and the two wavefront
-// substitutions.  A workgroup is 256 threads, four wavefronts.  Every sum has a fixed order: a thread's partial sum runs over its
+// substitutions.  batch_kkt.hpp builds the KKT core and the orthant on them, batch_conelp.hpp the conelp loop of the three cone
+// kernels.  A workgroup is 256 threads, four wavefronts.  Every sum has a fixed order: a thread's partial sum runs over its
 // indices ascending, a wavefront adds by an xor butterfly, the four wavefront sums are added 0..3.  No atomics.
 #pragma once
 #include <hip/hip_runtime.h>

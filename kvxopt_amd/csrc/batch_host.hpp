@@ -1,5 +1,8 @@
-// What the host entries of the batch solvers share (qp_batch_api.cpp, lp_batch_api.cpp): the refusal with its message, the
-// question for a device, and the device copies of one host call.
+// What the four batch solvers share outside their kernels (qp_batch, lp_batch, socp_batch, sdp_batch): the part of the kernel
+// arguments that is the same for all, and for the host entries (*_batch_api.cpp) the refusal with its message, the checks of
+// pointers, strides and options, the question for a device, the arguments packed from the C ABI, and the one ladder of upload,
+// allocation, launch, synchronisation and download.  A host entry keeps its limits with their texts, the placement of its cone
+// and its two extern "C" functions.
 #pragma once
 #include "../../include/kvxhip.h"
 #include "abi_guard.hpp"
@@ -17,6 +20,22 @@
     } while (0)
 
 namespace kvx {
+
+// The arguments every batch kernel takes; a solver's own struct derives from it and stays a trivially copyable aggregate.
+struct BatchArgs {
+    int64_t B;
+    int n, ml, p;                             // ml: the 'l' rows
+    // device pointers; matrices dense and column-major per member (G rows x n; A p x n); c: the linear term of the objective
+    // (q of a QP); s*: distance between two members in doubles, 0: one for all
+    const double *c, *G, *h, *A, *b;
+    int64_t sc, sG, sh, sA, sb;
+    int maxiters;
+    double abstol, reltol, feastol;
+    // results: x (n x B), y (p x B), s, z (rows x B), stats (the solver's NSTAT x B), iterations and exit (B each)
+    double *x, *y, *s, *z, *stats;
+    int64_t *iters, *exitc;
+};
+
 namespace batchhost {
 
 inline int refuse(const char *who, const std::string &why)
@@ -33,6 +52,43 @@ inline int need_device(const char *who)
         return KVX_EDEVICE;
     }
     return KVX_OK;
+}
+
+struct Part { const char *name; int64_t stride, size; };      // size: doubles of one member; stride 0 (shared) or >= size
+
+// What every entry checks after its own limits and before a device is asked for: the pointers, the member strides and the
+// options.  rows: the rows of G and h.  linear: the name of c.  first, first_ok: a solver's own leading data (P of a QP).
+inline int check_common(const char *who, const BatchArgs &a, int64_t rows, const char *linear = "c", const Part *first = nullptr,
+                        bool first_ok = true)
+{
+    if (!first_ok || !a.c || !a.G || !a.h || (a.p > 0 && (!a.A || !a.b))) return refuse(who, "a data pointer is NULL");
+    if (!a.x || !a.s || !a.z || !a.stats || !a.iters || !a.exitc || (a.p > 0 && !a.y)) return refuse(who, "a result pointer is NULL");
+    const int64_t n = a.n, p = a.p;
+    const Part parts[] = {first ? *first : Part{"", 0, 0}, {linear, a.sc, n}, {"G", a.sG, rows * n}, {"h", a.sh, rows},
+                          {"A", a.sA, p * n}, {"b", a.sb, p}};
+    for (const auto &t : parts)
+        if (t.stride != 0 && t.stride < t.size)
+            return refuse(who, std::string("the member stride of ") + t.name + " is 0 or at least its size");
+    if (a.maxiters < 1) return refuse(who, "maxiters must be a positive integer");
+    if (!(a.feastol > 0.0)) return refuse(who, "feastol must be a positive scalar");
+    if (!(a.reltol > 0.0) && !(a.abstol > 0.0)) return refuse(who, "at least one of reltol and abstol must be positive");
+    return KVX_OK;
+}
+
+// The common arguments as the C ABI passes them
+template <class Args>
+Args pack(int64_t B, int64_t n, int64_t ml, int64_t p, const double *c, int64_t sc, const double *G, int64_t sG, const double *h,
+          int64_t sh, const double *A, int64_t sA, const double *b, int64_t sb, int64_t maxiters, double abstol, double reltol,
+          double feastol, double *x, double *y, double *s, double *z, double *stats, int64_t *iterations, int64_t *exitcode)
+{
+    const auto small = [](int64_t v) { return (int)(v < -1 ? -1 : (v > 1000000000 ? 1000000000 : v)); };    // the checks see the range
+    Args a = {};
+    a.B = B; a.n = small(n); a.ml = small(ml); a.p = small(p);
+    a.c = c; a.G = G; a.h = h; a.A = A; a.b = b;
+    a.sc = sc; a.sG = sG; a.sh = sh; a.sA = sA; a.sb = sb;
+    a.maxiters = small(maxiters); a.abstol = abstol; a.reltol = reltol; a.feastol = feastol;
+    a.x = x; a.y = y; a.s = s; a.z = z; a.stats = stats; a.iters = iterations; a.exitc = exitcode;
+    return a;
 }
 
 struct Buffers {                              // the device copies of one host call, given back to the pool on every path
@@ -58,6 +114,46 @@ struct Buffers {                              // the device copies of one host c
 inline int down(void *h, const void *d, int64_t count)
 {
     if (count > 0) HIPCHK(hipMemcpy(h, d, (size_t)count * 8, hipMemcpyDeviceToHost));
+    return KVX_OK;
+}
+
+// The checked batch `a`, every pointer a device pointer (the _dev entry), through launch(args) and a synchronisation
+template <class Args, class Launch>
+int solve_dev(const Args &a, Launch launch)
+{
+    HIPCHK(launch(a));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    return KVX_OK;
+}
+
+// The checked batch `h` of host pointers: the data goes up, launch(args) and a synchronisation, the results come down, and the
+// copies return to the pool on every path.  rows: the rows of G, h, s and z; nstat: the stats of a member.  first: a solver's
+// own leading data (P of a QP) with its stride and size.
+template <class Args, class Launch>
+int solve_host(const Args &h, int64_t rows, int64_t nstat, Launch launch, const double *Args::*first = nullptr, int64_t sfirst = 0,
+               int64_t nfirst = 0)
+{
+    const int64_t B = h.B, n = h.n, p = h.p;
+    const auto extent = [&](int64_t stride, int64_t size) { return stride ? (B - 1) * stride + size : size; };
+    Args d = h;
+    Buffers buf;
+    int rc;
+    double *iters = nullptr, *exitc = nullptr;                     // int64 results travel in 8-byte slots of the same pool
+    if ((first && (rc = buf.up(&(d.*first), h.*first, extent(sfirst, nfirst)))) || (rc = buf.up(&d.c, h.c, extent(h.sc, n))) ||
+        (rc = buf.up(&d.G, h.G, extent(h.sG, rows * n))) || (rc = buf.up(&d.h, h.h, extent(h.sh, rows))) ||
+        (p > 0 && ((rc = buf.up(&d.A, h.A, extent(h.sA, p * n))) || (rc = buf.up(&d.b, h.b, extent(h.sb, p))))) ||
+        (rc = buf.get(&d.x, n * B)) || (rc = buf.get(&d.y, p * B)) || (rc = buf.get(&d.s, rows * B)) ||
+        (rc = buf.get(&d.z, rows * B)) || (rc = buf.get(&d.stats, nstat * B)) || (rc = buf.get(&iters, B)) ||
+        (rc = buf.get(&exitc, B)))
+        return rc;
+    d.iters = reinterpret_cast<int64_t *>(iters);
+    d.exitc = reinterpret_cast<int64_t *>(exitc);
+    HIPCHK(launch(d));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    if ((rc = down(h.x, d.x, n * B)) || (rc = down(h.y, d.y, p * B)) || (rc = down(h.s, d.s, rows * B)) ||
+        (rc = down(h.z, d.z, rows * B)) || (rc = down(h.stats, d.stats, nstat * B)) || (rc = down(h.iters, d.iters, B)) ||
+        (rc = down(h.exitc, d.exitc, B)))
+        return rc;
     return KVX_OK;
 }
 

@@ -14,14 +14,14 @@
 // (!(pivot > 0 && pivot < inf) fails) and makes every comparison of the stopping test false, so such a member ends with exit 3,
 // 2 or 1.
 #include "qp_batch.hpp"
-#include "batch_device.hpp"
+#include "batch_kkt.hpp"
 
 #include <cmath>
 
 namespace kvx {
 namespace {
 
-using namespace batchdev;                     // the reductions, tri_map, row_dot, gemv_t_add, chol_lds, the substitutions
+using namespace batchdev;                     // the reductions, row_dot, gemv_t_add, chol_lds; the KKT core and the orthant
 static_assert(NT == QPB_THREADS, "the shared helpers are written for the workgroup of k_qp_batch");
 
 struct Layout {                               // offsets in doubles from the LDS base; every part starts on 16 bytes
@@ -48,100 +48,39 @@ __host__ __device__ inline Layout layout(int n, int ml, int p)
     return L;
 }
 
-struct Member {                               // one member's data in HBM and its vectors and matrices in LDS
-    int n, ml, p, ldn, ldp;
-    const double *P, *q, *G, *h, *A, *b;
-    double *S, *T, *X, *K, *x, *dx, *rx, *y, *dy, *ry, *s, *z, *d, *di, *lm, *ds, *dz, *rz, *ws3, *red;
+struct Member : KktMem {                      // one member's data in HBM and its vectors and matrices in LDS
+    int ml;
+    const double *P, *q, *G, *h, *b;
+    double *x, *dx, *rx, *y, *dy, *ry, *s, *z, *d, *di, *lm, *ds, *dz, *rz, *ws3, *red;
 };
 
 // The KKT factorisation in the scaling di (misc.py:1436-1487): S = P + G' diag(di^2) G, its factor L in place, and for p > 0
-// X = L^-1 A', K = X'X and its factor.  false on a failed pivot.  Barriers before (the caller's) and after.
-__device__ bool factor(const Member &M)
+// X, K and its factor (batch_kkt.hpp).  false on a failed pivot.  Barriers before (the caller's) and after.
+__device__ __forceinline__ bool factor(const Member &M)
 {
-    const int tid = threadIdx.x, n = M.n, ml = M.ml, p = M.p, ldn = M.ldn, ldp = M.ldp;
+    const int tid = threadIdx.x, n = M.n, ml = M.ml, ldn = M.ldn;
     for (int e = tid; e < n * n; e += NT) {
         const int j = e / n, i = e - j * n;
         if (i >= j) M.S[i + j * ldn] = M.P[i + j * n];
     }
-    const int cnt = tri_count(n);
     for (int k0 = 0; k0 < ml; k0 += QPB_TILE) {
         const int kt = min((int)QPB_TILE, ml - k0);
         __syncthreads();                                   // the staged rows of the previous step have been read
-        for (int e = tid; e < QPB_TILE * n; e += NT) {
-            const int kk = e & (QPB_TILE - 1), c = e / QPB_TILE;
-            if (kk < kt) M.T[kk * ldn + c] = M.di[k0 + kk] * M.G[k0 + kk + (int64_t)c * ml];
-        }
+        orth_stage<QPB_TILE>(M, M.G, ml, M.di, k0, kt);
         __syncthreads();
-        for (int e = tid; e < cnt; e += NT) {
-            int i, j;
-            if (!tri_map(e, n, i, j)) continue;
-            double acc = 0.0;
-            for (int kk = 0; kk < kt; kk++) acc += M.T[kk * ldn + i] * M.T[kk * ldn + j];
-            M.S[i + j * ldn] += acc;
-        }
+        kkt_s_add_rows(M, kt);
     }
     __syncthreads();
-    if (!chol_lds(M.S, ldn, n)) return false;
-    if (p == 0) return true;
-    const int lane = tid & 63, w = tid >> 6;
-    for (int a = w; a < p; a += NW) {                      // the staged rows are dead: X may take their place
-        double v = lane < n ? M.A[a + (int64_t)lane * p] : 0.0;
-        v = wave_trsv_n(M.S, ldn, n, v);
-        if (lane < n) M.X[lane + a * ldn] = v;
-    }
-    __syncthreads();
-    for (int e = tid; e < tri_count(p); e += NT) {
-        int a, c;
-        if (!tri_map(e, p, a, c)) continue;
-        double acc = 0.0;
-        for (int i = 0; i < n; i++) acc += M.X[i + a * ldn] * M.X[i + c * ldn];
-        M.K[a + c * ldp] = acc;
-    }
-    __syncthreads();
-    return chol_lds(M.K, ldp, p);
+    return chol_lds(M.S, ldn, n) && kkt_equalities(M);
 }
 
 // misc.py:1489-1563 on the LDS vectors (vx, vy, vz) = (bx, by, bz): on return ux, uy, W uz.  Barriers before (the caller's)
 // and after.
-__device__ void kkt_solve(const Member &M, double *vx, double *vy, double *vz)
+__device__ __forceinline__ void kkt_solve(const Member &M, double *vx, double *vy, double *vz)
 {
-    const int tid = threadIdx.x, n = M.n, ml = M.ml, p = M.p, lane = tid & 63, w = tid >> 6;
-    for (int k = tid; k < ml; k += NT) vz[k] *= M.di[k];                                   // z := W^-T bz
-    __syncthreads();
-    gemv_t_add(M.G, ml, n, vz, M.di, 1.0, vx);                                             // x += G' W^-1 z
-    __syncthreads();
-    if (w == 0) {                                                                          // x := L^-1 x
-        const double v = wave_trsv_n(M.S, M.ldn, n, lane < n ? vx[lane] : 0.0);
-        if (lane < n) vx[lane] = v;
-    }
-    __syncthreads();
-    if (p > 0) {
-        if (tid < p) {                                                                     // y := X'x - y
-            double acc = 0.0;
-            for (int i = 0; i < n; i++) acc += M.X[i + tid * M.ldn] * vx[i];
-            vy[tid] = acc - vy[tid];
-        }
-        __syncthreads();
-        if (w == 0) {                                                                      // y := K^-1 y
-            double v = wave_trsv_n(M.K, M.ldp, p, lane < p ? vy[lane] : 0.0);
-            v = wave_trsv_t(M.K, M.ldp, p, v);
-            if (lane < p) vy[lane] = v;
-        }
-        __syncthreads();
-        if (tid < n) {                                                                     // x := x - X y
-            double acc = 0.0;
-            for (int a = 0; a < p; a++) acc += M.X[tid + a * M.ldn] * vy[a];
-            vx[tid] -= acc;
-        }
-        __syncthreads();
-    }
-    if (w == 0) {                                                                          // x := L^-T x
-        const double v = wave_trsv_t(M.S, M.ldn, n, lane < n ? vx[lane] : 0.0);
-        if (lane < n) vx[lane] = v;
-    }
-    __syncthreads();
-    for (int k = tid; k < ml; k += NT) vz[k] = M.di[k] * row_dot(M.G, ml, n, k, vx) - vz[k];   // W uz = W^-T (G ux - bz)
-    __syncthreads();
+    orth_kkt_before(M.G, M.ml, M.n, M.di, vx, vz);
+    kkt_reduced_solve(M, false, vx, vy);
+    orth_kkt_after(M.G, M.ml, M.n, M.di, vx, vz);
 }
 
 __global__ void __launch_bounds__(QPB_THREADS) k_qp_batch(QpBatchArgs a)
@@ -152,7 +91,7 @@ __global__ void __launch_bounds__(QPB_THREADS) k_qp_batch(QpBatchArgs a)
     const Layout L = layout(n, ml, p);
     Member M;
     M.n = n; M.ml = ml; M.p = p; M.ldn = L.ldn; M.ldp = L.ldp;
-    M.P = a.P + bm * a.sP; M.q = a.q + bm * a.sq; M.G = a.G + bm * a.sG; M.h = a.h + bm * a.sh;
+    M.P = a.P + bm * a.sP; M.q = a.c + bm * a.sc; M.G = a.G + bm * a.sG; M.h = a.h + bm * a.sh;
     M.A = p ? a.A + bm * a.sA : nullptr; M.b = p ? a.b + bm * a.sb : nullptr;
     M.S = lds + L.S; M.T = lds + L.XK; M.X = lds + L.X; M.K = lds + L.K;
     M.x = lds + L.x; M.dx = lds + L.dx; M.rx = lds + L.rx; M.y = lds + L.y; M.dy = lds + L.dy; M.ry = lds + L.ry;
@@ -246,11 +185,7 @@ __global__ void __launch_bounds__(QPB_THREADS) k_qp_batch(QpBatchArgs a)
         if (pres <= a.feastol && dres <= a.feastol && (gap <= a.abstol || relgap <= a.reltol)) { code = QPB_OPTIMAL; break; }
 
         // ---- scaling of the first iteration (misc.py:284-287), the factorisation
-        if (iters == 0)
-            for (int k = tid; k < ml; k += NT) {
-                const double sk = M.s[k], zk = M.z[k], dk = sqrt(sk / zk);
-                M.d[k] = dk; M.di[k] = 1.0 / dk; M.lm[k] = sqrt(sk * zk);
-            }
+        if (iters == 0) orth_first_scaling(ml, M.s, M.z, M.d, M.di, M.lm);
         __syncthreads();
         if (!factor(M)) { code = iters == 0 ? QPB_RANK : QPB_SINGULAR; break; }
 
@@ -293,14 +228,7 @@ __global__ void __launch_bounds__(QPB_THREADS) k_qp_batch(QpBatchArgs a)
         // ---- the step, the scaling update (misc.py:444-464), s and z of the next iteration (coneprog.py:2459-2547)
         if (tid < n) M.x[tid] += step * M.dx[tid];
         if (tid < p) M.y[tid] += step * M.dy[tid];
-        double g[1] = {0.0};
-        for (int k = tid; k < ml; k += NT) {
-            const double lk = M.lm[k], rs = sqrt((1.0 + step * M.ds[k]) * lk), rz = sqrt((1.0 + step * M.dz[k]) * lk);
-            const double dk = M.d[k] * rs / rz, dik = 1.0 / dk, ln = rs * rz;
-            M.d[k] = dk; M.di[k] = dik; M.lm[k] = ln;
-            M.s[k] = dk * ln; M.z[k] = dik * ln;
-            g[0] += ln * ln;
-        }
+        double g[1] = {orth_update(ml, step, M.ds, M.dz, M.d, M.di, M.lm, M.s, M.z)};
         blk_reduce<1, false>(g, M.red);
         gap = g[0];
     }

@@ -1,10 +1,9 @@
 // k_sdp_batch: one workgroup (256 threads, four wavefronts) carries one small dense semidefinite program from its starting point
-// to its status or its infeasibility certificate (sdp_batch.hpp).  It is k_lp_batch (lp_batch.hip) -- the device restatement of
-// _ipm.conelp_start / _ipm.conelp_loop with refinement 0 and the Newton solve of misc.kkt_chol2 -- on the cone
-// K = R^ml_+ x S^{m_0}_+ x ...: the 'l' rows are treated as there, the 's' rows by the reference's own operations, the ones
-// csrc/kkt_s.hip carries as stand-alone kernels: misc.compute_scaling / update_scaling (misc.py:354-419, 582-634), scale, scale2,
-// sprod, sinv, sdot and max_step (misc_solvers.c:188-240, 343-397, 700-770, 845-882, 1029-1046, 1086-1160), strung together as
-// cone.py::_ConeEngine strings them (coneprog.py:1130-1195 f6_no_ir, 1248-1333, 1336-1436).
+// to its status or its infeasibility certificate (sdp_batch.hpp).  It is conelp_member (batch_conelp.hpp) on the cone
+// K = R^ml_+ x S^{m_0}_+ x ...: the 'l' rows are the orthant of that header, the 's' rows are treated by the reference's own
+// operations, the ones csrc/kkt_s.hip carries as stand-alone kernels: misc.compute_scaling / update_scaling (misc.py:354-419,
+// 582-634), scale, scale2, sprod, sinv, sdot and max_step (misc_solvers.c:188-240, 343-397, 700-770, 845-882, 1029-1046,
+// 1086-1160), strung together as cone.py::_ConeEngine strings them.
 //
 // Vectors of the cone lie in LDS with every 's' block as its full symmetric m x m matrix, column-major with leading dimension m:
 // with a thread per entry a wavefront reads consecutive rows of one operand and at most 64 / m entries of the other, which are
@@ -28,12 +27,10 @@
 // (a, b), a >= b, as rti_k[:, a]'w_j.  G's 's' rows are read m_k times per factorisation, from L2; the scaled rows never leave
 // LDS, which keeps the Gram form and spares the _dev entry a workspace argument.
 //
-// Sums over all rows have the fixed order of batch_device.hpp.  No atomics, no communication between workgroups; every scalar is
-// computed by every thread from the same reduced values, so every branch around a barrier is workgroup-uniform.  Every loop is
-// bounded by maxiters, n, N, p, ns, m_k or SDPB_SWEEPS.  A NaN or Inf never passes a pivot test and makes every comparison of the
-// stopping tests false, and a block that is not finite is not iterated on, so such a member ends with exit 3, 2 or 1.
+// Sums over all rows have the fixed order of batch_device.hpp.  Every loop of this file is bounded by n, N, ns, m_k or
+// SDPB_SWEEPS.  A block that is not finite is not iterated on.
 #include "sdp_batch.hpp"
-#include "batch_device.hpp"
+#include "batch_conelp.hpp"
 
 #include <cmath>
 
@@ -46,6 +43,7 @@ static_assert(SDPB_MAX_M * SDPB_MAX_M <= NT, "a thread per entry of a block");
 constexpr int MM = SDPB_MAX_M * SDPB_MAX_M;
 constexpr int STAGE = SDPB_TILE + SDPB_MAX_M;      // the staged rows and, behind them, w of the block column being staged
 constexpr double RT2 = 1.41421356237309504880;
+static_assert(CONELP_NSTAT == SDPB_NSTAT, "the stats of conelp_member");
 
 struct Layout {                               // offsets in doubles from the LDS base; every part starts on 16 bytes
     int ldn, ldp;
@@ -80,11 +78,9 @@ __host__ __device__ inline Layout layout(int n, int ml, int N, int Nd, int Np, i
     return L;
 }
 
-struct Member {                               // one member's data in HBM and its vectors and matrices in LDS
-    int n, ml, ns, N, Nd, Np, p, ldn, ldp;
-    const double *c, *G, *h, *A, *b;
-    double *S, *T, *X, *K, *x, *dx, *rx, *x1, *y, *dy, *ry, *y1, *s, *z, *ds, *dz, *rz, *ws3, *z1, *tw, *th, *r, *rti, *lm, *d, *di,
-        *sgs, *sgz, *wa, *wb, *wc, *wd, *nrm, *red;
+struct Member : ConelpMem {                   // N = ml + sum m_k^2
+    int ml, ns, Nd, Np;
+    double *tw, *th, *r, *rti, *lm, *d, *di, *sgs, *sgz, *wa, *wb, *wc, *wd, *nrm;
     int *bo, *bl;                             // bo[k]: the first row of block k; bl[k]: the first entry of lmbda_k; [ns]: N, Nd
     int *flag;
     const unsigned short *prow, *pmir;
@@ -363,35 +359,18 @@ __device__ __forceinline__ void load_sym(const Member &M, const double *v, doubl
 // The lower triangle of S = Gs'Gs [+ A'A], Gs = W^-T G packed, in LDS.  Barriers before (the caller's) and after.
 __device__ __forceinline__ void assemble(const Member &M, bool sing)
 {
-    const int tid = threadIdx.x, n = M.n, ml = M.ml, N = M.N, p = M.p, ldn = M.ldn;
-    const int cnt = tri_count(n);
-    for (int e = tid; e < cnt; e += NT) {
-        int i, j;
-        if (!tri_map(e, n, i, j)) continue;
-        double acc = 0.0;
-        if (sing)
-            for (int a = 0; a < p; a++) acc += M.A[a + (int64_t)i * p] * M.A[a + (int64_t)j * p];
-        M.S[i + j * ldn] = acc;
-    }
+    const int tid = threadIdx.x, n = M.n, ml = M.ml, N = M.N, ldn = M.ldn;
+    kkt_s_init(M, sing);
     int fill = 0;                                          // staged rows not yet added to S
     const auto flush = [&]() {                             // S += T'T over the staged rows; the rows are free afterwards
         __syncthreads();
-        for (int e = tid; e < cnt; e += NT) {
-            int i, j;
-            if (!tri_map(e, n, i, j)) continue;
-            double acc = 0.0;
-            for (int kk = 0; kk < fill; kk++) acc += M.T[kk * ldn + i] * M.T[kk * ldn + j];
-            M.S[i + j * ldn] += acc;
-        }
+        kkt_s_add_rows(M, fill);
         __syncthreads();
         fill = 0;
     };
     for (int k0 = 0; k0 < ml; k0 += SDPB_TILE) {
         const int kt = min((int)SDPB_TILE, ml - k0);
-        for (int e = tid; e < SDPB_TILE * n; e += NT) {
-            const int kk = e & (SDPB_TILE - 1), col = e / SDPB_TILE;
-            if (kk < kt) M.T[kk * ldn + col] = M.di[k0 + kk] * M.G[k0 + kk + (int64_t)col * N];
-        }
+        orth_stage<SDPB_TILE>(M, M.G, N, M.di, k0, kt);
         fill = kt;
         if (fill == SDPB_TILE) flush();
     }
@@ -422,143 +401,6 @@ __device__ __forceinline__ void assemble(const Member &M, bool sing)
     if (fill) flush();
     __syncthreads();
 }
-
-// The KKT factorisation in the scaling W (misc.py:1395-1487), as in lp_batch.hip; also th = W^-T h.  false on a failed pivot.
-// Barriers before (the caller's) and after.
-__device__ __forceinline__ bool factor(const Member &M, bool &sing, bool first)
-{
-    const int tid = threadIdx.x, n = M.n, p = M.p, ldn = M.ldn, ldp = M.ldp;
-    load_sym(M, M.h, M.th);
-    __syncthreads();
-    wscale(M, M.th, M.th, true, true);
-    assemble(M, sing);
-    if (!chol_lds(M.S, ldn, n)) {
-        if (!first || p == 0) return false;
-        sing = true;
-        __syncthreads();                                   // every thread has read the failed pivot
-        assemble(M, true);
-        if (!chol_lds(M.S, ldn, n)) return false;
-    }
-    if (p == 0) return true;
-    const int lane = tid & 63, w = tid >> 6;
-    for (int a = w; a < p; a += NW) {                      // the staged rows are dead: X may take their place
-        double v = lane < n ? M.A[a + (int64_t)lane * p] : 0.0;
-        v = wave_trsv_n(M.S, ldn, n, v);
-        if (lane < n) M.X[lane + a * ldn] = v;
-    }
-    __syncthreads();
-    for (int e = tid; e < tri_count(p); e += NT) {
-        int a, c;
-        if (!tri_map(e, p, a, c)) continue;
-        double acc = 0.0;
-        for (int i = 0; i < n; i++) acc += M.X[i + a * ldn] * M.X[i + c * ldn];
-        M.K[a + c * ldp] = acc;
-    }
-    __syncthreads();
-    return chol_lds(M.K, ldp, p);
-}
-
-// misc.py:1489-1563 on the LDS vectors (vx, vy, vz) = (bx, by, bz): on return ux, uy, W uz.  Barriers before (the caller's)
-// and after.
-__device__ __forceinline__ void kkt_solve(const Member &M, bool sing, double *vx, double *vy, double *vz)
-{
-    const int tid = threadIdx.x, n = M.n, N = M.N, p = M.p, lane = tid & 63, w = tid >> 6;
-    wscale(M, vz, vz, true, true);                                                         // z := W^-T bz
-    wscale(M, vz, M.tw, true, false);
-    gemv_t_packed(M, M.tw, 1.0, vx);                                                       // x += G' W^-1 z
-    __syncthreads();
-    if (sing) {                                                                            // x += A' by
-        gemv_t_add(M.A, p, n, vy, nullptr, 1.0, vx);
-        __syncthreads();
-    }
-    if (w == 0) {                                                                          // x := L^-1 x
-        const double v = wave_trsv_n(M.S, M.ldn, n, lane < n ? vx[lane] : 0.0);
-        if (lane < n) vx[lane] = v;
-    }
-    __syncthreads();
-    if (p > 0) {
-        if (tid < p) {                                                                     // y := X'x - y
-            double acc = 0.0;
-            for (int i = 0; i < n; i++) acc += M.X[i + tid * M.ldn] * vx[i];
-            vy[tid] = acc - vy[tid];
-        }
-        __syncthreads();
-        if (w == 0) {                                                                      // y := K^-1 y
-            double v = wave_trsv_n(M.K, M.ldp, p, lane < p ? vy[lane] : 0.0);
-            v = wave_trsv_t(M.K, M.ldp, p, v);
-            if (lane < p) vy[lane] = v;
-        }
-        __syncthreads();
-        if (tid < n) {                                                                     // x := x - X y
-            double acc = 0.0;
-            for (int a = 0; a < p; a++) acc += M.X[tid + a * M.ldn] * vy[a];
-            vx[tid] -= acc;
-        }
-        __syncthreads();
-    }
-    if (w == 0) {                                                                          // x := L^-T x
-        const double v = wave_trsv_t(M.S, M.ldn, n, lane < n ? vx[lane] : 0.0);
-        if (lane < n) vx[lane] = v;
-    }
-    __syncthreads();
-    for (int q = tid; q < M.Np; q += NT) {
-        const double t = row_dot(M.G, N, n, M.prow[q], vx);
-        M.tw[M.prow[q]] = t; M.tw[M.pmir[q]] = t;
-    }
-    __syncthreads();
-    wscale(M, M.tw, M.tw, true, true);
-    for (int k = tid; k < N; k += NT) vz[k] = M.tw[k] - vz[k];                             // W uz = W^-T G ux - W^-T bz
-    __syncthreads();
-}
-
-// coneprog.py:861-896 as in lp_batch.hip, on the packed rows with the weights of misc.sdot.  Barriers before (the caller's) and
-// after.
-__device__ __forceinline__ void residuals(const Member &M, double tau, double (&r)[9])
-{
-    const int tid = threadIdx.x, n = M.n, N = M.N, p = M.p;
-    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
-    if (tid < n) M.rx[tid] = 0.0;
-    if (tid < p) {
-        const double t = row_dot(M.A, p, n, tid, M.x), bk = M.b[tid], u = t - tau * bk;
-        M.ry[tid] = u;
-        v[2] = t * t; v[3] = u * u;
-        w[1] = bk * M.y[tid];
-    }
-    for (int q = tid; q < M.Np; q += NT) {
-        const int k = M.prow[q];
-        const double wq = weight(M, q), t = row_dot(M.G, N, n, k, M.x) + M.s[k], hk = M.h[k], u = t - tau * hk;
-        M.rz[k] = u; M.rz[M.pmir[q]] = u;
-        v[4] += wq * (t * t); v[5] += wq * (u * u);
-        w[2] += wq * (hk * M.z[k]);
-    }
-    __syncthreads();
-    if (p > 0) gemv_t_add(M.A, p, n, M.y, nullptr, -1.0, M.rx);
-    __syncthreads();
-    gemv_t_packed(M, M.z, -1.0, M.rx);
-    __syncthreads();
-    if (tid < n) {
-        const double t = M.rx[tid], ck = M.c[tid], u = t - tau * ck;
-        M.rx[tid] = u;
-        v[0] = t * t; v[1] = u * u;
-        w[0] = ck * M.x[tid];
-    }
-    blk_reduce<6, false>(v, M.red);
-    blk_reduce<3, false>(w, M.red);                        // its barriers also publish rx
-#pragma unroll
-    for (int k = 0; k < 6; k++) r[k] = v[k];
-#pragma unroll
-    for (int k = 0; k < 3; k++) r[6 + k] = w[k];
-}
-
-// lmbda'lmbda.  Barriers before (the caller's) and after.
-__device__ __forceinline__ double lam_sq(const Member &M)
-{
-    double g[1] = {0.0};
-    for (int k = threadIdx.x; k < M.Nd; k += NT) g[0] += M.lm[k] * M.lm[k];
-    blk_reduce<1, false>(g, M.red);
-    return g[0];
-}
-
 // misc.compute_scaling on the 's' blocks (misc.py:354-419): r_k, rti_k and lmbda_k from s_k and z_k.  false when an s_k or z_k is
 // not positive definite.  Barriers before (the caller's) and after.
 __device__ __forceinline__ bool blocks_scaling(const Member &M)
@@ -584,276 +426,149 @@ __device__ __forceinline__ bool blocks_scaling(const Member &M)
     return true;
 }
 
-__global__ void __launch_bounds__(SDPB_THREADS) k_sdp_batch(SdpBatchArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int tid = threadIdx.x, n = a.n, ml = a.ml, ns = a.ns, N = a.N, Nd = a.Nd, Np = a.Np, p = a.p;
-    const int64_t bm = blockIdx.x;
-    const Layout L = layout(n, ml, N, Nd, Np, ns, p);
-    Member M;
-    M.n = n; M.ml = ml; M.ns = ns; M.N = N; M.Nd = Nd; M.Np = Np; M.p = p; M.ldn = L.ldn; M.ldp = L.ldp;
-    M.c = a.c + bm * a.sc; M.G = a.G + bm * a.sG; M.h = a.h + bm * a.sh;
-    M.A = p ? a.A + bm * a.sA : nullptr; M.b = p ? a.b + bm * a.sb : nullptr;
-    M.S = lds + L.S; M.T = lds + L.XK; M.X = lds + L.X; M.K = lds + L.K;
-    M.x = lds + L.x; M.dx = lds + L.dx; M.rx = lds + L.rx; M.x1 = lds + L.x1;
-    M.y = lds + L.y; M.dy = lds + L.dy; M.ry = lds + L.ry; M.y1 = lds + L.y1;
-    M.s = lds + L.s; M.z = lds + L.z; M.ds = lds + L.ds; M.dz = lds + L.dz; M.rz = lds + L.rz; M.ws3 = lds + L.ws3;
-    M.z1 = lds + L.z1; M.tw = lds + L.tw; M.th = lds + L.th; M.r = lds + L.r; M.rti = lds + L.rti;
-    M.lm = lds + L.lm; M.d = lds + L.d; M.di = lds + L.di; M.sgs = lds + L.sgs; M.sgz = lds + L.sgz;
-    M.wa = lds + L.wk; M.wb = M.wa + MM; M.wc = M.wb + MM; M.wd = M.wc + MM; M.nrm = lds + L.nrm;
-    M.red = lds + L.red;
-    M.bo = reinterpret_cast<int *>(lds + L.blk); M.bl = M.bo + (ns + 1);
-    M.flag = reinterpret_cast<int *>(lds + L.flag);
-    unsigned short *prow = reinterpret_cast<unsigned short *>(lds + L.prow), *pmir = reinterpret_cast<unsigned short *>(lds + L.pmir);
-    M.prow = prow; M.pmir = pmir;
-    double *xo = a.x + bm * n, *yo = p ? a.y + bm * p : nullptr, *so = a.s + bm * N, *zo = a.z + bm * N, *st = a.stats + bm * SDPB_NSTAT;
 
-    // ---- the cone: the first row and the first lmbda of every block, the packed rows and their mirror images
-    if (tid <= ns) {
-        int o = ml, ol = ml;
-        for (int k = 0; k < tid; k++) { o += a.m[k] * a.m[k]; ol += a.m[k]; }
-        M.bo[tid] = o; M.bl[tid] = ol;
-    }
-    for (int k = tid; k < ml; k += NT) { prow[k] = (unsigned short)k; pmir[k] = (unsigned short)k; }
-    __syncthreads();
+struct PackedRow {                            // a packed row of the cone: its entry, its mirror image, its weight
+    int k, mir;
+    double wq;
+    __device__ __forceinline__ double w(double v) const { return wq * v; }
+    __device__ __forceinline__ void put(double *vec, double v) const { vec[k] = v; vec[mir] = v; }
+};
+
+struct Cone {                                 // the cone of conelp_member: the orthant for the 'l' rows, the code here for 's'
+    const Member &M;
+
+    __device__ __forceinline__ int lmbda_len() const { return M.Nd; }
+    template <class F>
+    __device__ __forceinline__ void for_rows(F f) const
     {
-        int po = ml;
+        for (int q = threadIdx.x; q < M.Np; q += NT) f(PackedRow{M.prow[q], M.pmir[q], weight(M, q)});
+    }
+    __device__ __forceinline__ void load_h(double *out) const { load_sym(M, M.h, out); }
+    __device__ __forceinline__ void start() const                                   // d = di = 1, r_k = rti_k = I
+    {
+        const int tid = threadIdx.x, ml = M.ml, ns = M.ns, N = M.N;
+        for (int k = tid; k < ml; k += NT) { M.d[k] = 1.0; M.di[k] = 1.0; }
+        for (int k = tid; k < N; k += NT) M.z[k] = 0.0;
         for (int k = 0; k < ns; k++) {
-            const int o = M.bo[k], m = M.order(k);
-            for (int e = tid; e < m * m; e += NT) {
-                const int i = e % m, j = e / m;
-                if (i < j) continue;
-                const int q = po + j * m - (j * (j - 1)) / 2 + (i - j);
-                prow[q] = (unsigned short)(o + i + j * m);
-                pmir[q] = (unsigned short)(o + j + i * m);
-            }
-            po += (m * (m + 1)) / 2;
+            const int o = M.bo[k] - ml, m = M.order(k);
+            for (int e = tid; e < m * m; e += NT) { const double v = (e % m == e / m) ? 1.0 : 0.0; M.r[o + e] = v; M.rti[o + e] = v; }
         }
-    }
-
-    int code = SDPB_RANK, iters = 0;                       // solvers.sdp: ValueError("Rank(A) < p or Rank([G; A]) < n")
-    bool sing = false, at0 = false;
-    double tau = 1.0, kappa = 1.0, dg = 1.0, dgi = 1.0, lg = 1.0, gap = NAN, lam2 = 0.0;
-    double relgap = NAN, pcost = NAN, dcost = NAN, pres = NAN, dres = NAN, pinfres = NAN, dinfres = NAN;
-    double sp = 0.0, sd = 0.0;                             // what x, s and y, z are scaled by at the end; NaN: not returned
-    double resx0 = 1.0, resy0 = 1.0, resz0 = 1.0;
-
-    // ---- starting point (coneprog.py:662-842): W = I, that is d = di = 1, r_k = rti_k = I
-    for (int k = tid; k < ml; k += NT) { M.d[k] = 1.0; M.di[k] = 1.0; }
-    for (int k = tid; k < N; k += NT) M.z[k] = 0.0;
-    for (int k = 0; k < ns; k++) {
-        const int o = M.bo[k] - ml, m = M.order(k);
-        for (int e = tid; e < m * m; e += NT) { const double v = (e % m == e / m) ? 1.0 : 0.0; M.r[o + e] = v; M.rti[o + e] = v; }
-    }
-    if (tid < n) { M.x[tid] = 0.0; M.dx[tid] = -M.c[tid]; }
-    if (tid < p) { M.dy[tid] = M.b[tid]; M.y[tid] = 0.0; }
-    __syncthreads();
-    load_sym(M, M.h, M.s);
-    __syncthreads();
-    bool run = factor(M, sing, true);
-    if (run) {
-        kkt_solve(M, sing, M.x, M.dy, M.s);
-        kkt_solve(M, sing, M.dx, M.y, M.z);
-        double mx[2] = {-INFINITY, -INFINITY}, nr[4] = {0.0, 0.0, 0.0, 0.0}, r0[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        if (tid < n) { const double ck = M.c[tid]; r0[0] = ck * ck; r0[3] = ck * M.x[tid]; }
-        if (tid < p) { const double bk = M.b[tid]; r0[1] = bk * bk; r0[4] = bk * M.y[tid]; }
-        for (int k = tid; k < N; k += NT) M.s[k] = -M.s[k];
         __syncthreads();
-        for (int q = tid; q < Np; q += NT) {
-            const int k = prow[q];
-            const double wq = weight(M, q), sk = M.s[k], zk = M.z[k], hk = M.h[k];
-            if (k < ml) { mx[0] = fmax(mx[0], -sk); mx[1] = fmax(mx[1], -zk); }
-            nr[0] += wq * (sk * sk); nr[1] += wq * (zk * zk); nr[2] += wq * (sk * zk); nr[3] += wq * (hk * zk);
-            r0[2] += wq * (hk * hk);
-        }
+        load_sym(M, M.h, M.s);
+        __syncthreads();
+    }
+    __device__ __forceinline__ void max_step(const double *u0, double a0, const double *u1, double a1, double (&mx)[2]) const
+    {
+        orth_max_step(M.ml, u0, a0, u1, a1, mx);
         blk_reduce<2, true>(mx, M.red);
-        blk_reduce<4, false>(nr, M.red);
-        blk_reduce<5, false>(r0, M.red);
-        blocks_max_step(M, M.s, 1.0, M.z, 1.0, mx);
-        resx0 = fmax(1.0, sqrt(r0[0])); resy0 = fmax(1.0, sqrt(r0[1])); resz0 = fmax(1.0, sqrt(r0[2]));
-        gap = nr[2];
-        {
-            const double pc = r0[3], dc = -r0[4] - nr[3];
-            const double rg = pc < 0.0 ? gap / -pc : (dc > 0.0 ? gap / dc : NAN);
-            at0 = mx[0] <= 0.0 && mx[1] <= 0.0 && (gap <= a.abstol || rg <= a.reltol);
-        }
-        if (!at0) {                                        // both pushes into the cone (coneprog.py:806-842): along e
-            const bool ps = mx[0] >= -1e-8 * fmax(sqrt(nr[0]), 1.0), pz = mx[1] >= -1e-8 * fmax(sqrt(nr[1]), 1.0);
-            for (int k = tid; k < ml; k += NT) {
-                if (ps) M.s[k] += 1.0 + mx[0];
-                if (pz) M.z[k] += 1.0 + mx[1];
+        blocks_max_step(M, u0, a0, u1, a1, mx);
+    }
+    __device__ __forceinline__ void push(bool ps, bool pz, const double (&mx)[2]) const
+    {
+        const int tid = threadIdx.x, ns = M.ns;
+        orth_push(M.ml, ps, pz, mx, M.s, M.z);
+        for (int k = 0; k < ns; k++) {
+            const int m = M.order(k), r = M.bo[k] + tid * (m + 1);
+            if (tid < m) {
+                if (ps) M.s[r] += 1.0 + mx[0];
+                if (pz) M.z[r] += 1.0 + mx[1];
             }
-            for (int k = 0; k < ns; k++) {
-                const int m = M.order(k), r = M.bo[k] + tid * (m + 1);
-                if (tid < m) {
-                    if (ps) M.s[r] += 1.0 + mx[0];
-                    if (pz) M.z[r] += 1.0 + mx[1];
-                }
-            }
-            __syncthreads();
-            double g[1] = {0.0};
-            for (int q = tid; q < Np; q += NT) g[0] += weight(M, q) * (M.s[prow[q]] * M.z[prow[q]]);
-            blk_reduce<1, false>(g, M.red);
-            gap = g[0];
         }
+    }
+    __device__ __forceinline__ bool first_scaling() const                           // misc.py:284-419
+    {
+        orth_first_scaling(M.ml, M.s, M.z, M.d, M.di, M.lm);
+        return blocks_scaling(M);
+    }
+    __device__ __forceinline__ double lam_sq() const { return sum_sq(M.lm, M.Nd, M.red); }
+    __device__ __forceinline__ void prepare() const                                 // th = W^-T h
+    {
+        load_sym(M, M.h, M.th);
+        __syncthreads();
+        wscale(M, M.th, M.th, true, true);
+    }
+    __device__ __forceinline__ void assemble(bool sing) const { kvx::assemble(M, sing); }
+    __device__ __forceinline__ void kkt_before(double *vx, double *vz) const
+    {
+        wscale(M, vz, vz, true, true);                                                         // z := W^-T bz
+        wscale(M, vz, M.tw, true, false);
+        gemv_t_packed(M, M.tw, 1.0, vx);                                                       // x += G' W^-1 z
         __syncthreads();
     }
-
-    for (; run; iters++) {
-        // ---- residuals, objectives and the three stopping tests (coneprog.py:861-1024)
-        double r[9];
-        residuals(M, tau, r);
-        const double hresx = sqrt(r[0]), resx = sqrt(r[1]) / tau, hresy = sqrt(r[2]), resy = sqrt(r[3]) / tau;
-        const double hresz = sqrt(r[4]), resz = sqrt(r[5]) / tau, cx = r[6], by = r[7], hz = r[8];
-        if (iters > 0) { const double t = sqrt(lam2) / tau; gap = t * t; }
-        const double rt = kappa + cx + by + hz;
-        pcost = cx / tau; dcost = -(by + hz) / tau;
-        relgap = pcost < 0.0 ? gap / -pcost : (dcost > 0.0 ? gap / dcost : NAN);
-        pres = fmax(resy / resy0, resz / resz0);
-        dres = resx / resx0;
-        pinfres = hz + by < 0.0 ? hresx / resx0 / (-hz - by) : NAN;
-        dinfres = cx < 0.0 ? fmax(hresy / resy0, hresz / resz0) / (-cx) : NAN;
-        if (at0) { code = SDPB_OPTIMAL; pinfres = dinfres = NAN; sp = sd = 1.0; break; }      // coneprog.py:757-804: as they are
-        if (iters == a.maxiters) { code = SDPB_MAXITERS; sp = sd = 1.0 / tau; break; }
-        if (pres <= a.feastol && dres <= a.feastol && (gap <= a.abstol || relgap <= a.reltol)) {
-            code = SDPB_OPTIMAL; pinfres = dinfres = NAN; sp = sd = 1.0 / tau; break;
-        }
-        if (pinfres <= a.feastol) { code = SDPB_PRIMAL_INFEASIBLE; sp = NAN; sd = 1.0 / (-hz - by); break; }
-        if (dinfres <= a.feastol) { code = SDPB_DUAL_INFEASIBLE; sp = 1.0 / (-cx); sd = NAN; break; }
-
-        // ---- scaling of the first iteration (misc.py:284-419, coneprog.py:1041-1043)
-        if (iters == 0) {
-            for (int k = tid; k < ml; k += NT) {
-                const double sk = M.s[k], zk = M.z[k], dk = sqrt(sk / zk);
-                M.d[k] = dk; M.di[k] = 1.0 / dk; M.lm[k] = sqrt(sk * zk);
-            }
-            if (!blocks_scaling(M)) { code = SDPB_RANK; break; }     // lapack.potrf's ArithmeticError in misc.compute_scaling
-            __syncthreads();
-            lam2 = lam_sq(M);
-            dg = sqrt(kappa / tau); dgi = sqrt(tau / kappa); lg = sqrt(tau * kappa);
+    __device__ __forceinline__ void kkt_after(double *vx, double *vz) const
+    {
+        const int tid = threadIdx.x, n = M.n, N = M.N;
+        for (int q = tid; q < M.Np; q += NT) {
+            const double t = row_dot(M.G, N, n, M.prow[q], vx);
+            M.tw[M.prow[q]] = t; M.tw[M.pmir[q]] = t;
         }
         __syncthreads();
-
-        // ---- the factorisation and the constant system (coneprog.py:1066-1077): (x1, y1, z1) = dgi f3(-c, b, h)
-        if (!factor(M, sing, false)) {
-            if (iters == 0) code = SDPB_RANK;
-            else { code = SDPB_SINGULAR; sp = sd = 1.0 / tau; }
-            break;
-        }
-        load_sym(M, M.h, M.z1);
-        if (tid < n) M.x1[tid] = -M.c[tid];
-        if (tid < p) M.y1[tid] = M.b[tid];
+        wscale(M, M.tw, M.tw, true, true);
+        for (int k = tid; k < N; k += NT) vz[k] = M.tw[k] - vz[k];                             // W uz = W^-T G ux - W^-T bz
         __syncthreads();
-        kkt_solve(M, sing, M.x1, M.y1, M.z1);
-        double z1z1;
-        {
-            double g[1] = {0.0};
-            for (int k = tid; k < N; k += NT) M.z1[k] *= dgi;
-            if (tid < n) M.x1[tid] *= dgi;
-            if (tid < p) M.y1[tid] *= dgi;
-            __syncthreads();
-            for (int q = tid; q < Np; q += NT) { const double t = M.z1[prow[q]]; g[0] += weight(M, q) * (t * t); }
-            blk_reduce<1, false>(g, M.red);
-            z1z1 = g[0];
-        }
-
-        // ---- the two directions (coneprog.py:1248-1333) through f6_no_ir (:1130-1195)
-        const double mu = (lam2 + lg * lg) / (1 + Nd);          // coneprog.py:1248: 1 + cdim_diag, the length of lmbda
-        double sigma = 0.0, wkappa3 = 0.0, step = 0.0, tt = 0.0, tk = 0.0;
-        for (int i = 0; i < 2; i++) {
-            // ds := -(lmbda o\ (lmbda o lmbda [+ ws3 - sigma mu e])), dz := -((1 - sigma) rz + W'ds)
-            for (int k = tid; k < ml; k += NT) {
-                const double lk = M.lm[k];
-                double t = lk * lk;
-                if (i == 1) t += M.ws3[k] - sigma * mu;
-                M.ds[k] = -t / lk;
+    }
+    __device__ __forceinline__ void gemv_t(const double *u, double sign, double *v) const { gemv_t_packed(M, u, sign, v); }
+    __device__ __forceinline__ void rhs(int i, double sigma, double mu) const
+    {
+        const int tid = threadIdx.x, ns = M.ns, N = M.N;
+        orth_rhs<false>(M.ml, i, sigma, mu, M.lm, M.ws3, M.d, M.rz, M.ds, M.dz);
+        for (int k = 0; k < ns; k++) {                 // sinv with the diagonal lmbda_k (misc_solvers.c:845-882)
+            const int o = M.bo[k], m = M.order(k);
+            const double *lm = M.lm + M.bl[k];
+            for (int e = tid; e < m * m; e += NT) {
+                const int ii = e % m, jj = e / m;
+                double t = ii == jj ? lm[ii] * lm[ii] : 0.0;
+                if (i == 1) t += M.ws3[o + e] - (ii == jj ? sigma * mu : 0.0);
+                M.ds[o + e] = -(t / ((lm[ii] + lm[jj]) / 2.0));
             }
-            for (int k = 0; k < ns; k++) {                 // sinv with the diagonal lmbda_k (misc_solvers.c:845-882)
-                const int o = M.bo[k], m = M.order(k);
-                const double *lm = M.lm + M.bl[k];
+        }
+        __syncthreads();
+        wscale(M, M.ds, M.tw, false, true);
+        for (int k = tid; k < N; k += NT) M.dz[k] = -((1.0 - sigma) * M.rz[k] + M.tw[k]);
+    }
+    __device__ __forceinline__ double th_dot(const double *dz) const
+    {
+        double acc = 0.0;
+        for (int q = threadIdx.x; q < M.Np; q += NT) acc += weight(M, q) * (M.th[M.prow[q]] * dz[M.prow[q]]);
+        return acc;
+    }
+    __device__ __forceinline__ void combine(int i, double dtau, double (&mx)[2]) const
+    {
+        const int tid = threadIdx.x, ml = M.ml, ns = M.ns, N = M.N;
+        orth_combine(ml, i, dtau, M.lm, M.z1, M.ds, M.dz, M.ws3, mx);
+        for (int k = ml + tid; k < N; k += NT) {
+            const double zk = M.dz[k] + dtau * M.z1[k];
+            M.dz[k] = zk; M.ds[k] -= zk;
+        }
+        blk_reduce<2, true>(mx, M.red);                // its barriers also publish ds and dz
+        for (int k = 0; k < ns; k++) {
+            const int o = M.bo[k], ol = M.bl[k], m = M.order(k);
+            double *ds = M.ds + o, *dz = M.dz + o;
+            const double *lm = M.lm + ol;
+            if (i == 0) {                              // sprod (misc_solvers.c:700-742): (ds dz + dz ds) / 2
                 for (int e = tid; e < m * m; e += NT) {
-                    const int ii = e % m, jj = e / m;
-                    double t = ii == jj ? lm[ii] * lm[ii] : 0.0;
-                    if (i == 1) t += M.ws3[o + e] - (ii == jj ? sigma * mu : 0.0);
-                    M.ds[o + e] = -(t / ((lm[ii] + lm[jj]) / 2.0));
-                }
-            }
-            __syncthreads();
-            wscale(M, M.ds, M.tw, false, true);
-            for (int k = tid; k < N; k += NT) M.dz[k] = -((1.0 - sigma) * M.rz[k] + M.tw[k]);
-            if (tid < n) M.dx[tid] = (1.0 - sigma) * M.rx[tid];
-            if (tid < p) M.dy[tid] = -((1.0 - sigma) * M.ry[tid]);
-            double dkappa = lg * lg;
-            if (i == 1) dkappa += wkappa3 - sigma * mu;
-            __syncthreads();
-            kkt_solve(M, sing, M.dx, M.dy, M.dz);
-            dkappa = -dkappa / lg;
-            double dot[3] = {0.0, 0.0, 0.0};               // c'dx, b'dy, th'dz with th = W^-T h
-            if (tid < n) dot[0] = M.c[tid] * M.dx[tid];
-            if (tid < p) dot[1] = M.b[tid] * M.dy[tid];
-            for (int q = tid; q < Np; q += NT) dot[2] += weight(M, q) * (M.th[prow[q]] * M.dz[prow[q]]);
-            blk_reduce<3, false>(dot, M.red);
-            const double dtau = dgi * ((1.0 - sigma) * rt + dkappa / dgi + dot[0] + dot[1] + dot[2]) / (1.0 + z1z1);
-            if (tid < n) M.dx[tid] += dtau * M.x1[tid];
-            if (tid < p) M.dy[tid] += dtau * M.y1[tid];
-            // dz += dtau z1, ds -= dz, ws3 := ds o dz after the predictor, both scaled by lmbda (scale2), their max_step
-            double mx[2] = {-INFINITY, -INFINITY};
-            for (int k = tid; k < ml; k += NT) {
-                const double lk = M.lm[k], zk = M.dz[k] + dtau * M.z1[k], sk = M.ds[k] - zk;
-                if (i == 0) M.ws3[k] = sk * zk;
-                const double s2 = sk / lk, z2 = zk / lk;
-                M.ds[k] = s2; M.dz[k] = z2;
-                mx[0] = fmax(mx[0], -s2); mx[1] = fmax(mx[1], -z2);
-            }
-            for (int k = ml + tid; k < N; k += NT) {
-                const double zk = M.dz[k] + dtau * M.z1[k];
-                M.dz[k] = zk; M.ds[k] -= zk;
-            }
-            blk_reduce<2, true>(mx, M.red);                // its barriers also publish ds and dz
-            for (int k = 0; k < ns; k++) {
-                const int o = M.bo[k], ol = M.bl[k], m = M.order(k);
-                double *ds = M.ds + o, *dz = M.dz + o;
-                const double *lm = M.lm + ol;
-                if (i == 0) {                              // sprod (misc_solvers.c:700-742): (ds dz + dz ds) / 2
-                    for (int e = tid; e < m * m; e += NT) {
-                        const int ii = e % m, jj = e / m, aa = max(ii, jj), bb = min(ii, jj);
-                        double acc = 0.0;
-                        for (int q = 0; q < m; q++) acc += ds[aa + q * m] * dz[q + bb * m] + dz[aa + q * m] * ds[q + bb * m];
-                        M.ws3[o + e] = 0.5 * acc;
-                    }
-                    __syncthreads();
-                }
-                for (int e = tid; e < m * m; e += NT) {    // scale2 (misc_solvers.c:343-397)
-                    const double cc = sqrt(lm[e % m]) * sqrt(lm[e / m]);
-                    ds[e] = ds[e] / cc; dz[e] = dz[e] / cc;
+                    const int ii = e % m, jj = e / m, aa = max(ii, jj), bb = min(ii, jj);
+                    double acc = 0.0;
+                    for (int q = 0; q < m; q++) acc += ds[aa + q * m] * dz[q + bb * m] + dz[aa + q * m] * ds[q + bb * m];
+                    M.ws3[o + e] = 0.5 * acc;
                 }
                 __syncthreads();
-                // the eigenvalues in sgs, sgz; the eigenvectors replace the blocks (coneprog.py:1308-1321); the update consumes both
-                eig2(M, ds, 1.0, dz, 1.0, m, M.sgs + (ol - ml), M.sgz + (ol - ml), ds, dz);
-                mx[0] = fmax(mx[0], -M.sgs[ol - ml]);
-                mx[1] = fmax(mx[1], -M.sgz[ol - ml]);
             }
-            dkappa -= dtau;
-            if (i == 0) wkappa3 = dtau * dkappa;
-            tt = -dtau / lg; tk = -dkappa / lg;
-            const double t = fmax(fmax(0.0, fmax(mx[0], mx[1])), fmax(tt, tk));
-            step = t == 0.0 ? 1.0 : (i == 0 ? fmin(1.0, 1.0 / t) : fmin(1.0, 0.99 / t));
-            if (i == 0) { const double u = 1.0 - step; sigma = u * u * u; }
+            for (int e = tid; e < m * m; e += NT) {    // scale2 (misc_solvers.c:343-397)
+                const double cc = sqrt(lm[e % m]) * sqrt(lm[e / m]);
+                ds[e] = ds[e] / cc; dz[e] = dz[e] / cc;
+            }
+            __syncthreads();
+            // the eigenvalues in sgs, sgz; the eigenvectors replace the blocks (coneprog.py:1308-1321); the update consumes both
+            eig2(M, ds, 1.0, dz, 1.0, m, M.sgs + (ol - ml), M.sgz + (ol - ml), ds, dz);
+            mx[0] = fmax(mx[0], -M.sgs[ol - ml]);
+            mx[1] = fmax(mx[1], -M.sgz[ol - ml]);
         }
-
-        // ---- the step, the scaling update (misc.py:444-634, coneprog.py:1336-1436), s = W'lmbda and z = W^-1 lmbda
-        dg *= sqrt(1.0 - step * tk) / sqrt(1.0 - step * tt);
-        dgi = 1.0 / dg;
-        lg *= sqrt(1.0 - step * tt) * sqrt(1.0 - step * tk);
-        kappa = lg / dgi; tau = lg * dgi;
-        if (tid < n) M.x[tid] += step * M.dx[tid];
-        if (tid < p) M.y[tid] += step * M.dy[tid];
-        for (int k = tid; k < ml; k += NT) {
-            const double lk = M.lm[k], rs = sqrt((1.0 + step * M.ds[k]) * lk), rz = sqrt((1.0 + step * M.dz[k]) * lk);
-            const double dk = M.d[k] * rs / rz, dik = 1.0 / dk, ln = rs * rz;
-            M.d[k] = dk; M.di[k] = dik; M.lm[k] = ln;
-            M.s[k] = dk * ln; M.z[k] = dik * ln;
-        }
+    }
+    __device__ __forceinline__ void update(double step) const                       // misc.py:444-634; s = W'lmbda and z = W^-1 lmbda
+    {
+        const int tid = threadIdx.x, ml = M.ml, ns = M.ns;
+        orth_update(ml, step, M.ds, M.dz, M.d, M.di, M.lm, M.s, M.z);
         for (int k = 0; k < ns; k++) {
             const int o = M.bo[k], ol = M.bl[k], m = M.order(k);
             double *r = M.r + (o - ml), *rti = M.rti + (o - ml), *lm = M.lm + ol;
@@ -890,34 +605,54 @@ __global__ void __launch_bounds__(SDPB_THREADS) k_sdp_batch(SdpBatchArgs a)
             rdr(rti, lm, M.z + o, m);
             __syncthreads();
         }
-        __syncthreads();
-        lam2 = lam_sq(M);                                  // its barriers also publish x, y, s, z
     }
+};
 
-    // ---- the member's result: x, s scaled by sp and y, z by sd (coneprog.py:925-1024, 1082-1109); NaN for the half a certificate
-    //      comes without; after a first factorisation that failed: zeros.  The slacks are -max_step of the scaled s and z.
-    const bool rank = code == SDPB_RANK, xs = sp == sp, zs = sd == sd;
-    double mx[2] = {-INFINITY, -INFINITY};
+__global__ void __launch_bounds__(SDPB_THREADS) k_sdp_batch(SdpBatchArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int tid = threadIdx.x, ml = a.ml, ns = a.ns;
+    const Layout L = layout(a.n, ml, a.N, a.Nd, a.Np, ns, a.p);
+    Member M;
+    conelp_data(M, a, a.N);
+    M.ml = ml; M.ns = ns; M.Nd = a.Nd; M.Np = a.Np; M.ldn = L.ldn; M.ldp = L.ldp;
+    M.S = lds + L.S; M.T = lds + L.XK; M.X = lds + L.X; M.K = lds + L.K;
+    M.x = lds + L.x; M.dx = lds + L.dx; M.rx = lds + L.rx; M.x1 = lds + L.x1;
+    M.y = lds + L.y; M.dy = lds + L.dy; M.ry = lds + L.ry; M.y1 = lds + L.y1;
+    M.s = lds + L.s; M.z = lds + L.z; M.ds = lds + L.ds; M.dz = lds + L.dz; M.rz = lds + L.rz; M.ws3 = lds + L.ws3;
+    M.z1 = lds + L.z1; M.tw = lds + L.tw; M.th = lds + L.th; M.r = lds + L.r; M.rti = lds + L.rti;
+    M.lm = lds + L.lm; M.d = lds + L.d; M.di = lds + L.di; M.sgs = lds + L.sgs; M.sgz = lds + L.sgz;
+    M.wa = lds + L.wk; M.wb = M.wa + MM; M.wc = M.wb + MM; M.wd = M.wc + MM; M.nrm = lds + L.nrm;
+    M.red = lds + L.red;
+    M.bo = reinterpret_cast<int *>(lds + L.blk); M.bl = M.bo + (ns + 1);
+    M.flag = reinterpret_cast<int *>(lds + L.flag);
+    unsigned short *prow = reinterpret_cast<unsigned short *>(lds + L.prow), *pmir = reinterpret_cast<unsigned short *>(lds + L.pmir);
+    M.prow = prow; M.pmir = pmir;
+
+    // ---- the cone: the first row and the first lmbda of every block, the packed rows and their mirror images
+    if (tid <= ns) {
+        int o = ml, ol = ml;
+        for (int k = 0; k < tid; k++) { o += a.m[k] * a.m[k]; ol += a.m[k]; }
+        M.bo[tid] = o; M.bl[tid] = ol;
+    }
+    for (int k = tid; k < ml; k += NT) { prow[k] = (unsigned short)k; pmir[k] = (unsigned short)k; }
     __syncthreads();
-    for (int k = tid; k < N; k += NT) {
-        const double sk = sp * M.s[k], zk = sd * M.z[k];
-        so[k] = rank ? 0.0 : (xs ? sk : NAN); zo[k] = rank ? 0.0 : (zs ? zk : NAN);
-        if (k < ml) { mx[0] = fmax(mx[0], -sk); mx[1] = fmax(mx[1], -zk); }
+    {
+        int po = ml;
+        for (int k = 0; k < ns; k++) {
+            const int o = M.bo[k], m = M.order(k);
+            for (int e = tid; e < m * m; e += NT) {
+                const int i = e % m, j = e / m;
+                if (i < j) continue;
+                const int q = po + j * m - (j * (j - 1)) / 2 + (i - j);
+                prow[q] = (unsigned short)(o + i + j * m);
+                pmir[q] = (unsigned short)(o + j + i * m);
+            }
+            po += (m * (m + 1)) / 2;
+        }
     }
-    if (tid < n) xo[tid] = rank ? 0.0 : (xs ? sp * M.x[tid] : NAN);
-    if (tid < p) yo[tid] = rank ? 0.0 : (zs ? sd * M.y[tid] : NAN);
-    blk_reduce<2, true>(mx, M.red);
-    if (!rank) blocks_max_step(M, M.s, sp, M.z, sd, mx);
-    if (tid == 0) {
-        const bool pinf = code == SDPB_PRIMAL_INFEASIBLE, dinf = code == SDPB_DUAL_INFEASIBLE, cert = pinf || dinf;
-        const double out[SDPB_NSTAT] = {cert ? NAN : gap, cert ? NAN : relgap, pinf ? NAN : (dinf ? -1.0 : pcost),
-                                        dinf ? NAN : (pinf ? 1.0 : dcost), cert ? NAN : pres, cert ? NAN : dres,
-                                        xs ? -mx[0] : NAN, zs ? -mx[1] : NAN, dinf ? NAN : pinfres, pinf ? NAN : dinfres};
-#pragma unroll
-        for (int k = 0; k < SDPB_NSTAT; k++) st[k] = rank ? NAN : out[k];
-        a.iters[bm] = rank ? 0 : iters;
-        a.exitc[bm] = code;
-    }
+    __syncthreads();
+    conelp_member(Cone{M}, a);
 }
 
 }  // namespace

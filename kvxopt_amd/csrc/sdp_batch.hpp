@@ -7,6 +7,8 @@
 // the starting point to its status or its infeasibility certificate, the whole batch in one launch.  The cone is the same for
 // every member.  An 's' block is its m_k x m_k matrix in column-major order; only its lower triangle is read in G and h.
 #pragma once
+#include "batch_host.hpp"
+
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
@@ -16,23 +18,13 @@ namespace kvx {
 // cap on the sweeps of one Jacobi iteration, and the numbers of `stats`.
 enum { SDPB_MAX_N = 64, SDPB_MAX_ROWS = 384, SDPB_MAX_NS = 32, SDPB_MAX_M = 16, SDPB_THREADS = 256, SDPB_TILE = 32, SDPB_SWEEPS = 60,
        SDPB_NSTAT = 10 };
-// What a member ends with (the `exit` of kvxopt_amd.sdpbatch): the codes of lp_batch.hpp.
-enum { SDPB_OPTIMAL = 0, SDPB_MAXITERS = 1, SDPB_SINGULAR = 2, SDPB_RANK = 3, SDPB_PRIMAL_INFEASIBLE = 4, SDPB_DUAL_INFEASIBLE = 5 };
+// What a member ends with (the `exit` of kvxopt_amd.sdpbatch): the CONELP_ codes of batch_conelp.hpp.
 
-struct SdpBatchArgs {
-    int64_t B;
-    int n, ml, ns, N, Nd, Np, p;              // Nd = ml + sum m_k (lmbda), Np = ml + sum m_k (m_k + 1) / 2 (packed rows)
+// BatchArgs with G N x n and s, z N x B, 's' blocks as full symmetric matrices.  stats (SDPB_NSTAT x B) as in lp_batch.hpp; the
+// slacks are -max_step over the whole cone.
+struct SdpBatchArgs : BatchArgs {
+    int ns, N, Nd, Np;                        // Nd = ml + sum m_k (lmbda), Np = ml + sum m_k (m_k + 1) / 2 (packed rows)
     unsigned char m[SDPB_MAX_NS];             // the block orders travel with the kernel's arguments: no device copy of them
-    // device pointers; matrices dense and column-major per member (G N x n; A p x n); s*: distance between two members in
-    // doubles, 0: one for all
-    const double *c, *G, *h, *A, *b;
-    int64_t sc, sG, sh, sA, sb;
-    int maxiters;
-    double abstol, reltol, feastol;
-    // results: x (n x B), y (p x B), s, z (N x B, 's' blocks as full symmetric matrices), stats (SDPB_NSTAT x B, as in
-    // lp_batch.hpp; the slacks are -max_step over the whole cone), iterations and exit (B each)
-    double *x, *y, *s, *z, *stats;
-    int64_t *iters, *exitc;
 };
 
 // LDS of one workgroup in bytes: at most 150 KiB on the box of the limits above.

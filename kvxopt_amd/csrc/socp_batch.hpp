@@ -7,6 +7,8 @@
 // the starting point to its status or its infeasibility certificate, the whole batch in one launch.  The cone is the same for
 // every member.
 #pragma once
+#include "batch_host.hpp"
+
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
@@ -16,23 +18,13 @@ namespace kvx {
 // order up to which one thread adds a cone's column of (J v)'G by itself, and the numbers of `stats`.
 enum { SOCPB_MAX_N = 64, SOCPB_MAX_ROWS = 512, SOCPB_MAX_NQ = 128, SOCPB_THREADS = 256, SOCPB_TILE = 32, SOCPB_SERIAL = 16,
        SOCPB_NSTAT = 10 };
-// What a member ends with (the `exit` of kvxopt_amd.socpbatch): the codes of lp_batch.hpp.
-enum { SOCPB_OPTIMAL = 0, SOCPB_MAXITERS = 1, SOCPB_SINGULAR = 2, SOCPB_RANK = 3, SOCPB_PRIMAL_INFEASIBLE = 4, SOCPB_DUAL_INFEASIBLE = 5 };
+// What a member ends with (the `exit` of kvxopt_amd.socpbatch): the CONELP_ codes of batch_conelp.hpp.
 
-struct SocpBatchArgs {
-    int64_t B;
-    int n, ml, nq, N, p;
+// BatchArgs with G N x n and s, z N x B.  stats (SOCPB_NSTAT x B) as in lp_batch.hpp; the slacks are -max_step over the whole
+// cone.
+struct SocpBatchArgs : BatchArgs {
+    int nq, N;
     unsigned short q[SOCPB_MAX_NQ];           // the cone orders travel with the kernel's arguments: no device copy of them
-    // device pointers; matrices dense and column-major per member (G N x n; A p x n); s*: distance between two members in
-    // doubles, 0: one for all
-    const double *c, *G, *h, *A, *b;
-    int64_t sc, sG, sh, sA, sb;
-    int maxiters;
-    double abstol, reltol, feastol;
-    // results: x (n x B), y (p x B), s, z (N x B), stats (SOCPB_NSTAT x B, as in lp_batch.hpp; the slacks are -max_step over the
-    // whole cone), iterations and exit (B each)
-    double *x, *y, *s, *z, *stats;
-    int64_t *iters, *exitc;
 };
 
 // LDS of one workgroup in bytes: at most 150 KiB on the box of the limits above.
