@@ -742,6 +742,36 @@ int kvx_sdp_batch_solve_dev(int64_t B, int64_t n, int64_t ml, int64_t ns, const 
                             int64_t sb, int64_t maxiters, double abstol, double reltol, double feastol, double *x, double *y,
                             double *s, double *z, double *stats, int64_t *iterations, int64_t *exitcode);
 
+/* ---- B small dense cone programs over all three kinds of cone, each with its own matrices: replaces a loop of solvers.conelp
+ * calls (coneprog.conelp, coneprog.py:662-1436, with the 'q' and 's' blocks of misc.compute_scaling / update_scaling,
+ * misc.py:290-419, 467-634, of misc_solvers.scale, scale2, sprod, sinv, sdot and max_step, misc_solvers.c:144-240, 301-397,
+ * 671-770, 803-882, 1029-1160; the Newton systems of misc.kkt_chol2, misc.py:1395-1563, on Gs = W^-T G, with its F['singular']
+ * repair).
+ *     minimize c_b'x   subject to   G_b x + s = h_b,  s in R^ml_+ x Q^{q[0]} x ... x S^{m[0]}_+ x ...,  A_b x = b_b,      b = 0..B-1,
+ * in ONE launch, one workgroup per member from its starting point to its status or certificate (csrc/conelp_batch.hip);
+ * refinement 0 (solvers.conelp defaults to 1 with 'q' or 's' rows), no starting points.  The cone is the same for every
+ * member: q and m are HOST arrays of nq cone orders and ns block orders for both entries (they travel with the kernel's
+ * arguments), rows stacked as in conelp, the ml 'l' rows first, then the cones, then every block as its m[k] x m[k] matrix in
+ * column-major order, of which only the lower triangle is read in G and h.
+ * 1 <= n <= 64, ml >= 0, 0 <= nq <= 128, q[k] >= 1, 0 <= ns <= 32, 1 <= m[k] <= 16, 1 <= N = ml + sum q + sum m^2 <= 384,
+ * 0 <= p <= n, p + ml + sum q + sum m (m + 1) / 2 >= n, 1 <= B <= 2^31 - 1.  Matrices, strides, options, results, stats, exit
+ * codes and the independence of the members are those of kvx_lp_batch_solve with N rows in G, h, s and z; the 's' blocks of s
+ * and z are returned as full symmetric matrices; primal and dual slack are -max_step over the whole cone.  The kernel is the
+ * same whichever kinds are present; kvx_lp_batch_solve, kvx_socp_batch_solve and kvx_sdp_batch_solve are the faster entries
+ * for their cones.
+ * kvx_conelp_batch_solve: host pointers; uploads, launches, downloads.  kvx_conelp_batch_solve_dev: device pointers (q and m
+ * excepted), no workspace, results complete on return.  KVX_EINVAL for bad sizes, limits, strides, options, NULL pointers,
+ * cone orders or block orders on any box, before a device is asked for; KVX_EDEVICE without a GPU (never a CPU fallback). */
+int kvx_conelp_batch_solve(int64_t B, int64_t n, int64_t ml, int64_t nq, const int64_t *q, int64_t ns, const int64_t *m, int64_t p,
+                           const double *c, int64_t sc, const double *G, int64_t sG, const double *h, int64_t sh, const double *A,
+                           int64_t sA, const double *b, int64_t sb, int64_t maxiters, double abstol, double reltol, double feastol,
+                           double *x, double *y, double *s, double *z, double *stats, int64_t *iterations, int64_t *exitcode);
+int kvx_conelp_batch_solve_dev(int64_t B, int64_t n, int64_t ml, int64_t nq, const int64_t *q, int64_t ns, const int64_t *m, int64_t p,
+                               const double *c, int64_t sc, const double *G, int64_t sG, const double *h, int64_t sh, const double *A,
+                               int64_t sA, const double *b, int64_t sb, int64_t maxiters, double abstol, double reltol,
+                               double feastol, double *x, double *y, double *s, double *z, double *stats, int64_t *iterations,
+                               int64_t *exitcode);
+
 /* ---- dense helpers of the equality-constrained KKT solve with a general S (misc.py:1476-1487, 1545): K = A S^-1 A' formed
  * as a dense p x p matrix from X = S^-1 A' (kvx_chol_solve_dev with nrhs = p) when p is moderate ------------------------- */
 /* Y(j, c) = sum_i A(i, j) X(i, c) for the CCS matrix A with n columns and every column c < ncols of the dense X */

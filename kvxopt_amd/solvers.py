@@ -23,6 +23,10 @@
     sdp_batch(c, G, h, dims, A=None, b=None, options=None)                           no counterpart: B small dense SDPs in one launch,
                                                                                      dims = {'l': ml, 's': [...]} shared by the members
                                                                                      (-> sdpbatch.sdp_batch; reads its own `options` only)
+    conelp_batch(c, G, h, dims, A=None, b=None, options=None)                        no counterpart: B small dense cone programs in one
+                                                                                     launch, dims = {'l': ml, 'q': [...], 's': [...]}
+                                                                                     shared by the members
+                                                                                     (-> conelpbatch.conelp_batch; reads its own `options` only)
     options                                                                         the module-level dict of the reference
 
 Like the reference, algorithm parameters come from `solvers.options` ('maxiters', 'abstol', 'reltol', 'feastol',
@@ -41,6 +45,7 @@ from . import cone as _cone
 from . import cvx as _cvx
 from . import lp as _lp
 from . import osqp as _osqp
+from .conelpbatch import conelp_batch  # noqa: F401
 from .lpbatch import lp_batch  # noqa: F401
 from .qpbatch import qp_batch  # noqa: F401
 from .sdpbatch import sdp_batch  # noqa: F401

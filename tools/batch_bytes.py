@@ -1,9 +1,10 @@
-"""One SHA-256 per named batch of the four batch solvers: what a change that must not move a bit is held to.
+"""One SHA-256 per named batch of the five batch solvers: what a change that must not move a bit is held to.
 
-    python tools/batch_bytes.py [--only qp,lp,socp,sdp]
+    python tools/batch_bytes.py [--only qp,lp,socp,sdp,conelp]
     KVX_LIB_PATH=/path/to/other/libkvxhip.so python tools/batch_bytes.py
 
-For solvers.qp_batch, lp_batch, socp_batch and sdp_batch it runs every named batch of tests/{qp,lp,socp,sdp}_batch_numpy.py --
+For solvers.qp_batch, lp_batch, socp_batch, sdp_batch and conelp_batch it runs every named batch of
+tests/{qp,lp,socp,sdp,conelp}_batch_numpy.py --
 all of SHAPES, every key of BATCHES (qp: INDEPENDENCE and MIXED), the spoiled "mixed" variants as tests/test_*_batch_gpu.py spoil
 them, and the golden cases as those tests batch them (member 0 of a batch of three with shared matrices and perturbed linear
 terms; the tiny LPs in batches of their own) -- and prints, for each (solver, batch), the SHA-256 over the bytes of x, y, s, z,
@@ -25,6 +26,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import conelp_batch_numpy as CONE  # noqa: E402
 import lp_batch_numpy as LP  # noqa: E402
 import qp_batch_numpy as QP  # noqa: E402
 import sdp_batch_numpy as SDP  # noqa: E402
@@ -110,6 +112,15 @@ def spoil_sdp(M):
     return r
 
 
+def spoil_conelp(M):
+    r = spoil_lp(M, CONE)
+    h = M.h.copy()
+    o = SDP.blocks(M.Ms, M.s)[0][1]
+    h[o:o + 9, CONE.MIXED_CHANGED[0]] = 1e200 * np.diag([1.0, -1.0, 1.0]).reshape(-1)
+    r["h"] = h
+    return r
+
+
 def lp_batches():
     def solve(M, options, **replace):
         a = {"c": M.c, "G": M.G, "h": M.h, "A": M.A, "b": M.b}
@@ -146,12 +157,14 @@ SOLVERS = {
                                   ("doc_socp", "mixed_eq", "socp_pinf", "socp_dinf")), LP_STATS),
     "sdp": (lambda: dims_batches(SDP, solvers.sdp_batch, spoil_sdp, "g27_sdp_batch",
                                  ("doc_sdp", "doc_sdp_lower", "mixed_eq", "sdp_pinf", "sdp_dinf")), LP_STATS),
+    "conelp": (lambda: dims_batches(CONE, solvers.conelp_batch, spoil_conelp, "g28_conelp_batch",
+                                    ("doc_conelp", "doc_conelp_lower", "mixed_eq", "conelp_pinf", "conelp_dinf")), LP_STATS),
 }
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="qp,lp,socp,sdp")
+    ap.add_argument("--only", default="qp,lp,socp,sdp,conelp")
     a = ap.parse_args()
     _lib.require_device()
     print("library: %s" % _lib.LIB_PATH)
