@@ -772,6 +772,37 @@ int kvx_conelp_batch_solve_dev(int64_t B, int64_t n, int64_t ml, int64_t nq, con
                                double feastol, double *x, double *y, double *s, double *z, double *stats, int64_t *iterations,
                                int64_t *exitcode);
 
+/* ---- B small dense cone QPs over all three kinds of cone, each with its own matrices: replaces a loop of solvers.coneqp calls
+ * (coneprog.coneqp, coneprog.py:1440-2547, with the 'q' and 's' blocks of misc.compute_scaling / update_scaling,
+ * misc.py:290-419, 467-634, of misc_solvers.scale, scale2, sprod, sinv, sdot and max_step, misc_solvers.c:144-240, 301-397,
+ * 671-770, 803-882, 1029-1160; the Newton systems of misc.kkt_chol with H = P, misc.py:1395-1563, on S = P + Gs'Gs,
+ * Gs = W^-T G, without an A'A repair).
+ *     minimize (1/2) x'P_b x + q_b'x   subject to   G_b x + s = h_b,  s in R^ml_+ x Q^{qdims[0]} x ... x S^{m[0]}_+ x ...,
+ *     A_b x = b_b,      b = 0..B-1,
+ * in ONE launch, one workgroup per member from its starting point to its status (csrc/coneqp_batch.hip); refinement 0
+ * (solvers.coneqp defaults to 1 with 'q' or 's' rows), no initvals.  The cone, its HOST arrays qdims and m, the rows, the
+ * matrices, strides and options are those of kvx_conelp_batch_solve, and so are the limits except that there is no rank
+ * condition on the packed dimension: P (n x n per member, column-major, member stride sP or 0, its lower triangle read) may
+ * supply the rank, and a member whose first factorisation fails ends with exit 3.  use_correction: the Mehrotra correction
+ * (coneprog.py:2376-2392).  Results, stats (8 x B: gap, relative gap or NaN, primal and dual objective, primal and dual
+ * infeasibility, primal and dual slack as -max_step over the whole cone), exit codes 0-3 and the independence of the members
+ * are those of kvx_qp_batch_solve with N = ml + sum qdims + sum m^2 rows in G, h, s and z; the 's' blocks of s and z are
+ * returned as full symmetric matrices.
+ * kvx_coneqp_batch_solve: host pointers; uploads, launches, downloads.  kvx_coneqp_batch_solve_dev: device pointers (qdims
+ * and m excepted), no workspace, results complete on return.  KVX_EINVAL for bad sizes, limits, strides, options, NULL
+ * pointers, cone orders or block orders on any box, before a device is asked for; KVX_EDEVICE without a GPU (never a CPU
+ * fallback). */
+int kvx_coneqp_batch_solve(int64_t B, int64_t n, int64_t ml, int64_t nq, const int64_t *qdims, int64_t ns, const int64_t *m, int64_t p,
+                           const double *P, int64_t sP, const double *q, int64_t sq, const double *G, int64_t sG, const double *h,
+                           int64_t sh, const double *A, int64_t sA, const double *b, int64_t sb, int64_t maxiters, double abstol,
+                           double reltol, double feastol, int use_correction, double *x, double *y, double *s, double *z, double *stats,
+                           int64_t *iterations, int64_t *exitcode);
+int kvx_coneqp_batch_solve_dev(int64_t B, int64_t n, int64_t ml, int64_t nq, const int64_t *qdims, int64_t ns, const int64_t *m,
+                               int64_t p, const double *P, int64_t sP, const double *q, int64_t sq, const double *G, int64_t sG,
+                               const double *h, int64_t sh, const double *A, int64_t sA, const double *b, int64_t sb, int64_t maxiters,
+                               double abstol, double reltol, double feastol, int use_correction, double *x, double *y, double *s,
+                               double *z, double *stats, int64_t *iterations, int64_t *exitcode);
+
 /* ---- dense helpers of the equality-constrained KKT solve with a general S (misc.py:1476-1487, 1545): K = A S^-1 A' formed
  * as a dense p x p matrix from X = S^-1 A' (kvx_chol_solve_dev with nrhs = p) when p is moderate ------------------------- */
 /* Y(j, c) = sum_i A(i, j) X(i, c) for the CCS matrix A with n columns and every column c < ncols of the dense X */

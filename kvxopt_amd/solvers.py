@@ -27,7 +27,11 @@
                                                                                      launch, dims = {'l': ml, 'q': [...], 's': [...]}
                                                                                      shared by the members
                                                                                      (-> conelpbatch.conelp_batch; reads its own `options` only)
-    options                                                                         the module-level dict of the reference
+    coneqp_batch(P, q, G, h, dims, A=None, b=None, options=None)                     no counterpart: B small dense cone QPs in one
+                                                                                     launch, dims = {'l': ml, 'q': [...], 's': [...]}
+                                                                                     shared by the members
+                                                                                     (-> coneqpbatch.coneqp_batch; reads its own `options` only)
+    options                                                                        the module-level dict of the reference
 
 Like the reference, algorithm parameters come from `solvers.options` ('maxiters', 'abstol', 'reltol', 'feastol',
 'refinement', 'show_progress'); a keyword `options=` overrides it per call.  `conelp / lp / coneqp / qp (..., kktsolver=f)`
@@ -46,6 +50,7 @@ from . import cvx as _cvx
 from . import lp as _lp
 from . import osqp as _osqp
 from .conelpbatch import conelp_batch  # noqa: F401
+from .coneqpbatch import coneqp_batch  # noqa: F401
 from .lpbatch import lp_batch  # noqa: F401
 from .qpbatch import qp_batch  # noqa: F401
 from .sdpbatch import sdp_batch  # noqa: F401
