@@ -803,6 +803,38 @@ int kvx_coneqp_batch_solve_dev(int64_t B, int64_t n, int64_t ml, int64_t nq, con
                                double abstol, double reltol, double feastol, int use_correction, double *x, double *y, double *s,
                                double *z, double *stats, int64_t *iterations, int64_t *exitcode);
 
+/* ---- many small dense geometric programs at once: B members of cvxprog.gp (cvxprog.py:1967-2155: the evaluator :2094-2153,
+ * cp's epigraph form :1746-1964, cpl's iteration with its relaxed and backtracking line search :556-1356; the Newton systems
+ * of misc.kkt_chol2, misc.py:1395-1563, on S = H + J' diag(di^2) J without an A'A repair)
+ *     minimize log sum exp(F0_b x + g0_b)   subject to   log sum exp(Fi_b x + gi_b) <= 0 (i = 1..mnl),  G_b x <= h_b,
+ *     A_b x = b_b,      b = 0..B-1,
+ * in ONE launch, one workgroup per member from x = 0, t = 0, s = z = 1 to its status (csrc/gp_batch.hip); refinement 0
+ * (solvers.gp defaults to 1).  K: a HOST array of mnl + 1 positive block sizes for both entries, block 0 the objective;
+ * l = sum K.  F (l x n), G (ml x n), A (p x n): dense, column-major per member; g (l), h (ml), b (p); every datum with its
+ * member stride in doubles (0: shared; otherwise at least its size).  Limits: 1 <= n <= 63, N = mnl + 1 + ml <= 192,
+ * l <= 768, 0 <= p <= n, ml >= 0 (G, h may be NULL when ml = 0; A, b, y when p = 0).  Results: x (n x B), y (p x B), s, z
+ * (N x B: the objective row of the epigraph form first, then the mnl constraint rows, then the ml rows of G), stats (8 x B:
+ * gap, relative gap or NaN, primal and dual objective, primal and dual infeasibility, primal and dual slack), iterations and
+ * exitcode (B each): 0 optimal, 1 maxiters, 2 singular KKT matrix after iteration 0, 3 the first factorisation failed (the
+ * reference raises ValueError("Rank(A) < p or Rank([H(x); A; Df(x); G]) < n")): zeros, 0 iterations, NaN stats, 4 a line
+ * search did not end within 64 halvings of its step (the reference has no bound): the last accepted iterate.  A member's bytes
+ * do not depend on B, on its place or on the other members.
+ * kvx_gp_batch_solve: host pointers; uploads, allocates the workspace, launches, downloads.  kvx_gp_batch_solve_dev: device
+ * pointers (K excepted), results complete on return; scratch: B * kvx_gp_batch_scratch_doubles(n, mnl, ml, p) doubles of
+ * device memory, contents arbitrary (a member's A with a zero column for t, and the saved state of its line search).
+ * KVX_EINVAL for bad sizes, limits, strides, options, NULL pointers or a non-positive K[i] on any box, before a device is asked
+ * for; KVX_EDEVICE without a GPU (never a CPU fallback).  kvx_gp_batch_scratch_doubles: -1 outside the limits. */
+int64_t kvx_gp_batch_scratch_doubles(int64_t n, int64_t mnl, int64_t ml, int64_t p);
+int kvx_gp_batch_solve(int64_t B, int64_t n, int64_t mnl, const int64_t *K, int64_t ml, int64_t p, const double *F, int64_t sF,
+                       const double *g, int64_t sg, const double *G, int64_t sG, const double *h, int64_t sh, const double *A, int64_t sA,
+                       const double *b, int64_t sb, int64_t maxiters, double abstol, double reltol, double feastol, double *x, double *y,
+                       double *s, double *z, double *stats, int64_t *iterations, int64_t *exitcode);
+int kvx_gp_batch_solve_dev(int64_t B, int64_t n, int64_t mnl, const int64_t *K, int64_t ml, int64_t p, const double *F, int64_t sF,
+                           const double *g, int64_t sg, const double *G, int64_t sG, const double *h, int64_t sh, const double *A,
+                           int64_t sA, const double *b, int64_t sb, int64_t maxiters, double abstol, double reltol, double feastol,
+                           double *x, double *y, double *s, double *z, double *stats, int64_t *iterations, int64_t *exitcode,
+                           double *scratch);
+
 /* ---- dense helpers of the equality-constrained KKT solve with a general S (misc.py:1476-1487, 1545): K = A S^-1 A' formed
  * as a dense p x p matrix from X = S^-1 A' (kvx_chol_solve_dev with nrhs = p) when p is moderate ------------------------- */
 /* Y(j, c) = sum_i A(i, j) X(i, c) for the CCS matrix A with n columns and every column c < ncols of the dense X */

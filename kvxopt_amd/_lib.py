@@ -254,6 +254,9 @@ _SIGS = {
                                + [i64, f64, f64, f64, ctypes.c_int] + [f64p] * 5 + [i64p] * 2),
     "kvx_coneqp_batch_solve_dev": (ctypes.c_int, [i64] * 4 + [i64p, i64, i64p, i64] + [vp, i64] * 6
                                    + [i64, f64, f64, f64, ctypes.c_int] + [vp] * 7),
+    "kvx_gp_batch_scratch_doubles": (i64, [i64] * 4),
+    "kvx_gp_batch_solve": (ctypes.c_int, [i64] * 3 + [i64p, i64, i64] + [f64p, i64] * 6 + [i64, f64, f64, f64] + [f64p] * 5 + [i64p] * 2),
+    "kvx_gp_batch_solve_dev": (ctypes.c_int, [i64] * 3 + [i64p, i64, i64] + [vp, i64] * 6 + [i64, f64, f64, f64] + [vp] * 8),
     "kvx_vec_scatter_dev": (ctypes.c_int, [i64, vp, vp, vp]),
     "kvx_nts_colscale_dev": (ctypes.c_int, [i64, vp, vp, vp, vp]),
     "kvx_spmm_t_dev": (ctypes.c_int, [i64, i64, vp, vp, vp, vp, i64, vp, i64]),

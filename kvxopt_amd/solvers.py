@@ -31,6 +31,9 @@
                                                                                      launch, dims = {'l': ml, 'q': [...], 's': [...]}
                                                                                      shared by the members
                                                                                      (-> coneqpbatch.coneqp_batch; reads its own `options` only)
+    gp_batch(K, F, g, G=None, h=None, A=None, b=None, options=None)                  no counterpart: B small dense geometric programs
+                                                                                     in one launch, K shared by the members
+                                                                                     (-> gpbatch.gp_batch; reads its own `options` only)
     options                                                                        the module-level dict of the reference
 
 Like the reference, algorithm parameters come from `solvers.options` ('maxiters', 'abstol', 'reltol', 'feastol',
@@ -51,6 +54,7 @@ from . import lp as _lp
 from . import osqp as _osqp
 from .conelpbatch import conelp_batch  # noqa: F401
 from .coneqpbatch import coneqp_batch  # noqa: F401
+from .gpbatch import gp_batch  # noqa: F401
 from .lpbatch import lp_batch  # noqa: F401
 from .qpbatch import qp_batch  # noqa: F401
 from .sdpbatch import sdp_batch  # noqa: F401
