@@ -658,6 +658,53 @@ int kvx_qp_batch_solve_dev(int64_t B, int64_t n, int64_t ml, int64_t p, const do
                            int64_t sb, int64_t maxiters, double abstol, double reltol, double feastol, int use_correction, double *x,
                            double *y, double *s, double *z, double *stats, int64_t *iterations, int64_t *exitcode);
 
+/* ---- derivatives of a solved batch of kvx_qp_batch_solve (no reference counterpart; the mathematics of Amos & Kolter,
+ * "OptNet", 2017, section 3).  At the returned x, y, s, z of member b the differentiated KKT conditions are a linear system
+ * with the matrix
+ *     K = [P A' G'; A 0 0; G 0 -diag(s / z)],
+ * the Newton matrix of the solver in the scaling di = sqrt(z / s): csrc/qp_batch_diff.hip assembles and factors it per member
+ * as kvx_qp_batch_solve does (S = P + G' diag(z / s) G, X = L^-1 A', K = X'X), one workgroup per member, ONE launch, and solves
+ * with `refinement` (0 to 3) steps of iterative refinement on the full system in float64 (the shape of f4, coneprog.py:2288-2316).
+ * B, n, ml, p, P, G, A, their strides and their limits are those of kvx_qp_batch_solve; q, h, b do not enter.  x (n x B),
+ * y (p x B), s, z (ml x B) and exitcode (B) are what kvx_qp_batch_solve returned.  The derivative is that of the solution handed
+ * in, a point of the central path: for derivatives of the exact QP solve with tolerances near 1e-8 to 1e-9.
+ * kvx_qp_batch_vjp (reverse mode): the cotangent gx (n x B); K [ux; uy; uz] = [-gx; 0; 0].  Results ux (n x B), uy (p x B),
+ * uz (ml x B) -- the gradients of q, h, b are ux, -uz, -uy -- and for each of gP, gG, gA that is not NULL the gradient of that
+ * matrix, (ux x' + x ux') / 2, uz x' + z ux', uy x' + y ux', column-major: per member, one after the other (B n^2, B ml n,
+ * B p n doubles), where the matrix has a member stride, and the sum over the members as one matrix where its stride is 0
+ * (csrc/qp_batch_diff.hip, k_batch_outer_sum: a second launch, fixed order, no atomics).  gP is symmetric to the last bit.
+ * kvx_qp_batch_jvp (forward mode): perturbations dP (symmetric, its lower triangle read), dq, dG, dh, dA, db, each NULL (zero)
+ * or with its member stride in doubles (0: one for all, otherwise at least its size);
+ * K [dx; dy; dz] = [-(dP x + dq + dG'z + dA'y); db - dA x; dh - dG x] and ds = -(s / z) dz.  Results dx, dy, dz, ds.
+ * gexit (B): 0 done; 1 skipped, the member's exitcode is not 0; 2 a pivot of S or K failed (<= 0 or not finite) or an entry of
+ * s or z is not positive and finite.  A member with 1 or 2 has zeros in every result and adds nothing to a sum.  A member's
+ * bytes depend on its own data alone, not on B or its place; two identical calls return identical bytes.  A, y, uy / dy, gA,
+ * dA, db may be NULL when p = 0.
+ * kvx_qp_batch_vjp, kvx_qp_batch_jvp: host pointers; upload, launch, download.  The _dev entries: device pointers, no
+ * workspace, results complete on return -- what an autograd function binds.  KVX_EINVAL for bad sizes, limits, strides, a
+ * refinement outside 0 to 3 or NULL required pointers on any box, before a device is asked for; KVX_EDEVICE without a GPU
+ * (never a CPU fallback).  kvx_qp_batch_diff_lds_bytes: the LDS of one workgroup of the derivative in bytes, -1 outside the
+ * limits; *forward (may be NULL): that of kvx_qp_batch_solve, which is never smaller. */
+int kvx_qp_batch_vjp(int64_t B, int64_t n, int64_t ml, int64_t p, const double *P, int64_t sP, const double *G, int64_t sG,
+                     const double *A, int64_t sA, const double *x, const double *y, const double *s, const double *z,
+                     const int64_t *exitcode, int64_t refinement, const double *gx, double *ux, double *uy, double *uz, double *gP,
+                     double *gG, double *gA, int64_t *gexit);
+int kvx_qp_batch_vjp_dev(int64_t B, int64_t n, int64_t ml, int64_t p, const double *P, int64_t sP, const double *G, int64_t sG,
+                         const double *A, int64_t sA, const double *x, const double *y, const double *s, const double *z,
+                         const int64_t *exitcode, int64_t refinement, const double *gx, double *ux, double *uy, double *uz, double *gP,
+                         double *gG, double *gA, int64_t *gexit);
+int kvx_qp_batch_jvp(int64_t B, int64_t n, int64_t ml, int64_t p, const double *P, int64_t sP, const double *G, int64_t sG,
+                     const double *A, int64_t sA, const double *x, const double *y, const double *s, const double *z,
+                     const int64_t *exitcode, int64_t refinement, const double *dP, int64_t sdP, const double *dq, int64_t sdq,
+                     const double *dG, int64_t sdG, const double *dh, int64_t sdh, const double *dA, int64_t sdA, const double *db,
+                     int64_t sdb, double *dx, double *dy, double *dz, double *ds, int64_t *gexit);
+int kvx_qp_batch_jvp_dev(int64_t B, int64_t n, int64_t ml, int64_t p, const double *P, int64_t sP, const double *G, int64_t sG,
+                         const double *A, int64_t sA, const double *x, const double *y, const double *s, const double *z,
+                         const int64_t *exitcode, int64_t refinement, const double *dP, int64_t sdP, const double *dq, int64_t sdq,
+                         const double *dG, int64_t sdG, const double *dh, int64_t sdh, const double *dA, int64_t sdA, const double *db,
+                         int64_t sdb, double *dx, double *dy, double *dz, double *ds, int64_t *gexit);
+int64_t kvx_qp_batch_diff_lds_bytes(int64_t n, int64_t ml, int64_t p, int64_t *forward);
+
 /* ---- B small dense LPs, each with its own matrices: replaces a loop of solvers.lp calls (coneprog.py:662-1436 on the orthant:
  * the starting point with W = I, both pushes and the optimal-at-iteration-0 return :662-842, the residuals and the three
  * stopping tests with their scalings :861-1024, the scaling, the constant system and f6_no_ir :1031-1195, the two directions

@@ -241,6 +241,11 @@ _SIGS = {
     "kvx_admm_batch_end": (ctypes.c_int, [vp]),
     "kvx_qp_batch_solve": (ctypes.c_int, [i64] * 4 + [f64p, i64] * 6 + [i64, f64, f64, f64, ctypes.c_int] + [f64p] * 5 + [i64p] * 2),
     "kvx_qp_batch_solve_dev": (ctypes.c_int, [i64] * 4 + [vp, i64] * 6 + [i64, f64, f64, f64, ctypes.c_int] + [vp] * 7),
+    "kvx_qp_batch_vjp": (ctypes.c_int, [i64] * 4 + [f64p, i64] * 3 + [f64p] * 4 + [i64p, i64] + [f64p] * 7 + [i64p]),
+    "kvx_qp_batch_vjp_dev": (ctypes.c_int, [i64] * 4 + [vp, i64] * 3 + [vp] * 5 + [i64] + [vp] * 8),
+    "kvx_qp_batch_jvp": (ctypes.c_int, [i64] * 4 + [f64p, i64] * 3 + [f64p] * 4 + [i64p, i64] + [f64p, i64] * 6 + [f64p] * 4 + [i64p]),
+    "kvx_qp_batch_jvp_dev": (ctypes.c_int, [i64] * 4 + [vp, i64] * 3 + [vp] * 5 + [i64] + [vp, i64] * 6 + [vp] * 5),
+    "kvx_qp_batch_diff_lds_bytes": (i64, [i64] * 3 + [i64p]),
     "kvx_lp_batch_solve": (ctypes.c_int, [i64] * 4 + [f64p, i64] * 5 + [i64, f64, f64, f64] + [f64p] * 5 + [i64p] * 2),
     "kvx_lp_batch_solve_dev": (ctypes.c_int, [i64] * 4 + [vp, i64] * 5 + [i64, f64, f64, f64] + [vp] * 7),
     "kvx_socp_batch_solve": (ctypes.c_int, [i64] * 4 + [i64p, i64] + [f64p, i64] * 5 + [i64, f64, f64, f64] + [f64p] * 5 + [i64p] * 2),

@@ -14,6 +14,11 @@
     gp(K, F, g, G=None, h=None, A=None, b=None)                                      cvxprog.py:1967 (-> cvx.gp: kvx_gp_eval_dev, cp)
     qp_batch(P, q, G, h, A=None, b=None, options=None)                               no counterpart: B small dense QPs in one launch
                                                                                      (-> qpbatch.qp_batch; reads its own `options` only)
+    qp_batch_vjp(P, q, G, h, A=None, b=None, *, sol, gx, wrt=..., options=None)      no counterpart: the gradients of a loss through a
+                                                                                     solved qp_batch, from its cotangent gx = dl/dx
+    qp_batch_jvp(P, q, G, h, A=None, b=None, *, sol, dP=None, ..., db=None,          no counterpart: the directional derivative of the
+                 options=None)                                                       solution of a solved qp_batch
+                                                                                     (-> qpbatchdiff; options: 'refinement' 0..3 only)
     lp_batch(c, G, h, A=None, b=None, options=None)                                  no counterpart: B small dense LPs in one launch,
                                                                                      with conelp's infeasibility certificates
                                                                                      (-> lpbatch.lp_batch; reads its own `options` only)
@@ -57,6 +62,7 @@ from .coneqpbatch import coneqp_batch  # noqa: F401
 from .gpbatch import gp_batch  # noqa: F401
 from .lpbatch import lp_batch  # noqa: F401
 from .qpbatch import qp_batch  # noqa: F401
+from .qpbatchdiff import qp_batch_jvp, qp_batch_vjp  # noqa: F401
 from .sdpbatch import sdp_batch  # noqa: F401
 from .socpbatch import socp_batch  # noqa: F401
 
