@@ -291,7 +291,11 @@ void kvx_free(void *p);
 /* Plan S = G' diag(w) G (+ P) on a fixed lower-triangular CCS pattern (misc.py:1418-1426,
  * 1451-1455 -> sparse.c:1260-1283, 2176-2256).  G is ml x n CCS.  The plan computes the
  * pattern of tril(G'G) (union with the lower pattern of P when Pp != NULL) and returns it
- * through kvx_atda_pattern(). */
+ * through kvx_atda_pattern().  The lower triangle of P is read: an entry above the diagonal is in
+ * neither the pattern nor the sum, so a full symmetric P gives what its lower triangle gives;
+ * entries stored at one position are added in the order they are stored.  Every entry of S is
+ * written by one lane (no floating-point atomics), and an entry of a lower triangle without
+ * repeats is S_ij + P_ij in one addition. */
 int kvx_atda_plan(int64_t ml, int64_t n, const int64_t *Gp, const int64_t *Gi,
                   const int64_t *Pp, const int64_t *Pi, kvx_atda **out);
 int kvx_atda_pattern(kvx_atda *T, int64_t *snz, int64_t *Sp, int64_t *Si);

@@ -374,9 +374,20 @@ __global__ __launch_bounds__(256) void k_atda(int64_t snz, const int64_t *__rest
     if (LPE >= 4) acc += __shfl_xor(acc, 2);
     if (sub == 0 && e < snz) sx[e] = acc;
 }
-__global__ void k_add_at(int64_t pnz, const int64_t *__restrict__ slot, const double *__restrict__ px, double *__restrict__ sx)
+// S += tril(P): one lane per stored entry e of S gathers the entries of the caller's P that lie at its position, qi[qp[e] .. qp[e + 1]),
+// in the order they are stored, and writes the slot once (an entry of a lower triangle without repeats: S_ij + P_ij in one addition).
+// Entries of P above the diagonal are in no list.
+__global__ void k_add_p(int64_t snz, const int64_t *__restrict__ qp, const int64_t *__restrict__ qi, const double *__restrict__ px,
+                        double *__restrict__ sx)
 {
-    GS_LOOP(q, pnz) sx[slot[q]] += px[q];
+    GS_LOOP(e, snz) {
+        const int64_t q0 = qp[e], q1 = qp[e + 1];
+        if (q0 < q1) {
+            double v = sx[e];
+            for (int64_t q = q0; q < q1; q++) v += px[qi[q]];
+            sx[e] = v;
+        }
+    }
 }
 void launch_atda(hipStream_t st, int64_t snz, int64_t gnz, const int64_t *pp, const int32_t *pa, const int32_t *pb,
                  const int32_t *gi, const double *gx, const double *w, double *wg, double *sx, bool w_is_di)
@@ -389,8 +400,8 @@ void launch_atda(hipStream_t st, int64_t snz, int64_t gnz, const int64_t *pp, co
     else if (lpe == 2) hipLaunchKernelGGL(k_atda<2>, dim3((unsigned)((2 * snz + 255) / 256)), dim3(256), 0, st, snz, pp, pa, pb, wg, gx, sx);
     else hipLaunchKernelGGL(k_atda<1>, dim3((unsigned)((snz + 255) / 256)), dim3(256), 0, st, snz, pp, pa, pb, wg, gx, sx);
 }
-void launch_add_at(hipStream_t st, int64_t pnz, const int64_t *slot, const double *px, double *sx)
-{ if (pnz > 0) hipLaunchKernelGGL(k_add_at, dim3(grid_for(pnz)), dim3(256), 0, st, pnz, slot, px, sx); }
+void launch_add_p(hipStream_t st, int64_t snz, const int64_t *qp, const int64_t *qi, const double *px, double *sx)
+{ if (snz > 0) hipLaunchKernelGGL(k_add_p, dim3(grid_for(snz)), dim3(256), 0, st, snz, qp, qi, px, sx); }
 
 // ---- CCS mat-vec -------------------------------------------------------------------------------------
 // 'T': y_j = beta*y_j + alpha * <A(:,j), x>  -- one 16-lane group per column (columns are short).

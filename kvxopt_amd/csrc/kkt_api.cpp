@@ -29,9 +29,9 @@ struct kvx_atda {
     std::vector<int64_t> Sp, Si;
     std::vector<int64_t> pp;        // [snz+1]
     std::vector<int32_t> pa, pb;    // product list: indices into Gx
-    std::vector<int64_t> pslot;     // per entry of the caller's P arrays: slot in S (or -1)
+    std::vector<int64_t> qp, qi;    // per slot of S: the entries of the caller's P arrays at its position, qi[qp[e] .. qp[e + 1]), as stored
     bool dev = false;
-    int64_t *d_pp = nullptr, *d_pslot = nullptr;
+    int64_t *d_pp = nullptr, *d_qp = nullptr, *d_qi = nullptr;
     int32_t *d_pa = nullptr, *d_pb = nullptr, *d_gi = nullptr;
     std::vector<int32_t> gi32;
     double *d_gx = nullptr, *d_w = nullptr, *d_px = nullptr, *d_sx = nullptr;   // staging for the host variant
@@ -84,7 +84,10 @@ int atda_device(kvx_atda *T)
     if ((rc = up(&T->d_pa, T->pa))) return rc;
     if ((rc = up(&T->d_pb, T->pb))) return rc;
     if ((rc = up(&T->d_gi, T->gi32))) return rc;
-    if ((rc = up(&T->d_pslot, T->pslot))) return rc;
+    if (T->pnz > 0) {
+        if ((rc = up(&T->d_qp, T->qp))) return rc;
+        if ((rc = up(&T->d_qi, T->qi))) return rc;
+    }
     HIPCHK(pool_malloc((void **)&T->d_wg, std::max<int64_t>(T->gnz, 1) * sizeof(double)));
     T->dev = true;
     return KVX_OK;
@@ -174,16 +177,22 @@ static int kvx_atda_plan_impl(int64_t ml, int64_t n, const int64_t *Gp, const in
         }
     }
     if (Pp) {
+        // per slot the positions of P's entries that fall on it, in storage order: the lower triangle is read, as for 'L' storage --
+        // an entry above the diagonal is in no list, entries stored at one position are all in that slot's list
         T->pnz = Pp[n];
-        T->pslot.assign((size_t)T->pnz, -1);
+        T->qp.assign((size_t)T->snz + 1, 0);
+        T->qi.clear();
+        std::vector<int64_t> pslot((size_t)T->pnz, -1);
         for (int64_t j = 0; j < n; j++) {
             for (int64_t e = T->Sp[j]; e < T->Sp[j + 1]; e++) slot[T->Si[e]] = e;
             for (int64_t p = Pp[j]; p < Pp[j + 1]; p++)
-                if (Pi[p] >= j) T->pslot[p] = slot[Pi[p]];
+                if (Pi[p] >= j) { pslot[p] = slot[Pi[p]]; T->qp[pslot[p] + 1]++; }
         }
-        // entries of P above the diagonal are ignored (lower triangle is read, as for 'L' storage)
+        for (int64_t e = 0; e < T->snz; e++) T->qp[e + 1] += T->qp[e];
+        T->qi.resize((size_t)T->qp[T->snz]);
+        std::vector<int64_t> cur(T->qp.begin(), T->qp.end() - 1);
         for (int64_t p = 0; p < T->pnz; p++)
-            if (T->pslot[p] < 0) T->pslot[p] = 0;   // neutralised below by a zero value
+            if (pslot[p] >= 0) T->qi[cur[pslot[p]]++] = p;
     }
     *out = hold.release();
     return KVX_OK;
@@ -215,7 +224,7 @@ int kvx_atda_assemble_dev(kvx_atda *T, const double *Gx, const double *w, const 
     int rc = atda_device(T);
     if (rc) return rc;
     launch_atda(nullptr, T->snz, T->gnz, T->d_pp, T->d_pa, T->d_pb, T->d_gi, Gx, w, T->d_wg, Sx);
-    if (Px && T->pnz > 0) launch_add_at(nullptr, T->pnz, T->d_pslot, Px, Sx);
+    if (Px && T->pnz > 0) launch_add_p(nullptr, T->snz, T->d_qp, T->d_qi, Px, Sx);
     HIPCHK(hipGetLastError());
     return KVX_OK;
 }
@@ -227,7 +236,7 @@ int kvx_atda_assemble_sq_dev(kvx_atda *T, const double *Gx, const double *di, co
     int rc = atda_device(T);
     if (rc) return rc;
     launch_atda(nullptr, T->snz, T->gnz, T->d_pp, T->d_pa, T->d_pb, T->d_gi, Gx, di, T->d_wg, Sx, true);
-    if (Px && T->pnz > 0) launch_add_at(nullptr, T->pnz, T->d_pslot, Px, Sx);
+    if (Px && T->pnz > 0) launch_add_p(nullptr, T->snz, T->d_qp, T->d_qi, Px, Sx);
     HIPCHK(hipGetLastError());
     return KVX_OK;
 }
@@ -245,10 +254,7 @@ static int kvx_atda_assemble_impl(kvx_atda *T, const double *Gx, const double *w
     }
     if (T->gnz) HIPCHK(hipMemcpy(T->d_gx, Gx, T->gnz * sizeof(double), hipMemcpyHostToDevice));
     if (T->ml) HIPCHK(hipMemcpy(T->d_w, w, T->ml * sizeof(double), hipMemcpyHostToDevice));
-    std::vector<double> ptmp;
-    if (Px && T->pnz) {
-        HIPCHK(hipMemcpy(T->d_px, Px, T->pnz * sizeof(double), hipMemcpyHostToDevice));
-    }
+    if (Px && T->pnz) HIPCHK(hipMemcpy(T->d_px, Px, T->pnz * sizeof(double), hipMemcpyHostToDevice));
     rc = kvx_atda_assemble_dev(T, T->d_gx, T->d_w, (Px && T->pnz) ? T->d_px : nullptr, T->d_sx);
     if (rc) return rc;
     HIPCHK(hipDeviceSynchronize());
@@ -264,7 +270,7 @@ int kvx_atda_assemble(kvx_atda *T, const double *Gx, const double *w, const doub
 void kvx_atda_free(kvx_atda *T)
 {
     if (!T) return;
-    void *ptrs[] = {T->d_pp, T->d_pslot, T->d_pa, T->d_pb, T->d_gi, T->d_gx, T->d_w, T->d_px, T->d_sx, T->d_wg};
+    void *ptrs[] = {T->d_pp, T->d_qp, T->d_qi, T->d_pa, T->d_pb, T->d_gi, T->d_gx, T->d_w, T->d_px, T->d_sx, T->d_wg};
     for (void *p : ptrs)
         if (p) (void)pool_free(p);
     delete T;
