@@ -1,8 +1,8 @@
-// What the four batch solvers share outside their kernels (qp_batch, lp_batch, socp_batch, sdp_batch): the part of the kernel
-// arguments that is the same for all, and for the host entries (*_batch_api.cpp) the refusal with its message, the checks of
-// pointers, strides and options, the question for a device, the arguments packed from the C ABI, and the one ladder of upload,
-// allocation, launch, synchronisation and download.  A host entry keeps its limits with their texts, the placement of its cone
-// and its two extern "C" functions.
+// What the batch solvers share outside their kernels (qp_batch, lp_batch, socp_batch, sdp_batch, conelp_batch, coneqp_batch,
+// gp_batch, and the derivatives of qp_batch_diff): the part of the kernel arguments that is the same for all, and for the host
+// entries (*_batch_api.cpp) the refusal with its message, the checks of pointers, strides and options, the question
+// for a device, the arguments packed from the C ABI, and the one ladder of upload, allocation, launch, synchronisation and
+// download.  A host entry keeps its limits with their texts, the placement of its cone and its two extern "C" functions.
 #pragma once
 #include "../../include/kvxhip.h"
 #include "abi_guard.hpp"

@@ -2,16 +2,14 @@
 // status or its infeasibility certificate (conelp_batch.hpp).  It is conelp_member (batch_conelp.hpp) on the cone
 // K = R^ml_+ x Q^{q_0} x ... x S^{m_0}_+ x ... with all three kinds at once.  The policy below is the composition of the two that
 // k_socp_batch and k_sdp_batch carry: per operation the orthant functions of batch_conelp.hpp / batch_kkt.hpp on the 'l' rows,
-// the 'q' operations of socp_batch.hip on the 'q' rows and the 's' operations of sdp_batch.hip on the 's' rows, each written as
-// there (the reference's misc.compute_scaling / update_scaling, misc.py:284-419, 444-634, and scale, scale2, sprod, sinv, sdot,
+// the 'q' operations of batch_cone_q.hpp on the 'q' rows and the 's' operations of batch_cone_s.hpp on the 's' rows (the
+// reference's misc.compute_scaling / update_scaling, misc.py:284-419, 444-634, and scale, scale2, sprod, sinv, sdot,
 // max_step of misc_solvers.c), strung together as cone.py::_ConeEngine strings them.
 //
-// The cone's device code -- the layout, the member, the 'q' and 's' operations, W, the assembly of S and the policy -- is
-// batch_cone.hpp, included below into this file's anonymous namespace and shared with k_coneqp_batch; this kernel's instructions
-// are those it had when the text stood here.  The two sibling files keep their 'q' and 's' code in their anonymous
-// namespaces: their members' bytes are pinned by digests, and a block's bytes depend on which products the compiler contracts into
-// its additions (sum16), which moving the functions into shared headers could change.  What a member of this kernel computes on
-// a row of a kind is the expression the sibling has for it.
+// The cone's device code is batch_cone.hpp, included below into this file's anonymous namespace and shared with k_coneqp_batch:
+// the layout, the member, W, the assembly of S and the policy.  The 'q' and the 's' operations it strings together are
+// batch_cone_q.hpp and batch_cone_s.hpp, the text k_socp_batch and k_sdp_batch run as well, each kernel with an internal copy
+// (DESIGN 16, 17, 18).  What a member of this kernel computes on a row of a kind is what the sibling computes on it.
 //
 // Rows.  A vector of the cone has N = ml + sum q_k + sum m_k^2 entries: the 'l' rows, the cones, then every 's' block as its full
 // symmetric m x m matrix, column-major with leading dimension m; both triangles are written from one value.  G and h are read

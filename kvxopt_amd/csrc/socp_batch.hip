@@ -1,9 +1,9 @@
 // k_socp_batch: one workgroup (256 threads, four wavefronts) carries one small dense second-order-cone program from its starting
 // point to its status or its infeasibility certificate (socp_batch.hpp).  It is conelp_member (batch_conelp.hpp) on the cone
 // K = R^ml_+ x Q^{q_0} x ...: the 'l' rows are the orthant of that header, the 'q' rows are treated by the reference's own
-// operations, the ones csrc/kkt_q.hip carries as stand-alone kernels: misc.compute_scaling / update_scaling (misc.py:290-352,
-// 467-580), scale, scale2, sprod, sinv (misc_solvers.c:144-186, 301-341, 671-700, 803-835) and max_step
-// (misc_solvers.c:1073-1085), strung together as cone.py::_ConeEngine strings them.
+// operations, which are batch_cone_q.hpp, included below into this file's anonymous namespace and shared with k_conelp_batch and
+// k_coneqp_batch, strung together as cone.py::_ConeEngine strings them.  What stands here is this kernel's own: its layout and
+// member, (J v_k)'h_k in place of a stored th, the assembly of S, the glue of the policy, the kernel and the launch.
 //
 // W_k = beta_k (2 v_k v_k' - J) is symmetric, so W^-T = W^-1 = (1 / beta_k)(2 (J v_k)(J v_k)' - J).  S = Gs'Gs with Gs = W^-1 G
 // is assembled from staged rows of Gs, 32 at a time: row i of cone k is (2 (J v_k)_i g_k - (J G_k)_i) / beta_k with the row
@@ -14,10 +14,6 @@
 // rows of the slot whose 'l' rows hold d; one more N-vector of work (W^-1 of a right-hand side); beta_k and (J v_k)'h_k in arrays
 // of length nq; the first row of every cone and the cone of every row as integers; the ring of g_k behind the staged rows, in the
 // region X and K take afterwards.
-//
-// A cone belongs to one wavefront at a time: its lanes run along the rows, a lane adds its rows ascending, the lanes add by
-// the xor butterfly of batch_device.hpp.  The order of a cone's sums depends on its order m_k alone.  A lane reads, of what its
-// wavefront writes in one pass over a cone, only the rows it wrote itself; the first row's values travel in registers.
 #include "socp_batch.hpp"
 #include "batch_conelp.hpp"
 
@@ -65,55 +61,14 @@ struct Member : ConelpMem {                   // N = ml + sum q_k
     unsigned short *cone;                     // cone[r - ml]: the cone of row r >= ml
 };
 
-// r[0..K) := the sums over the rows i = 0..m-1 of a cone of what f adds for row i, the same bytes in every lane of the wavefront
-template <int K, class F>
-__device__ inline void cone_sum(int m, double (&r)[K], F f)
-{
-#pragma unroll
-    for (int k = 0; k < K; k++) r[k] = 0.0;
-    for (int i = threadIdx.x & 63; i < m; i += 64) f(i, r);
-#pragma unroll
-    for (int k = 0; k < K; k++) r[k] = wave_sum(r[k]);
-}
-
-__device__ inline double jsign(int i, double u) { return i ? -u : u; }                     // (J u)_i
-__device__ inline double jnrm(double x0, double tail_sq)                                  // misc.jnrm2 as the reference forms it
-{
-    const double a = sqrt(tail_sq);
-    return sqrt(x0 - a) * sqrt(x0 + a);
-}
+#include "batch_cone_q.hpp"
 
 // out := W^-1 in (INV) or W in; in == out is allowed.  The caller's barriers stand before and after.
 template <bool INV>
 __device__ void wscale(const Member &M, const double *in, double *out)
 {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    for (int k = tid; k < M.ml; k += NT) out[k] = (INV ? M.di[k] : M.d[k]) * in[k];
-    for (int c = w; c < M.nq; c += NW) {
-        const int o = M.off[c], m = M.off[c + 1] - o;
-        const double *v = M.d + o;
-        double r[1];
-        cone_sum<1>(m, r, [&](int i, double (&r)[1]) { r[0] += (INV ? jsign(i, v[i]) : v[i]) * in[o + i]; });
-        const double be = M.beta[c];
-        for (int i = lane; i < m; i += 64) {
-            const double t = 2.0 * (INV ? jsign(i, v[i]) : v[i]) * r[0] - jsign(i, in[o + i]);
-            out[o + i] = INV ? t / be : t * be;
-        }
-    }
-}
-
-// mx[0], mx[1] := the larger of themselves and max_step over the 'q' blocks of a1 u1 and a2 u2 (misc_solvers.c:1073-1085)
-__device__ void cone_max_step(const Member &M, const double *u1, double a1, const double *u2, double a2, double (&mx)[2])
-{
-    for (int c = threadIdx.x >> 6; c < M.nq; c += NW) {
-        const int o = M.off[c], m = M.off[c + 1] - o;
-        double r[2];
-        cone_sum<2>(m, r, [&](int i, double (&r)[2]) {
-            if (i) { const double t1 = a1 * u1[o + i], t2 = a2 * u2[o + i]; r[0] += t1 * t1; r[1] += t2 * t2; }
-        });
-        mx[0] = fmax(mx[0], sqrt(r[0]) - a1 * u1[o]);
-        mx[1] = fmax(mx[1], sqrt(r[1]) - a2 * u2[o]);
-    }
+    for (int k = threadIdx.x; k < M.ml; k += NT) out[k] = (INV ? M.di[k] : M.d[k]) * in[k];
+    cones_wscale<INV>(M, in, out);
 }
 
 // hv[k] := (J v_k)'h_k.  The caller's barriers stand before and after.
@@ -204,7 +159,7 @@ struct Cone {                                 // the cone of conelp_member: the 
     __device__ __forceinline__ void max_step(const double *u0, double a0, const double *u1, double a1, double (&mx)[2]) const
     {
         orth_max_step(M.ml, u0, a0, u1, a1, mx);
-        cone_max_step(M, u0, a0, u1, a1, mx);
+        cones_max_step(M, u0, a0, u1, a1, mx);
         blk_reduce<2, true>(mx, M.red);
     }
     __device__ __forceinline__ void push(bool ps, bool pz, const double (&mx)[2]) const
@@ -218,31 +173,8 @@ struct Cone {                                 // the cone of conelp_member: the 
     }
     __device__ __forceinline__ bool first_scaling() const                           // misc.py:284-352
     {
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nq = M.nq;
         orth_first_scaling(M.ml, M.s, M.z, M.d, M.di, M.lm);
-        for (int c = w; c < nq; c += NW) {
-            const int o = M.off[c], m = M.off[c + 1] - o;
-            const double *sk = M.s + o, *zk = M.z + o;
-            double q[3];                               // |s1|^2, |z1|^2, s'z
-            cone_sum<3>(m, q, [&](int i, double (&q)[3]) {
-                const double u = sk[i], v = zk[i];
-                if (i) { q[0] += u * u; q[1] += v * v; }
-                q[2] += u * v;
-            });
-            const double s0 = sk[0], z0 = zk[0], aa = jnrm(s0, q[0]), bb = jnrm(z0, q[1]);
-            const double cc = sqrt((q[2] / aa / bb + 1.0) / 2.0);
-            const double v0 = (z0 / bb + s0 / aa) * (1.0 / 2.0 / cc) + 1.0, vs = 1.0 / sqrt(2.0 * v0);
-            const double dd = 2.0 * cc + s0 / aa + z0 / bb;
-            const double cs = (cc + z0 / bb) / dd / aa, cz = (cc + s0 / aa) / dd / bb, sab = sqrt(aa * bb);
-            for (int i = lane; i < m; i += 64) {
-                if (i == 0) { M.d[o] = v0 * vs; M.lm[o] = cc * sab; }
-                else {
-                    M.d[o + i] = ((-zk[i] / bb + sk[i] / aa) * (1.0 / 2.0 / cc)) * vs;
-                    M.lm[o + i] = (sk[i] * cs + zk[i] * cz) * sab;
-                }
-            }
-            if (lane == 0) M.beta[c] = sqrt(aa / bb);
-        }
+        cones_scaling(M);
         return true;
     }
     __device__ __forceinline__ double lam_sq() const { return sum_sq(M.lm, M.N, M.red); }
@@ -273,38 +205,8 @@ struct Cone {                                 // the cone of conelp_member: the 
     }
     __device__ __forceinline__ void rhs(int i, double sigma, double mu) const
     {
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nq = M.nq;
         orth_rhs<true>(M.ml, i, sigma, mu, M.lm, M.ws3, M.d, M.rz, M.ds, M.dz);
-        for (int c = w; c < nq; c += NW) {
-            const int o = M.off[c], m = M.off[c + 1] - o;
-            const double *lm = M.lm + o, *v = M.d + o;
-            const double l0 = lm[0];
-            double q[2];                               // lmbda'lmbda, |lmbda_1|^2
-            cone_sum<2>(m, q, [&](int j, double (&q)[2]) { const double t = lm[j] * lm[j]; q[0] += t; if (j) q[1] += t; });
-            double d0 = q[0];                          // sprod (misc_solvers.c:671-700): head lmbda'lmbda, tail 2 l0 lmbda_1
-            if (i == 1) d0 += M.ws3[o] - sigma * mu;
-            double u[1];                               // sinv (misc_solvers.c:803-835)
-            cone_sum<1>(m, u, [&](int j, double (&u)[1]) {
-                if (j) { double t = l0 * lm[j] + lm[j] * l0; if (i == 1) t += M.ws3[o + j]; u[0] += t * lm[j]; }
-            });
-            const double nl = sqrt(q[1]), aq = (l0 + nl) * (l0 - nl), dq = u[0];
-            double vd[1];                              // v'ds of W'ds
-            cone_sum<1>(m, vd, [&](int j, double (&vd)[1]) {
-                double t;
-                if (j == 0) t = (d0 * l0 - dq) * (1.0 / aq);
-                else {
-                    t = l0 * lm[j] + lm[j] * l0;
-                    if (i == 1) t += M.ws3[o + j];
-                    t = (t * (aq / l0) + (dq / l0 - d0) * lm[j]) * (1.0 / aq);
-                }
-                t = -t;
-                M.ds[o + j] = t;
-                vd[0] += v[j] * t;
-            });
-            const double be = M.beta[c];
-            for (int j = lane; j < m; j += 64)
-                M.dz[o + j] = -((1.0 - sigma) * M.rz[o + j] + (2.0 * v[j] * vd[0] - jsign(j, M.ds[o + j])) * be);
-        }
+        cones_rhs(M, i, sigma, mu);
     }
     __device__ __forceinline__ double th_dot(const double *dz) const
     {
@@ -314,91 +216,14 @@ struct Cone {                                 // the cone of conelp_member: the 
     }
     __device__ __forceinline__ void combine(int i, double dtau, double (&mx)[2]) const
     {
-        const int w = threadIdx.x >> 6, nq = M.nq;
         orth_combine(M.ml, i, dtau, M.lm, M.z1, M.ds, M.dz, M.ws3, mx);
-        for (int c = w; c < nq; c += NW) {
-            const int o = M.off[c], m = M.off[c + 1] - o;
-            const double *lm = M.lm + o;
-            const double l0 = lm[0], z0 = M.dz[o] + dtau * M.z1[o], s0 = M.ds[o] - z0;
-            double q[4];                               // ds'dz, |lmbda_1|^2, lmbda_1'ds_1, lmbda_1'dz_1
-            cone_sum<4>(m, q, [&](int j, double (&q)[4]) {
-                const double zk = M.dz[o + j] + dtau * M.z1[o + j], sk = M.ds[o + j] - zk;
-                M.ds[o + j] = sk; M.dz[o + j] = zk;
-                q[0] += sk * zk;
-                if (j) { q[1] += lm[j] * lm[j]; q[2] += lm[j] * sk; q[3] += lm[j] * zk; }
-            });
-            const double nl = sqrt(q[1]), aq = sqrt(l0 + nl) * sqrt(l0 - nl);          // scale2 (misc_solvers.c:301-341)
-            const double lxs = (l0 * s0 - q[2]) / aq, lxz = (l0 * z0 - q[3]) / aq;
-            const double bs = -((s0 + lxs) / (l0 / aq + 1.0) / aq), bz = -((z0 + lxz) / (l0 / aq + 1.0) / aq);
-            double t2[2];
-            cone_sum<2>(m, t2, [&](int j, double (&t2)[2]) {
-                const double sk = M.ds[o + j], zk = M.dz[o + j];
-                if (i == 0) M.ws3[o + j] = j ? z0 * sk + s0 * zk : q[0];
-                const double s2 = (j ? sk + bs * lm[j] : lxs) * (1.0 / aq), z2 = (j ? zk + bz * lm[j] : lxz) * (1.0 / aq);
-                M.ds[o + j] = s2; M.dz[o + j] = z2;
-                if (j) { t2[0] += s2 * s2; t2[1] += z2 * z2; }
-            });
-            mx[0] = fmax(mx[0], sqrt(t2[0]) - lxs * (1.0 / aq));
-            mx[1] = fmax(mx[1], sqrt(t2[1]) - lxz * (1.0 / aq));
-        }
+        cones_combine(M, i, dtau, mx);
         blk_reduce<2, true>(mx, M.red);
     }
     __device__ __forceinline__ void update(double step) const                       // misc.py:444-580; s = W'lmbda and z = W^-1 lmbda
     {
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nq = M.nq;
         orth_update(M.ml, step, M.ds, M.dz, M.d, M.di, M.lm, M.s, M.z);
-        for (int c = w; c < nq; c += NW) {
-            const int o = M.off[c], m = M.off[c + 1] - o;
-            double *lm = M.lm + o, *v = M.d + o;
-            const double l0 = lm[0], vk0 = v[0], e0s = 1.0 + step * M.ds[o], e0z = 1.0 + step * M.dz[o];
-            // ds := e + step ds, dz := e + step dz, then scale2 with inverse 'I': the new iterates in the current scaling
-            double q[3];                                   // lmbda'ds, lmbda'dz, |lmbda_1|^2
-            cone_sum<3>(m, q, [&](int j, double (&q)[3]) {
-                const double sk = (j ? 0.0 : 1.0) + step * M.ds[o + j], zk = (j ? 0.0 : 1.0) + step * M.dz[o + j];
-                M.ds[o + j] = sk; M.dz[o + j] = zk;
-                q[0] += lm[j] * sk; q[1] += lm[j] * zk;
-                if (j) q[2] += lm[j] * lm[j];
-            });
-            const double nl = sqrt(q[2]), aq = sqrt(l0 + nl) * sqrt(l0 - nl);
-            const double lxs = q[0] / aq, lxz = q[1] / aq;
-            const double bs = (e0s + lxs) / (l0 / aq + 1.0) / aq, bz = (e0z + lxz) / (l0 / aq + 1.0) / aq;
-            const double S0 = lxs * aq, Z0 = lxz * aq;
-            double u[5];                                   // update_scaling: |s1|^2, |z1|^2, s'z, v's, v'Jz
-            cone_sum<5>(m, u, [&](int j, double (&u)[5]) {
-                const double sk = j ? (M.ds[o + j] + bs * lm[j]) * aq : S0, zk = j ? (M.dz[o + j] + bz * lm[j]) * aq : Z0;
-                M.ds[o + j] = sk; M.dz[o + j] = zk;
-                if (j) { u[0] += sk * sk; u[1] += zk * zk; }
-                u[2] += sk * zk; u[3] += v[j] * sk; u[4] += jsign(j, v[j]) * zk;
-            });
-            const double aa = jnrm(S0, u[0]), bb = jnrm(Z0, u[1]);
-            const double s0 = S0 / aa, z0 = Z0 / bb;
-            const double cc = sqrt((1.0 + u[2] / aa / bb) / 2.0);
-            const double vsd = u[3] / aa, vzd = u[4] / bb;
-            const double vq = (vsd + vzd) / 2.0 / cc, vu = vsd - vzd;
-            const double wk0 = 2.0 * vk0 * vq - (s0 + z0) / 2.0 / cc;
-            const double dd = (vk0 * vu - s0 / 2.0 + z0 / 2.0) / (wk0 + 1.0);
-            const double sab = sqrt(aa * bb);
-            const double nv0 = 2.0 * vq * vk0 - s0 / 2.0 / cc - 0.5 / cc * z0 + 1.0, nvs = 1.0 / sqrt(2.0 * nv0);
-            const double be = M.beta[c] * sqrt(aa / bb);
-            double t2[2];                                  // v'lmbda and (J v)'lmbda of the new scaling
-            cone_sum<2>(m, t2, [&](int j, double (&t2)[2]) {
-                const double si = M.ds[o + j] / aa, zi = M.dz[o + j] / bb, vi = v[j];
-                double ln, vn;
-                if (j == 0) { ln = cc * sab; vn = nv0 * nvs; }
-                else {
-                    ln = (vi * (2.0 * (-dd * vq + 0.5 * vu)) + si * (0.5 * (1.0 - dd / cc)) + zi * (0.5 * (1.0 + dd / cc))) * sab;
-                    vn = (2.0 * vq * vi + 0.5 / cc * si - 0.5 / cc * zi) * nvs;
-                }
-                lm[j] = ln; v[j] = vn;
-                t2[0] += vn * ln; t2[1] += jsign(j, vn) * ln;
-            });
-            for (int j = lane; j < m; j += 64) {
-                const double ln = lm[j], vn = v[j];
-                M.s[o + j] = (2.0 * vn * t2[0] - jsign(j, ln)) * be;
-                M.z[o + j] = (2.0 * jsign(j, vn) * t2[1] - jsign(j, ln)) / be;
-            }
-            if (lane == 0) M.beta[c] = be;
-        }
+        cones_update(M, step);
     }
 };
 

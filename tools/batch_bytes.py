@@ -1,13 +1,14 @@
-"""One SHA-256 per named batch of the five batch solvers: what a change that must not move a bit is held to.
+"""One SHA-256 per named batch of the six batch solvers: what a change that must not move a bit is held to.
 
-    python tools/batch_bytes.py [--only qp,lp,socp,sdp,conelp]
+    python tools/batch_bytes.py [--only qp,lp,socp,sdp,conelp,coneqp]
     KVX_LIB_PATH=/path/to/other/libkvxhip.so python tools/batch_bytes.py
 
-For solvers.qp_batch, lp_batch, socp_batch, sdp_batch and conelp_batch it runs every named batch of
-tests/{qp,lp,socp,sdp,conelp}_batch_numpy.py --
-all of SHAPES, every key of BATCHES (qp: INDEPENDENCE and MIXED), the spoiled "mixed" variants as tests/test_*_batch_gpu.py spoil
-them, and the golden cases as those tests batch them (member 0 of a batch of three with shared matrices and perturbed linear
-terms; the tiny LPs in batches of their own) -- and prints, for each (solver, batch), the SHA-256 over the bytes of x, y, s, z,
+For solvers.qp_batch, lp_batch, socp_batch, sdp_batch, conelp_batch and coneqp_batch it runs every named batch of
+tests/{qp,lp,socp,sdp,conelp,coneqp}_batch_numpy.py --
+all of SHAPES, every key of BATCHES (qp: INDEPENDENCE and MIXED; coneqp: each with its options), the spoiled "mixed" variants as
+tests/test_*_batch_gpu.py spoil them, and the golden cases as those tests batch them (member 0 of a batch of three with shared
+matrices and perturbed linear terms; the tiny LPs in batches of their own; coneqp's with the options recorded with the case) --
+and prints, for each (solver, batch), the SHA-256 over the bytes of x, y, s, z,
 every stat, `iterations`, `exit` and the statuses.  The last line is the whole as JSON.  The library is loaded through
 kvxopt_amd._lib, so KVX_LIB_PATH selects the build; run two builds in two processes and compare the two last lines.  The digests
 belong to one compiler and one device: none is kept in the repository.
@@ -27,6 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import conelp_batch_numpy as CONE  # noqa: E402
+import coneqp_batch_numpy as CONEQP  # noqa: E402
 import lp_batch_numpy as LP  # noqa: E402
 import qp_batch_numpy as QP  # noqa: E402
 import sdp_batch_numpy as SDP  # noqa: E402
@@ -150,6 +152,27 @@ def dims_batches(R, fn, spoil, gfile, cases):
         yield "golden-" + name, fn(perturbed(get("c")), get("G"), get("h"), meta[name]["dims"], get("A"), get("b"))
 
 
+def coneqp_batches():
+    def call(M, options, **replace):
+        a = {"P": M.P, "q": M.q, "G": M.G, "h": M.h, "A": M.A, "b": M.b}
+        a.update(replace)
+        return solvers.coneqp_batch(a["P"], a["q"], a["G"], a["h"], M.dims, a["A"], a["b"], options=options)
+
+    for name in CONEQP.BATCHES:
+        M, options = CONEQP.batch(name), CONEQP.BATCHES[name][4]
+        yield name, call(M, options)
+        if name == "mixed":                                # test_coneqp_batch_gpu.py::test_mixed_outcomes_in_one_batch
+            h = M.h.copy()
+            h[1, CONEQP.MIXED_NAN] = np.nan
+            yield "mixed-spoiled", call(M, options, h=h)
+    meta = json.load(open(os.path.join(GOLDEN, "g29_coneqp_batch.json")))["cases"]
+    g = np.load(os.path.join(GOLDEN, "g29_coneqp_batch.npz"))
+    for name in ("doc_coneqp", "doc_coneqp_garbage", "mixed_eq", "mixed_eq_garbage", "p_rank_deficient", "mixed_eq_cut"):
+        get = lambda k: g["%s__%s" % (name, k)] if "%s__%s" % (name, k) in g else None         # noqa: E731
+        yield "golden-" + name, solvers.coneqp_batch(get("P"), perturbed(get("q")), get("G"), get("h"), meta[name]["dims"], get("A"),
+                                                     get("b"), options=meta[name]["options"])
+
+
 SOLVERS = {
     "qp": (qp_batches, QP_STATS),
     "lp": (lp_batches, LP_STATS),
@@ -159,12 +182,13 @@ SOLVERS = {
                                  ("doc_sdp", "doc_sdp_lower", "mixed_eq", "sdp_pinf", "sdp_dinf")), LP_STATS),
     "conelp": (lambda: dims_batches(CONE, solvers.conelp_batch, spoil_conelp, "g28_conelp_batch",
                                     ("doc_conelp", "doc_conelp_lower", "mixed_eq", "conelp_pinf", "conelp_dinf")), LP_STATS),
+    "coneqp": (coneqp_batches, QP_STATS),
 }
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="qp,lp,socp,sdp,conelp")
+    ap.add_argument("--only", default="qp,lp,socp,sdp,conelp,coneqp")
     a = ap.parse_args()
     _lib.require_device()
     print("library: %s" % _lib.LIB_PATH)
@@ -174,7 +198,7 @@ def main():
         out[solver] = {}
         for name, sol in batches():
             out[solver][name] = digest(sol, stats)
-            print("%-5s %-28s %s" % (solver, name, out[solver][name]), flush=True)
+            print("%-6s %-28s %s" % (solver, name, out[solver][name]), flush=True)
     print(json.dumps(out, sort_keys=True))
 
 
