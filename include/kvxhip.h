@@ -854,6 +854,66 @@ int kvx_coneqp_batch_solve_dev(int64_t B, int64_t n, int64_t ml, int64_t nq, con
                                double abstol, double reltol, double feastol, int use_correction, double *x, double *y, double *s,
                                double *z, double *stats, int64_t *iterations, int64_t *exitcode);
 
+/* ---- derivatives of a solved batch of kvx_coneqp_batch_solve (no reference counterpart).  The differentiated KKT conditions
+ * of member b are a linear system with the matrix
+ *     K = [P A' G'; A 0 0; G 0 -W'W],   W the Nesterov-Todd scaling of (s, z),
+ * the Newton matrix of the solver.  On the 'q' and 's' rows W'W linearises the complementarity condition exactly only on the
+ * central path (lmbda o lmbda = mu e), where the returned point is not.  So csrc/coneqp_batch_diff.hip, one workgroup per
+ * member, ONE launch, first takes at most `centering` (0 to 16) centring steps from x, y, s, z -- a Newton step of the solver
+ * with sigma = 1, no Mehrotra term, mu = s'z / degree of the point handed in, step length min(1, 0.99 / t) -- until
+ * |lmbda o lmbda - mu e|_2 <= centol mu (centol > 0), and then solves with K at the centred point and `refinement` (0 to 3)
+ * steps of iterative refinement on the full system in float64.  centering = 0 takes the point as it is.
+ * B .. sb: the problem as kvx_coneqp_batch_solve takes it, with its limits.  x (n x B), y (p x B), s, z (N x B, 's' blocks as
+ * full symmetric matrices) and exitcode (B) are what kvx_coneqp_batch_solve returned; they are not written.
+ * kvx_coneqp_batch_vjp (reverse mode): the cotangent gx (n x B); K [ux; uy; uz] = [-gx; 0; 0].  Results ux (n x B), uy (p x B),
+ * uz (N x B, 's' blocks full symmetric) -- the gradients of q, h, b are ux, -uz, -uy -- and for each of gP, gG, gA that is not
+ * NULL the gradient of that matrix at the centred x, y, z, (ux x' + x ux') / 2, uz x' + z ux', uy x' + y ux', column-major: per
+ * member, one after the other (B n^2, B N n, B p n doubles), where the matrix has a member stride, and the sum over the done
+ * members as one matrix where its stride is 0 (k_batch_outer_sum of csrc/qp_batch_diff.hip: a second launch, fixed order, no
+ * atomics).  Rows (i, j) and (j, i) of an 's' block of gG and of uz evaluate one expression: the gradient with respect to a
+ * symmetric argument, as gP is; who holds only the lower triangle as free parameters adds the two.
+ * kvx_coneqp_batch_jvp (forward mode): perturbations dP, dq, dG, dh, dA, db, each NULL (zero) or with its member stride in
+ * doubles (0: one for all, otherwise at least its size); of dP and of every 's' block of dG and dh the lower triangle is read.
+ * K [dx; dy; dz] = [-(dP x + dq + dG'z + dA'y); db - dA x; dh - dG x] and ds = -W'W dz.  Results dx, dy, dz, ds.
+ * centrality (B): the final |lmbda o lmbda - mu e|_2 / mu, NaN for a member with gexit 1 or 2; steps (B): the centring steps
+ * taken.  gexit (B): 0 done; 1 skipped, the member's exitcode is not 0; 2 the scaling or a pivot failed or a value is not
+ * finite; 3 not centred within `centering` steps.  A member with 1, 2 or 3 has zeros in every derivative and adds nothing to a
+ * sum.  A member's bytes depend on its own data alone, not on B or its place; two identical calls return identical bytes.
+ * A, b, y, uy / dy, gA, dA, db may be NULL when p = 0.
+ * kvx_coneqp_batch_vjp, kvx_coneqp_batch_jvp: host pointers; upload, launch, download.  The _dev entries: device pointers
+ * (qdims and m excepted), no workspace, results complete on return.  KVX_EINVAL for bad sizes, limits, strides, options or
+ * NULL required pointers on any box, before a device is asked for; KVX_EDEVICE without a GPU (never a CPU fallback).
+ * kvx_coneqp_batch_diff_lds_bytes: the LDS of one workgroup of the derivative in bytes, -1 outside the limits; *forward (may
+ * be NULL): that of kvx_coneqp_batch_solve, which is 8 (n + p) bytes smaller, rounded up to 16 each. */
+int kvx_coneqp_batch_vjp(int64_t B, int64_t n, int64_t ml, int64_t nq, const int64_t *qdims, int64_t ns, const int64_t *m, int64_t p,
+                         const double *P, int64_t sP, const double *q, int64_t sq, const double *G, int64_t sG, const double *h,
+                         int64_t sh, const double *A, int64_t sA, const double *b, int64_t sb, const double *x, const double *y,
+                         const double *s, const double *z, const int64_t *exitcode, int64_t refinement, int64_t centering,
+                         double centol, const double *gx, double *ux, double *uy, double *uz, double *gP, double *gG, double *gA,
+                         double *centrality, int64_t *steps, int64_t *gexit);
+int kvx_coneqp_batch_vjp_dev(int64_t B, int64_t n, int64_t ml, int64_t nq, const int64_t *qdims, int64_t ns, const int64_t *m, int64_t p,
+                             const double *P, int64_t sP, const double *q, int64_t sq, const double *G, int64_t sG, const double *h,
+                             int64_t sh, const double *A, int64_t sA, const double *b, int64_t sb, const double *x, const double *y,
+                             const double *s, const double *z, const int64_t *exitcode, int64_t refinement, int64_t centering,
+                             double centol, const double *gx, double *ux, double *uy, double *uz, double *gP, double *gG, double *gA,
+                             double *centrality, int64_t *steps, int64_t *gexit);
+int kvx_coneqp_batch_jvp(int64_t B, int64_t n, int64_t ml, int64_t nq, const int64_t *qdims, int64_t ns, const int64_t *m, int64_t p,
+                         const double *P, int64_t sP, const double *q, int64_t sq, const double *G, int64_t sG, const double *h,
+                         int64_t sh, const double *A, int64_t sA, const double *b, int64_t sb, const double *x, const double *y,
+                         const double *s, const double *z, const int64_t *exitcode, int64_t refinement, int64_t centering,
+                         double centol, const double *dP, int64_t sdP, const double *dq, int64_t sdq, const double *dG, int64_t sdG,
+                         const double *dh, int64_t sdh, const double *dA, int64_t sdA, const double *db, int64_t sdb, double *dx,
+                         double *dy, double *dz, double *ds, double *centrality, int64_t *steps, int64_t *gexit);
+int kvx_coneqp_batch_jvp_dev(int64_t B, int64_t n, int64_t ml, int64_t nq, const int64_t *qdims, int64_t ns, const int64_t *m, int64_t p,
+                             const double *P, int64_t sP, const double *q, int64_t sq, const double *G, int64_t sG, const double *h,
+                             int64_t sh, const double *A, int64_t sA, const double *b, int64_t sb, const double *x, const double *y,
+                             const double *s, const double *z, const int64_t *exitcode, int64_t refinement, int64_t centering,
+                             double centol, const double *dP, int64_t sdP, const double *dq, int64_t sdq, const double *dG,
+                             int64_t sdG, const double *dh, int64_t sdh, const double *dA, int64_t sdA, const double *db, int64_t sdb,
+                             double *dx, double *dy, double *dz, double *ds, double *centrality, int64_t *steps, int64_t *gexit);
+int64_t kvx_coneqp_batch_diff_lds_bytes(int64_t n, int64_t ml, int64_t nq, const int64_t *qdims, int64_t ns, const int64_t *m, int64_t p,
+                                        int64_t *forward);
+
 /* ---- many small dense geometric programs at once: B members of cvxprog.gp (cvxprog.py:1967-2155: the evaluator :2094-2153,
  * cp's epigraph form :1746-1964, cpl's iteration with its relaxed and backtracking line search :556-1356; the Newton systems
  * of misc.kkt_chol2, misc.py:1395-1563, on S = H + J' diag(di^2) J without an A'A repair)

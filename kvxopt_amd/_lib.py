@@ -259,6 +259,14 @@ _SIGS = {
                                + [i64, f64, f64, f64, ctypes.c_int] + [f64p] * 5 + [i64p] * 2),
     "kvx_coneqp_batch_solve_dev": (ctypes.c_int, [i64] * 4 + [i64p, i64, i64p, i64] + [vp, i64] * 6
                                    + [i64, f64, f64, f64, ctypes.c_int] + [vp] * 7),
+    "kvx_coneqp_batch_vjp": (ctypes.c_int, [i64] * 4 + [i64p, i64, i64p, i64] + [f64p, i64] * 6 + [f64p] * 4 + [i64p, i64, i64, f64]
+                             + [f64p] * 8 + [i64p] * 2),
+    "kvx_coneqp_batch_vjp_dev": (ctypes.c_int, [i64] * 4 + [i64p, i64, i64p, i64] + [vp, i64] * 6 + [vp] * 5 + [i64, i64, f64] + [vp] * 10),
+    "kvx_coneqp_batch_jvp": (ctypes.c_int, [i64] * 4 + [i64p, i64, i64p, i64] + [f64p, i64] * 6 + [f64p] * 4 + [i64p, i64, i64, f64]
+                             + [f64p, i64] * 6 + [f64p] * 5 + [i64p] * 2),
+    "kvx_coneqp_batch_jvp_dev": (ctypes.c_int, [i64] * 4 + [i64p, i64, i64p, i64] + [vp, i64] * 6 + [vp] * 5 + [i64, i64, f64]
+                                 + [vp, i64] * 6 + [vp] * 7),
+    "kvx_coneqp_batch_diff_lds_bytes": (i64, [i64] * 3 + [i64p, i64, i64p, i64, i64p]),
     "kvx_gp_batch_scratch_doubles": (i64, [i64] * 4),
     "kvx_gp_batch_solve": (ctypes.c_int, [i64] * 3 + [i64p, i64, i64] + [f64p, i64] * 6 + [i64, f64, f64, f64] + [f64p] * 5 + [i64p] * 2),
     "kvx_gp_batch_solve_dev": (ctypes.c_int, [i64] * 3 + [i64p, i64, i64] + [vp, i64] * 6 + [i64, f64, f64, f64] + [vp] * 8),

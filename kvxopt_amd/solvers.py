@@ -36,6 +36,12 @@
                                                                                      launch, dims = {'l': ml, 'q': [...], 's': [...]}
                                                                                      shared by the members
                                                                                      (-> coneqpbatch.coneqp_batch; reads its own `options` only)
+    coneqp_batch_vjp(P, q, G, h, dims, A=None, b=None, *, sol, gx, wrt=...,          no counterpart: the gradients of a loss through a
+                     options=None)                                                   solved coneqp_batch, from its cotangent gx = dl/dx
+    coneqp_batch_jvp(P, q, G, h, dims, A=None, b=None, *, sol, dP=None, ...,         no counterpart: the directional derivative of the
+                     db=None, options=None)                                          solution of a solved coneqp_batch, after centring
+                                                                                     (-> coneqpbatchdiff; options: 'refinement' 0..3,
+                                                                                     'centering' 0..16 and 'centol' only)
     gp_batch(K, F, g, G=None, h=None, A=None, b=None, options=None)                  no counterpart: B small dense geometric programs
                                                                                      in one launch, K shared by the members
                                                                                      (-> gpbatch.gp_batch; reads its own `options` only)
@@ -59,6 +65,7 @@ from . import lp as _lp
 from . import osqp as _osqp
 from .conelpbatch import conelp_batch  # noqa: F401
 from .coneqpbatch import coneqp_batch  # noqa: F401
+from .coneqpbatchdiff import coneqp_batch_jvp, coneqp_batch_vjp  # noqa: F401
 from .gpbatch import gp_batch  # noqa: F401
 from .lpbatch import lp_batch  # noqa: F401
 from .qpbatch import qp_batch  # noqa: F401
