@@ -187,6 +187,13 @@ int kvx_chol_prof_read(kvx_chol *F, double *total_ms, int64_t *launches);
 int kvx_dbg_tile_cover(int uonly, const int32_t *hm, const int32_t *hk, int count, int kb, int klen, int col_lim, int tmax,
                        int32_t *counts, int64_t *info);
 int kvx_dbg_syrk_counts(int64_t *out, int reset);
+/* The chain step whose trailing update solves its own panel rows (k_syrk_solve, KVX_SOLVE_IN_UPDATE_TILES).
+ * kvx_dbg_syrk_solve_count: such launches enqueued by this process (reset = 1 zeroes the counter after reading it).
+ * kvx_dbg_solve_in_update: the host's decision for one trailing update -- knob = KVX_SOLVE_IN_UPDATE_TILES, cls = numbered over
+ * size classes, pair = a step of the pair schedule, the panel columns [jb, jb + klen), col_lim, tiles = the launch's tile count
+ * (upper estimate); 1 = the fused step, 0 = panel solve and update as two launches. */
+int64_t kvx_dbg_syrk_solve_count(int reset);
+int kvx_dbg_solve_in_update(int64_t knob, int cls, int pair, int klen, int col_lim, int64_t tiles);
 /* kvx_dbg_lu_counts: launches enqueued by the sparse LU path of this process, one counter per routing outcome (out may be NULL;
  * reset = 1 zeroes them); returns the number of counters, 30.  Order: k_lu_front_wp<T> at index T (T = 1, 2, 3, 4, 6, 7; 0 and 5
  * unused), k_lu_front_tiled<T> at 8 + T, then from 16: LDS-resident legacy kernel, unblocked big fronts, k_lub_panel_reg<32,1>,

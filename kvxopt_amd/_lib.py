@@ -107,6 +107,8 @@ _SIGS = {
     "kvx_dbg_tile_cover": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), i64p]),
     "kvx_dbg_syrk_counts": (ctypes.c_int, [i64p, ctypes.c_int]),
+    "kvx_dbg_syrk_solve_count": (i64, [ctypes.c_int]),
+    "kvx_dbg_solve_in_update": (ctypes.c_int, [i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64]),
     "kvx_dbg_lu_counts": (ctypes.c_int, [i64p, ctypes.c_int]),
     "kvx_dbg_chol_small_counts": (ctypes.c_int, [i64p, ctypes.c_int]),
     "kvx_dbg_chol_big_solve_counts": (ctypes.c_int, [i64p, ctypes.c_int]),

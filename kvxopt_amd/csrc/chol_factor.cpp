@@ -229,6 +229,26 @@ void trsm_step(const Level &L, int jb)
     launch_trsm_blk(L.F->stream, L.F->ds, L.list, L.nbig, L.bigm, jb, L.F->d_Lx, L.F->d_Linv);
 }
 
+// one panel over the whole trailing matrix, the panel solve inside the update (size classes of the chain list of step jb)
+void syrk_solve_step(const Level &L, int jb)
+{
+    kvx_chol *F = L.F;
+    ProfScope ps(F, FAM_SYRK);
+    const kvx_chol::ChainList &cl = F->chain_steps[(size_t)L.l][(size_t)(jb / KVX_NB)];
+    launch_syrk_solve(F->stream, F->ds, F->d_chain + cl.off, F->chain_m.data() + cl.off, F->chain_k.data() + cl.off, cl.cnt, jb,
+                      F->d_Lx, L.Uout, F->d_Linv, F->d_status);
+}
+
+// the panels jb0, jb0 + 64, ... that steps of that form left unsolved, one launch over the fronts still in the chain at step jb0
+// (largest first)
+void trsm_panels_step(const Level &L, int jb0, int npanels)
+{
+    kvx_chol *F = L.F;
+    ProfScope ps(F, FAM_TRSM);
+    const kvx_chol::ChainList &cl = F->chain_steps[(size_t)L.l][(size_t)(jb0 / KVX_NB)];
+    if (cl.cnt > 0) launch_trsm_panels(F->stream, F->ds, F->d_chain + cl.off, cl.cnt, F->chain_m[(size_t)cl.off], jb0, npanels, F->d_Lx, F->d_Linv);
+}
+
 // Outer blocks of `outer_block` (1024) columns, one rank-1024 update of the trailing matrix per block (128-tile kernel: 34 TF/s
 // on a dense trailing matrix; rocBLAS dgemm at K = 256 reaches 48-59).  Measured on MI355X against the
 // single-level path: dense n = 10240 14.8 vs 16.7 ms, 3-D 80^3 49.6 vs 51.0 ms, but 21-point 1000^2
@@ -309,12 +329,30 @@ int chain_blocked(const Level &L)
 // launches.  Where a launch is a handful of tiles (the pivot chain at the top of the tree) the pass over C is not what the
 // step waits for and the eight operand rounds of a K = 128 tile would lengthen the chain: one panel per launch there.
 // (K.pair_tiles: from this tile count on -- an upper estimate: largest front x fronts in the launch)
+// Where a launch is at most K.solve_in_update_tiles tiles (same estimate; 0 = never) the step is ONE launch: the update's
+// workgroups solve the panel rows they need themselves (syrk_solve_step).  They cannot store them -- the solved rows go where
+// the others still read the unsolved ones -- so the panels of such steps [owed, owed_end) are solved once more and stored by one
+// launch when the chain is through (or before a step of the two-launch form, should one follow): nothing in between reads them.
 void chain_pairs(const Level &L, bool cls)
 {
     const int maxk = L.P.chain_maxk;
+    int owed = 0, owed_end = 0;
+    auto settle = [&] {
+        if (owed_end > owed) trsm_panels_step(L, owed, (owed_end - owed) / KVX_NB);
+        owed = owed_end = 0;
+    };
     for (int jb = 0; jb < maxk;) {
         const int64_t T = (L.bigm - jb - 1 + KVX_TILE - 1) / KVX_TILE;
-        const bool pair = jb + KVX_NB < maxk && T * (T + 1) / 2 * L.nbig >= L.F->K.pair_tiles;
+        const int64_t tiles = T * (T + 1) / 2 * L.nbig;
+        const bool pair = jb + KVX_NB < maxk && tiles >= L.F->K.pair_tiles;
+        if (solve_in_update(L.F->K, cls, pair, KVX_NB, INT_MAX, tiles)) {
+            syrk_solve_step(L, jb);
+            if (owed_end == owed) owed = jb;
+            owed_end = jb + KVX_NB;
+            jb += KVX_NB;
+            continue;
+        }
+        settle();
         // the trailing update of panel jb also factors and inverts the diagonal block of panel jb + 64
         trsm_step(L, jb);
         if (!pair) {
@@ -327,6 +365,7 @@ void chain_pairs(const Level &L, bool cls)
         syrk_step(L, cls, jb, 2 * KVX_NB, INT_MAX);
         jb += 2 * KVX_NB;
     }
+    settle();
 }
 
 // kvx_chol_factorize_solve_dev: level l is complete -- its forward sweep goes onto the sweep's own streams right here, so
@@ -440,3 +479,11 @@ int finish_factor(kvx_chol *F, int64_t *minor)
 }
 
 }  // namespace kvx
+
+// the policy of the fused chain step on the host (tests/test_solve_in_update_cpu.py): 1 = the step solves its own panel rows
+extern "C" int kvx_dbg_solve_in_update(int64_t knob, int cls, int pair, int klen, int col_lim, int64_t tiles)
+{
+    CholKnobs K;
+    K.solve_in_update_tiles = knob;
+    return solve_in_update(K, cls != 0, pair != 0, klen, col_lim, tiles) ? 1 : 0;
+}

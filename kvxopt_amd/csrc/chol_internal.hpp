@@ -99,6 +99,7 @@ struct CholKnobs {
     // ---- the schedule of the factorisation and of the sweeps (every test that sets one of these starts a process of its own)
     int64_t asm_potrf_wgs = 1024;   // KVX_ASM_POTRF_WGS: largest extend-add launch (workgroups) that also factors the first diagonal block; 0 = never
     int64_t pair_tiles = 3000;      // KVX_PAIR_TILES: tile count of a launch from which on two panels share one pass (chain_pairs)
+    int64_t solve_in_update_tiles = 300;   // KVX_SOLVE_IN_UPDATE_TILES: largest tile count of a single-panel chain step whose update solves its own panel rows (k_syrk_solve; same estimate as pair_tiles); 0 = never
     int defer_u = 1;                // KVX_DEFER_U=0: the round-3 schedules -- no blocked chain, two-level outer blocks from two_level_m on
     bool syrk_direct = false;       // KVX_SYRK_DIRECT=1: the round-3 trailing-update kernels; process-wide, the launchers read the same syrk_direct() (device.hpp)
     double blocked_gf = 0.5;        // KVX_BLOCKED_GF: Gflop per panel step from which on a level's chain is blocked (choose_chain)
@@ -107,6 +108,13 @@ struct CholKnobs {
     bool solve_nofork = false;      // KVX_SOLVE_NOFORK (non-zero): the sweeps keep every kernel class of a level on one stream
 };
 CholKnobs read_chol_knobs();
+// The policy of the fused chain step, and nothing else: does a trailing update of `tiles` tiles (chain_pairs' upper estimate) with
+// the panel columns [jb, jb + klen), limited to the columns < col_lim, solve its own panel rows (no panel-solve launch in front)?
+// Single panels over the whole trailing matrix only, numbered over size classes (cls), never a step of the pair schedule.
+inline bool solve_in_update(const CholKnobs &K, bool cls, bool pair, int klen, int col_lim, int64_t tiles)
+{
+    return K.solve_in_update_tiles > 0 && cls && !pair && klen == KVX_NB && col_lim == 0x7fffffff && tiles <= K.solve_in_update_tiles;
+}
 // ---- per call, debugging: read where they are used, every time (KVX_SPSOLVE_DENSE is toggled on one factor by its test)
 //   chol_factor.cpp  KVX_DBG_MEMSET_NODES, KVX_DBG_GRAPH_SYNC, KVX_DBG_GRAPH_DOT          api.cpp  KVX_SPSOLVE_DENSE, KVX_FREE_TIMING
 //   chol_solve.cpp   KVX_DBG_NO_SOLVE_GRAPH, KVX_FUSED_EAGER, KVX_SUBTREES_PLAIN, KVX_PIPE_FRONTS (first fused call of a factor), KVX_DBG_T (once)

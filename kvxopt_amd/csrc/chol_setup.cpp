@@ -27,6 +27,7 @@ CholKnobs read_chol_knobs()
     if ((e = getenv("KVX_OUTER_BLOCK")) && atoi(e) >= 64) K.outer_block = atoi(e) / 64 * 64;
     if ((e = getenv("KVX_ASM_POTRF_WGS"))) K.asm_potrf_wgs = atoll(e);
     if ((e = getenv("KVX_PAIR_TILES"))) K.pair_tiles = atoll(e);
+    if ((e = getenv("KVX_SOLVE_IN_UPDATE_TILES"))) K.solve_in_update_tiles = std::max<long long>(0, atoll(e));
     if ((e = getenv("KVX_DEFER_U"))) K.defer_u = atoi(e);
     K.syrk_direct = syrk_direct();
     if ((e = getenv("KVX_BLOCKED_GF"))) K.blocked_gf = atof(e);

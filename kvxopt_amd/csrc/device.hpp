@@ -199,6 +199,9 @@ void launch_potrf_blk(hipStream_t st, const DevSym &ds, const int32_t *list, int
                       double *Lx, double *Linv, int *status);
 void launch_trsm_blk(hipStream_t st, const DevSym &ds, const int32_t *list, int count, int max_m, int jb,
                      double *Lx, const double *Linv);
+// the same for the panels jb0, jb0 + 64, ... (npanels of them) in one launch: the panel solves the fused chain steps left out
+void launch_trsm_panels(hipStream_t st, const DevSym &ds, const int32_t *list, int count, int max_m, int jb0, int npanels,
+                        double *Lx, const double *Linv);
 // C -= X X' on the trailing tiles; the workgroup of tile (0, 0) also factors + inverts the NEXT diagonal
 // block (jb + 64), so launch_potrf_blk is needed for the first panel of a front only
 // col_lim: INT_MAX = the whole trailing matrix; KVX_COLS_PIVOT = the pivot columns only (the update matrix is brought up to
@@ -210,6 +213,10 @@ void launch_syrk_trailing(hipStream_t st, const DevSym &ds, const int32_t *list,
 // step kb, sorted by the order of their update region (largest first); hm / hk = their orders and pivot counts (host arrays)
 void launch_syrk_step(hipStream_t st, const DevSym &ds, const int32_t *list, const int32_t *hm, const int32_t *hk, int count, int kb, int klen,
                       double *Lx, double *Uout, double *Linv, int *status, int col_lim);
+// one panel, whole trailing matrix, the panel solve inside the update's workgroups (no launch_trsm_blk in front; the panel itself
+// is solved by launch_trsm_panels behind the chain)
+void launch_syrk_solve(hipStream_t st, const DevSym &ds, const int32_t *list, const int32_t *hm, const int32_t *hk, int count, int kb,
+                       double *Lx, double *Uout, double *Linv, int *status);
 // deferred ("far") update with the panel block [kb, kb + klen): C -= X X' on everything from column t0 on (later pivot columns
 // and the update matrix; t0 >= k: the update matrix alone)
 void launch_syrk_far(hipStream_t st, const DevSym &ds, const int32_t *list, const int32_t *hm, const int32_t *hk, int count, int kb, int klen,
@@ -242,7 +249,9 @@ enum SyrkVariant {
     SYRK_T128_PANEL,     // k_syrk_trailing128 with one panel (KVX_SYRK_DIRECT=1, KVX_SYRK128_TILES)
     SYRK_OUTER,          // k_syrk_trailing128 as the outer update of the two-level blocking
     SYRK_FAR_SIDE,       // far updates enqueued on a stream of their own (KVX_U_STREAM)
-    SYRK_NVAR
+    SYRK_NVAR,           // (kvx_dbg_syrk_counts reports the entries up to here)
+    SYRK_SOLVE = SYRK_NVAR,   // k_syrk_solve: chain step with the panel solve inside (KVX_SOLVE_IN_UPDATE_TILES; kvx_dbg_syrk_solve_count)
+    SYRK_NALL
 };
 void syrk_count(SyrkVariant v);
 // Host-side count of the small-front launches enqueued (m <= 128, k <= 64: factorisation and sweeps), one counter per routing

@@ -6,6 +6,8 @@
 //   k_syrk_trailing: C -= X X' on 64x64 tiles, FP64 MFMA; its (0, 0) workgroup goes on to factor and
 //                   invert the NEXT diagonal block (potrf_lds), so the 64 sequential pivots of panel
 //                   jb + 64 overlap the update of panel jb;
+//   k_syrk_solve  : the two in ONE launch where a step is a few hundred tiles at most (the top of the tree): every tile
+//                   workgroup solves the panel rows it needs itself; k_trsm_panels stores the solved panels behind the chain;
 //   k_potrf_blk   : the same factor + inverse of a 64x64 diagonal block as a kernel of its own, for the
 //                   first panel of a front only.  In LDS: 16-column blocks, the 16x16 diagonal blocks by a
 //                   register column sweep of one wave (factor and inverse in the same instruction
@@ -456,6 +458,44 @@ void launch_assemble_big_potrf(hipStream_t st, const DevSym &ds, const int32_t *
 // trailing update (D[i][j]: i <-> panel column, j <-> row) so that stores run along rows.  All
 // operand loads of the 16 k-steps are branch-free; Linv is lower triangular, so k-groups above a
 // column tile are skipped.
+// The solve itself, for NS strips of 16 rows per wave against one inverse (trsm_rows: one strip, stored to the panel;
+// k_syrk_solve: the strips of a tile's rows and columns, kept in LDS): lane (lr, lk) of a wave takes the row rr[s] of strip s.
+// acc[s][t][qq] = X[rr[s]][16 t + lk + 4 qq]; the order of the products of one entry is that of the 16 k-steps, whatever NS.
+template <int NS>
+__device__ __forceinline__ void trsm_strips(const double *__restrict__ P, const double *__restrict__ Y, int m, int jb, int nbk,
+                                            const int (&rr)[NS], const bool (&rin)[NS], int lr, int lk, d4 (&acc)[NS][4])
+{
+#pragma unroll
+    for (int s = 0; s < NS; s++)
+#pragma unroll
+        for (int t = 0; t < 4; t++) acc[s][t] = (d4){0.0, 0.0, 0.0, 0.0};
+    // every operand of the 16 k-steps is requested before the first MFMA (56 loads per lane and strip, predicated, no branch in between): the
+    // kernel is one memory round trip + 40 MFMAs instead of four rounds of load -> wait -> MFMA (6 -> 4 us per launch on the pivot chain)
+    double bq[NS][4][4], aq[4][4][4];
+#pragma unroll
+    for (int g = 0; g < 4; g++)
+#pragma unroll
+        for (int qq = 0; qq < 4; qq++) {
+            const int kc = 16 * g + 4 * qq + lk;
+            const bool kin = kc < nbk;
+#pragma unroll
+            for (int s = 0; s < NS; s++) bq[s][g][qq] = kvx_ld0(P, rr[s] + (int64_t)(jb + kc) * m, kin && rin[s]);
+#pragma unroll
+            for (int t = g; t < 4; t++) {            // (Linv is lower triangular: column tiles left of the k-group hold nothing)
+                const int cc = 16 * t + lr;
+                aq[g][qq][t] = kvx_ld0(Y, cc + kc * NB, kin && cc < nbk && kc <= cc);
+            }
+        }
+#pragma unroll
+    for (int s = 0; s < NS; s++)
+#pragma unroll
+        for (int g = 0; g < 4; g++)
+#pragma unroll
+            for (int qq = 0; qq < 4; qq++)
+#pragma unroll
+                for (int t = g; t < 4; t++) acc[s][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq[g][qq][t], bq[s][g][qq], acc[s][t], 0, 0, 0);
+}
+
 __device__ __forceinline__ void trsm_rows(const FrontDesc &fd, int jb, int rb, double *__restrict__ Lx, const double *__restrict__ Linv,
                                           const int lt)                  // lt: thread 0..255 of the four waves doing this row block
 {
@@ -466,40 +506,17 @@ __device__ __forceinline__ void trsm_rows(const FrontDesc &fd, int jb, int rb, d
     double *P = Lx + fd.px;
     const double *Y = Linv + fd.linv + (int64_t)(jb / NB) * NB * NB;
     const int w = lt >> 6, l = lt & 63, lr = l & 15, lk = l >> 4;
-    const int rr = r0 + 16 * w + lr;
-    const bool rin = rr < m;
-    d4 acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) acc[t] = (d4){0.0, 0.0, 0.0, 0.0};
-    // every operand of the 16 k-steps is requested before the first MFMA (56 loads per lane, predicated, no branch in between): the
-    // kernel is one memory round trip + 40 MFMAs instead of four rounds of load -> wait -> MFMA (6 -> 4 us per launch on the pivot chain)
-    double bq[4][4], aq[4][4][4];
-#pragma unroll
-    for (int g = 0; g < 4; g++)
-#pragma unroll
-        for (int qq = 0; qq < 4; qq++) {
-            const int kc = 16 * g + 4 * qq + lk;
-            const bool kin = kc < nbk;
-            bq[g][qq] = kvx_ld0(P, rr + (int64_t)(jb + kc) * m, kin && rin);
-#pragma unroll
-            for (int t = g; t < 4; t++) {            // (Linv is lower triangular: column tiles left of the k-group hold nothing)
-                const int cc = 16 * t + lr;
-                aq[g][qq][t] = kvx_ld0(Y, cc + kc * NB, kin && cc < nbk && kc <= cc);
-            }
-        }
-#pragma unroll
-    for (int g = 0; g < 4; g++)
-#pragma unroll
-        for (int qq = 0; qq < 4; qq++)
-#pragma unroll
-            for (int t = g; t < 4; t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq[g][qq][t], bq[g][qq], acc[t], 0, 0, 0);
-    if (rin) {
+    const int rr[1] = {r0 + 16 * w + lr};
+    const bool rin[1] = {rr[0] < m};
+    d4 acc[1][4];
+    trsm_strips<1>(P, Y, m, jb, nbk, rr, rin, lr, lk, acc);
+    if (rin[0]) {
 #pragma unroll
         for (int t = 0; t < 4; t++)
 #pragma unroll
             for (int qq = 0; qq < 4; qq++) {
                 const int c = 16 * t + lk + 4 * qq;
-                if (c < nbk) P[rr + (int64_t)(jb + c) * m] = acc[t][qq];
+                if (c < nbk) P[rr[0] + (int64_t)(jb + c) * m] = acc[0][t][qq];
             }
     }
 }
@@ -520,6 +537,33 @@ void launch_trsm_blk(hipStream_t st, const DevSym &ds, const int32_t *list, int 
     if (rows <= 0) return;
     dim3 grid((unsigned)((rows + 63) / 64), (unsigned)count);
     hipLaunchKernelGGL(k_trsm_blk, grid, dim3(256), 0, st, ds, list, jb, Lx, Linv);
+}
+
+// The panel solves that the chain steps of the fused form (k_syrk_solve) left out: the panels jb0, jb0 + 64, ... of the level's
+// fronts in ONE launch behind the level's chain.  A fused step cannot store X itself: X goes where the unsolved panel
+// is, and the other tile workgroups of that launch read the unsolved rows.  Nothing on the chain reads a solved panel again
+// (the updates of the later panels touch later columns only), so the stores wait until the chain is through.
+// blockIdx.x numbers the (panel, row block) pairs of the largest front: nb0 row blocks below panel jb0, one fewer per panel.
+__global__ __launch_bounds__(256) void k_trsm_panels(DevSym ds, const int32_t *__restrict__ list, int jb0, int nb0,
+                                                     double *__restrict__ Lx, const double *__restrict__ Linv)
+{
+    int rb = (int)blockIdx.x, z = 0;
+    for (int nb = nb0; nb > 0 && rb >= nb; nb--) { rb -= nb; z++; }          // (uniform)
+    const FrontDesc fd = ds.fd[list[blockIdx.y]];
+    const int jb = jb0 + NB * z;
+    if (jb >= fd.k) return;
+    trsm_rows(fd, jb, rb, Lx, Linv, (int)threadIdx.x);
+}
+
+void launch_trsm_panels(hipStream_t st, const DevSym &ds, const int32_t *list, int count, int max_m, int jb0, int npanels,
+                        double *Lx, const double *Linv)
+{
+    if (count <= 0 || npanels <= 0) return;
+    const int rows = max_m - jb0 - 1;                              // (launch_trsm_blk's estimate for panel jb0; 64 rows fewer per panel)
+    if (rows <= 0) return;
+    const int nb0 = (rows + 63) / 64, np = std::min(npanels, nb0);
+    const unsigned blocks = (unsigned)(np * nb0 - np * (np - 1) / 2);
+    hipLaunchKernelGGL(k_trsm_panels, dim3(blocks, (unsigned)count), dim3(256), 0, st, ds, list, jb0, nb0, Lx, Linv);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -652,6 +696,135 @@ __global__ __launch_bounds__(256) void k_syrk_trailing(DevSym ds, const int32_t 
         for (int g = 0; g < 4; g++) KVX_PHASE_ADD(10 + g, qr[g], qr[g + 1]);
 #endif
         KVX_PHASE_ADD(1, q0, q1); KVX_PHASE_ADD(2, q1, q2); KVX_PHASE_ADD(3, q2, q3); KVX_PHASE_ADD(4, q3, q4); KVX_PHASE_ADD(5, q4, q5);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// The chain form of k_syrk_trailing<64> with no panel solve in front of it (launches of few tiles at the top of the tree, where a
+// step is two nearly empty dependent launches): the workgroup of tile (ti, tj) solves the two 64-row strips it needs, X_ti and
+// X_tj (one if ti == tj), from the unsolved panel columns [jb, jb + nbk) and the inverse of panel jb's diagonal block
+// (trsm_strips: the products of k_trsm_blk in its order), keeps them in LDS and takes the operands of the tile update from
+// there, k-groups of 16, q, t as k_syrk_trailing<64> has them: the bits of C are those of the two-launch step.  The strips are
+// NOT stored to the panel here (the other workgroups read those rows unsolved): launch_trsm_panels does that behind the chain.
+// LDS: 2 x 64 x 64 doubles, X[row][c] of a strip at c * 64 + ((row + 16 c) mod 64) -- the four k of a lane group (c mod 4 = lk)
+// land in four different quarters of the banks; the image of the next diagonal block (PotrfLds) takes the storage over once
+// the tile is in registers, as in SyrkLdsU.  Launched over size classes only, whole trailing matrix only (col_lim = INT_MAX).
+struct SyrkSolveLds {
+    double x[2][NB * KVX_TILE];         // [0]: the strip of the tile's rows, [1]: of its columns
+};
+union SyrkSolveLdsU {
+    SyrkSolveLds xs;
+    PotrfLds po;
+};
+__device__ __forceinline__ int xs_idx(int row, int c) { return c * KVX_TILE + ((row + 16 * c) & (KVX_TILE - 1)); }
+
+__global__ __launch_bounds__(256) void k_syrk_solve(DevSym ds, const int32_t *__restrict__ list, int jb,
+                                                    double *__restrict__ Lx, double *__restrict__ Uo,
+                                                    double *__restrict__ Linv, int *status, const TileClasses tc)
+{
+    __shared__ SyrkSolveLdsU lds;
+    int ti, tj, fi;
+    if (!cls_decode(tc, blockIdx.x, fi, ti, tj)) return;
+    const FrontDesc fd = ds.fd[list[fi]];
+    const int k = fd.k, m = fd.m, u = m - k;
+    SyrkTile g;
+    if (!syrk_tile_guard(false, m, k, jb, NB, INT_MAX, ti, tj, g)) return;
+    const int nbk = g.nbk, t0 = g.t0, r0 = g.r0, c0 = g.c0, cend = g.cend;
+    double *P = Lx + fd.px;
+    double *U = Uo + fd.ux;
+    const double *Y = Linv + fd.linv + (int64_t)(jb / NB) * NB * NB;
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, lr = l & 15, lk = l >> 4;
+    const int rr = r0 + 16 * w + lr;
+    const bool rin = rr < m;
+    const int i = 16 * w + lr;                         // the lane's row inside a strip
+    // ---- the strips (rows past m and columns past nbk as zeros: what the predicated loads of the two-launch update give)
+    if (ti == tj) {                                    // workgroup-uniform
+        const int r1[1] = {rr};
+        const bool in1[1] = {rin};
+        d4 x[1][4];
+        trsm_strips<1>(P, Y, m, jb, nbk, r1, in1, lr, lk, x);
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+            for (int qq = 0; qq < 4; qq++) {
+                const int c = 16 * t + lk + 4 * qq;
+                lds.xs.x[0][xs_idx(i, c)] = (rin && c < nbk) ? x[0][t][qq] : 0.0;
+            }
+    } else {
+        const int cr = c0 + 16 * w + lr;
+        const int r2[2] = {rr, cr};
+        const bool in2[2] = {rin, cr < m};
+        d4 x[2][4];
+        trsm_strips<2>(P, Y, m, jb, nbk, r2, in2, lr, lk, x);
+#pragma unroll
+        for (int s = 0; s < 2; s++)
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+#pragma unroll
+                for (int qq = 0; qq < 4; qq++) {
+                    const int c = 16 * t + lk + 4 * qq;
+                    lds.xs.x[s][xs_idx(i, c)] = (in2[s] && c < nbk) ? x[s][t][qq] : 0.0;
+                }
+    }
+    __syncthreads();
+    // ---- the tile update, operands from the strips
+    const double *xb = lds.xs.x[0];
+    const double *xa = lds.xs.x[ti == tj ? 0 : 1];
+    d4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) acc[t] = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int kg = 0; kg < NB; kg += 16) {
+        if (kg < nbk) {                             // wave-uniform
+            double bq[4], aq[4][4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int kc = kg + 4 * q + lk;
+                bq[q] = xb[xs_idx(i, kc)];
+#pragma unroll
+                for (int t = 0; t < 4; t++) aq[q][t] = xa[xs_idx(16 * t + lr, kc)];
+            }
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+#pragma unroll
+                for (int t = 0; t < 4; t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq[q][t], bq[q], acc[t], 0, 0, 0);
+        }
+    }
+    // ---- read-modify-write of the tile and the next diagonal block, as in k_syrk_trailing
+    const int rs = min(rr, m - 1);
+    double *ptr[4][4];
+    double old[4][4];
+    bool ok[4][4];
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int c = c0 + 16 * t + lk + 4 * q;
+            ok[t][q] = rin && c <= rr && c < cend;
+            const int cs = min(c, rs);
+            ptr[t][q] = (cs < k) ? P + rs + (int64_t)cs * m : U + (rs - k) + (int64_t)(cs - k) * u;
+            old[t][q] = *ptr[t][q];
+        }
+    const bool fused = ti == 0 && tj == 0 && t0 < cend && t0 < k;   // workgroup-uniform
+    const int dend = fused ? t0 + min(NB, k - t0) : 0;              // rows below dend (a partial last block) are written as always
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            if (ok[t][q] && rr >= dend) *ptr[t][q] = old[t][q] - acc[t][q];
+    if (fused) {
+        __syncthreads();                               // every wave has its operands: the strips become the image of the diagonal block
+        const int nb2 = min(NB, k - t0);
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int cc = 16 * t + lk + 4 * q;
+                if (t <= w) lds.po.S[s_idx(i, cc)] = (i < nb2 && cc <= i) ? old[t][q] - acc[t][q] : (cc == i ? 1.0 : 0.0);
+            }
+        __syncthreads();
+        potrf_lds(lds.po, nb2, threadIdx.x, status, fd.first + t0, make_piv_rule(ds));
+        potrf_store(lds.po, nb2, threadIdx.x, P, m, t0, Linv + fd.linv + (int64_t)(t0 / NB) * NB * NB);
     }
 }
 
@@ -877,7 +1050,19 @@ void launch_syrk_step(hipStream_t st, const DevSym &ds, const int32_t *list, con
     }
     launch_syrk_lds_cls(st, false, ds, list, tc, kb, klen, Lx, Uout, Linv, status, col_lim);
 }
-static std::atomic<unsigned long long> g_syrk_counts[SYRK_NVAR];
+// a chain step of one panel over the whole trailing matrix with the panel solve inside the update (k_syrk_solve); the caller
+// leaves out the step's launch_trsm_blk and owes the panel a launch_trsm_panels behind the chain
+void launch_syrk_solve(hipStream_t st, const DevSym &ds, const int32_t *list, const int32_t *hm, const int32_t *hk, int count, int kb,
+                       double *Lx, double *Uout, double *Linv, int *status)
+{
+    if (count <= 0) return;
+    const TileClasses tc = make_tile_classes(false, hm, hk, count, kb, NB, INT_MAX);
+    const unsigned gx = tc.ncls > 0 ? tc.wg[tc.ncls] : 0u;
+    if (gx == 0) return;
+    syrk_count(SYRK_SOLVE);
+    hipLaunchKernelGGL(k_syrk_solve, dim3(gx), dim3(256), 0, st, ds, list, kb, Lx, Uout, Linv, status, tc);
+}
+static std::atomic<unsigned long long> g_syrk_counts[SYRK_NALL];
 void syrk_count(SyrkVariant v) { g_syrk_counts[v].fetch_add(1, std::memory_order_relaxed); }
 
 }  // namespace kvx
@@ -889,6 +1074,12 @@ extern "C" int kvx_dbg_syrk_counts(int64_t *out, int reset)
         if (out) out[v] = (int64_t)c;
     }
     return kvx::SYRK_NVAR;
+}
+
+// the launches of the fused chain step (SYRK_SOLVE): a reader of its own, kvx_dbg_syrk_counts keeps its ten entries
+extern "C" int64_t kvx_dbg_syrk_solve_count(int reset)
+{
+    return (int64_t)(reset ? kvx::g_syrk_counts[kvx::SYRK_SOLVE].exchange(0) : kvx::g_syrk_counts[kvx::SYRK_SOLVE].load());
 }
 
 extern "C" int kvx_dbg_tile_cover(int uonly, const int32_t *hm, const int32_t *hk, int count, int kb, int klen, int col_lim, int tmax,
