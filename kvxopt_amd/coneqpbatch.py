@@ -39,36 +39,19 @@ first iteration, 3 the factorisation with W = I or the first one failed (solvers
 Rank([P; A; G]) < n")): that member has zeros in x, y, s, z, 0 iterations and nan statistics, and does not disturb the others.  's'
 and 'z' are N x B with every 's' block a full symmetric matrix, as cone.coneqp returns them; 'primal slack' and 'dual slack' are the
 reference's -max_step over the whole cone."""
-import numpy as np
+from . import _batch
+from ._batch import EXIT_OPTIMAL, MAX_M, MAX_N, MAX_NQ, MAX_NS  # noqa: F401
+from ._batch import MAX_CONE_ROWS as MAX_ROWS
+from ._batch import QP_STATS as _STATS
 
-from . import _ipm, _lib
-from .conelpbatch import MAX_M, MAX_NQ, MAX_NS, MAX_ROWS
-from .qpbatch import _STATS, EXIT_OPTIMAL, MAX_N, _columns, _matrix, _shared_or_batch
-
-
-def _limit(name, value, lo, hi):
-    if not lo <= value <= hi:
-        raise ValueError("coneqp_batch: %s = %d is outside its limit %d <= %s <= %s; solvers.coneqp solves one problem of any size"
-                         % (name, value, lo, name, "n" if name == "p" else "%d" % hi))
+_limit = _batch.limiter("coneqp_batch", "coneqp")
 
 
 def _prepare(P, q, G, h, dims, A, b, options):
     """Every argument check, on the host; returns what kvx_coneqp_batch_solve takes."""
-    user = dict(options or {})
-    if user.get("refinement") is None:
-        user["refinement"] = 0
-    if not isinstance(dims, dict):
-        raise TypeError("'dims' must be a dictionary with the keys 'l', 'q' and 's'")
-    dims = _ipm.check_dims(dims)
-    opt = _ipm.options(user, dims, qp=True)
-    if opt.refinement != 0:
-        raise NotImplementedError("coneqp_batch: options['refinement'] = %d is not carried, only 0 (the default here); "
-                                  "solvers.coneqp refines, once by default" % opt.refinement)
+    opt, dims = _batch.options("coneqp_batch", "coneqp", options, dims, "'l', 'q' and 's'", qp=True)
     ml, qd, sd = int(dims["l"]), [int(k) for k in dims["q"]], [int(k) for k in dims["s"]]
-    q = _columns(q, "q", "one column per member")
-    n, B = q.shape
-    if B < 1:
-        raise TypeError("'q' must have at least one column")
+    q, n, B = _batch.members(q, "q")
     _limit("n", n, 1, MAX_N)
     _limit("nq", len(qd), 0, MAX_NQ)
     _limit("ns", len(sd), 0, MAX_NS)
@@ -76,43 +59,16 @@ def _prepare(P, q, G, h, dims, A, b, options):
         _limit("m_k", m, 1, MAX_M)
     N = ml + sum(qd) + sum(m * m for m in sd)
     _limit("N", N, 1, MAX_ROWS)
-    Pv, sP, _ = _matrix(P, "P", n, B, rows=n)
-    Gv, sG, rows = _matrix(G, "G", n, B)
+    Pv, sP, _ = _batch.matrix(P, "P", n, B, rows=n)
+    Gv, sG, rows = _batch.matrix(G, "G", n, B)
     if rows != N:
         raise TypeError("'G' must be a 'd' matrix of size (%d, %d)" % (N, n))
-    hv, sh = _shared_or_batch(h, "h", N, B, "'h' must be a 'd' matrix of size (%d,1)" % N)
-    if A is None:
-        p, Av, sA = 0, None, 0
-        if b is not None and _columns(b, "b", "0 rows").shape[0] != 0:
-            raise TypeError("'b' must have length 0")
-        bv, sb = None, 0
-    else:
-        Av, sA, p = _matrix(A, "A", n, B)
-        _limit("p", p, 0, n)
-        if p == 0:
-            Av, bv, sA, sb = None, None, 0, 0
-        else:
-            if b is None:
-                raise TypeError("'b' must have length %d" % p)
-            bv, sb = _shared_or_batch(b, "b", p, B, "'b' must have length %d" % p)
-    qv = np.ascontiguousarray(q.T).reshape(-1)
-    return opt, (B, n, ml, qd, sd, N, p), ((Pv, sP), (qv, n if B > 1 else 0), (Gv, sG), (hv, sh), (Av, sA), (bv, sb))
+    hv, sh = _batch.shared_or_batch(h, "h", N, B, "'h' must be a 'd' matrix of size (%d,1)" % N)
+    p, eqA, eqb = _batch.equalities(A, b, n, B, "q", _limit)
+    return opt, (B, n, ml, qd, sd, N, p), ((Pv, sP), _batch.flat(q, B), (Gv, sG), (hv, sh), eqA, eqb)
 
 
 def coneqp_batch(P, q, G, h, dims, A=None, b=None, options=None):
     opt, (B, n, ml, qd, sd, N, p), data = _prepare(P, q, G, h, dims, A, b, options)
-    L = _lib.lib()
-    x, y, sv, z = (np.zeros((rows, B), order="F") for rows in (n, p, N, N))
-    stats = np.zeros((len(_STATS), B), order="F")
-    iters, code = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
-    qv, mv = np.asarray(qd, dtype=np.int64), np.asarray(sd, dtype=np.int64)
-    args = [B, n, ml, len(qd), _lib.pi(qv) if qd else None, len(sd), _lib.pi(mv) if sd else None, p]
-    for v, stride in data:
-        args += [None if v is None else _lib.pd(v), stride]
-    args += [int(opt.maxiters), float(opt.abstol), float(opt.reltol), float(opt.feastol), int(opt.correction)]
-    args += [_lib.pd(x), _lib.pd(y) if p else None, _lib.pd(sv), _lib.pd(z), _lib.pd(stats), _lib.pi(iters), _lib.pi(code)]
-    _lib.raise_for(L.kvx_coneqp_batch_solve(*args), "kvx_coneqp_batch_solve")
-    sol = {"status": ["optimal" if c == EXIT_OPTIMAL else "unknown" for c in code], "x": x, "y": y, "s": sv, "z": z}
-    sol.update((k, stats[i].copy()) for i, k in enumerate(_STATS))
-    sol.update({"iterations": iters, "exit": code})
-    return sol
+    return _batch.solve("kvx_coneqp_batch_solve", [B, n, ml] + _batch.orders(qd) + _batch.orders(sd) + [p], data, opt, B, n, p, N, _STATS, _batch.QP_STATUS,
+                        correction=True)

@@ -53,10 +53,10 @@ CPU fallback.  Not carried: derivatives of conelp_batch (its certificates), gp_b
 the centred point as a result, several cotangents per call, a torch binding."""
 import numpy as np
 
-from . import _lib, coneqpbatch, qpbatch
-from .qpbatchdiff import MAX_REFINEMENT, WRT, _column_gradient, _from_members
+from . import _batch, _batchdiff, coneqpbatch
+from ._batchdiff import EXIT_DONE, EXIT_FAILED, EXIT_SKIPPED, MAX_REFINEMENT, WRT  # noqa: F401
 
-EXIT_DONE, EXIT_SKIPPED, EXIT_FAILED, EXIT_NOT_CENTRED = range(4)
+EXIT_NOT_CENTRED = 3
 MAX_CENTERING = 16
 DEFAULT_CENTERING, DEFAULT_CENTOL = 8, 1e-6               # DESIGN 21 has the table they are chosen from
 
@@ -67,50 +67,27 @@ def _options(who, options):
     if o:
         raise ValueError("%s: options accepts only 'refinement', 'centering' and 'centol', not %s"
                          % (who, ", ".join(repr(k) for k in sorted(o, key=str))))
-    for name, v, hi in (("refinement", ref, MAX_REFINEMENT), ("centering", cen, MAX_CENTERING)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
-            raise ValueError("options['%s'] must be a nonnegative integer" % name)
-        if v > hi:
-            raise ValueError("%s: options['%s'] = %d is outside its limit 0 <= %s <= %d" % (who, name, v, name, hi))
+    ref, cen = _batchdiff.count(who, "refinement", ref, MAX_REFINEMENT), _batchdiff.count(who, "centering", cen, MAX_CENTERING)
     if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not tol > 0:
         raise ValueError("options['centol'] must be a positive scalar")
-    return int(ref), int(cen), float(tol)
+    return ref, cen, float(tol)
 
 
 def _problem(who, P, q, G, h, dims, A, b):
     """coneqp_batch's own checks of the problem arguments, under the entry's name."""
-    try:
-        _, sizes, data = coneqpbatch._prepare(P, q, G, h, dims, A, b, None)
-    except ValueError as e:
-        raise ValueError(str(e).replace("coneqp_batch:", who + ":", 1)) from None
-    return sizes, data
-
-
-def _solution(sol, B, n, N, p):
-    """x, y, s, z and exit of `sol` as contiguous arrays of their own, one member after the other."""
-    if not isinstance(sol, dict) or any(k not in sol for k in ("x", "y", "s", "z", "exit")):
-        raise TypeError("'sol' must be the dictionary coneqp_batch returned, with 'x', 'y', 's', 'z' and 'exit'")
-    out = []
-    for k, rows in (("x", n), ("y", p), ("s", N), ("z", N)):
-        v = np.asarray(sol[k], dtype=np.float64)
-        if v.shape != (rows, B):
-            raise TypeError("sol['%s'] must be a 'd' matrix of size (%d, %d)" % (k, rows, B))
-        out.append(np.array(v.T, order="C").reshape(-1))
-    code = np.asarray(sol["exit"])
-    if code.shape != (B,) or code.dtype.kind not in "iu":
-        raise TypeError("sol['exit'] must be an integer array of length %d" % B)
-    return out, np.array(code, dtype=np.int64)
+    return _batchdiff.problem(who, "coneqp_batch", coneqpbatch._prepare, P, q, G, h, dims, A, b)
 
 
 def _common(sizes, data, vecs, code, opts):
     """The leading arguments of all four C entries: sizes, the cone, the data with strides, the solution, the options."""
     B, n, ml, qd, sd, N, p = sizes
-    qv, mv = np.asarray(qd, dtype=np.int64), np.asarray(sd, dtype=np.int64)
-    args = [B, n, ml, len(qd), _lib.pi(qv) if qd else None, len(sd), _lib.pi(mv) if sd else None, p]
-    for v, stride in data:
-        args += [None if v is None else _lib.pd(v), stride]
-    x, y, s, z = vecs
-    return args + [_lib.pd(x), _lib.pd(y) if p else None, _lib.pd(s), _lib.pd(z), _lib.pi(code)] + list(opts), (qv, mv)
+    head = [B, n, ml] + _batch.orders(qd) + _batch.orders(sd) + [p]
+    return head + _batch.pointers(data) + _batchdiff.solution_pointers(vecs, code, p) + list(opts)
+
+
+def _extra(B):
+    """The results the cone entries have beyond the orthant's, in the order of the C entries."""
+    return {"centrality": np.zeros(B), "centering steps": np.zeros(B, dtype=np.int64)}
 
 
 def coneqp_batch_vjp(P, q, G, h, dims, A=None, b=None, *, sol, gx, wrt=WRT, options=None):
@@ -118,49 +95,9 @@ def coneqp_batch_vjp(P, q, G, h, dims, A=None, b=None, *, sol, gx, wrt=WRT, opti
     opts = _options(who, options)
     sizes, data = _problem(who, P, q, G, h, dims, A, b)
     B, n, ml, qd, sd, N, p = sizes
-    vecs, code = _solution(sol, B, n, N, p)
-    g = qpbatch._columns(gx, "gx", "one column per member")
-    if g.shape != (n, B):
-        raise TypeError("'gx' must be a 'd' matrix of size (%d, %d)" % (n, B))
-    wrt = (wrt,) if isinstance(wrt, str) else tuple(wrt)
-    if any(k not in WRT for k in wrt):
-        raise ValueError("%s: wrt names %s; it takes 'P', 'q', 'G', 'h', 'A', 'b'" % (who, ", ".join(repr(k) for k in wrt if k not in WRT)))
-    gv = np.ascontiguousarray(g.T).reshape(-1)
-    sP, sG, sA = data[0][1], data[2][1], data[4][1]
-    L = _lib.lib()
-    ux, uy, uz = (np.zeros((rows, B), order="F") for rows in (n, p, N))
-    gexit, steps, cen = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64), np.zeros(B)
-    mats = {}
-    for k, rows, stride in (("P", n, sP), ("G", N, sG), ("A", p, sA)):
-        mats[k] = np.zeros((B if stride else 1) * rows * n) if k in wrt and rows else None
-    args, keep = _common(sizes, data, vecs, code, opts)
-    args += [_lib.pd(gv), _lib.pd(ux), _lib.pd(uy) if p else None, _lib.pd(uz)]
-    args += [None if mats[k] is None else _lib.pd(mats[k]) for k in ("P", "G", "A")] + [_lib.pd(cen), _lib.pi(steps), _lib.pi(gexit)]
-    _lib.raise_for(L.kvx_coneqp_batch_vjp(*args), "kvx_coneqp_batch_vjp")
-    del keep
-    out = {"ux": ux, "uy": uy, "uz": uz, "exit": gexit, "centrality": cen, "centering steps": steps}
-    done = gexit == EXIT_DONE
-    for k in wrt:
-        if k == "q":
-            out[k] = ux.copy()
-        elif k == "h":
-            out[k] = _column_gradient(0.0 - uz, h, data[3][1] == 0, done)            # 0 - u: no negative zeros
-        elif k == "b":
-            out[k] = _column_gradient(0.0 - uy, b, data[5][1] == 0, done) if p else None
-        else:
-            rows, stride = {"P": (n, sP), "G": (N, sG), "A": (p, sA)}[k]
-            out[k] = None if mats[k] is None else _from_members(mats[k], stride == 0, rows, n, B)
-    return out
-
-
-def _perturbation(name, v, like, n, B, rows):
-    """(values or None, member stride) of one perturbation, checked as coneqp_batch checks the datum it perturbs."""
-    if v is None:
-        return None, 0
-    if like in ("P", "G", "A"):
-        vals, stride, _ = qpbatch._matrix(v, name, n, B, rows=rows)
-        return vals, stride
-    return qpbatch._shared_or_batch(v, name, rows, B, "'%s' must be a 'd' matrix of size (%d,1)" % (name, rows))
+    vecs, code = _batchdiff.solution(sol, "coneqp_batch", B, n, N, p, copy=True)
+    return _batchdiff.vjp("kvx_coneqp_batch_vjp", who, lambda: _common(sizes, data, vecs, code, opts),
+                          _batchdiff.strides(data), B, n, N, p, gx, wrt, h, b, _extra(B))
 
 
 def coneqp_batch_jvp(P, q, G, h, dims, A=None, b=None, *, sol, dP=None, dq=None, dG=None, dh=None, dA=None, db=None, options=None):
@@ -168,16 +105,6 @@ def coneqp_batch_jvp(P, q, G, h, dims, A=None, b=None, *, sol, dP=None, dq=None,
     opts = _options(who, options)
     sizes, data = _problem(who, P, q, G, h, dims, A, b)
     B, n, ml, qd, sd, N, p = sizes
-    vecs, code = _solution(sol, B, n, N, p)
-    pert = [_perturbation("d" + k, v, k, n, B, rows)
-            for k, v, rows in (("P", dP, n), ("q", dq, n), ("G", dG, N), ("h", dh, N), ("A", dA, p), ("b", db, p))]
-    L = _lib.lib()
-    dx, dy, dz, ds = (np.zeros((rows, B), order="F") for rows in (n, p, N, N))
-    gexit, steps, cen = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64), np.zeros(B)
-    args, keep = _common(sizes, data, vecs, code, opts)
-    for k, (vals, stride) in zip(WRT, pert):
-        args += [None if vals is None or (k in "Ab" and not p) else _lib.pd(vals), stride]
-    args += [_lib.pd(dx), _lib.pd(dy) if p else None, _lib.pd(dz), _lib.pd(ds), _lib.pd(cen), _lib.pi(steps), _lib.pi(gexit)]
-    _lib.raise_for(L.kvx_coneqp_batch_jvp(*args), "kvx_coneqp_batch_jvp")
-    del keep
-    return {"x": dx, "y": dy, "z": dz, "s": ds, "exit": gexit, "centrality": cen, "centering steps": steps}
+    vecs, code = _batchdiff.solution(sol, "coneqp_batch", B, n, N, p, copy=True)
+    pert = _batchdiff.perturbations((dP, dq, dG, dh, dA, db), B, n, N, p)
+    return _batchdiff.jvp("kvx_coneqp_batch_jvp", lambda: _common(sizes, data, vecs, code, opts), pert, B, n, N, p, _extra(B))

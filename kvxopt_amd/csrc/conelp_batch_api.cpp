@@ -2,7 +2,7 @@
 // placement of its cone, and its launch through the host entry that the batch solvers share (batch_host.hpp).  The cone orders
 // and the block orders are host arrays for both entries: they travel to the kernel with its arguments.  The kernel stages the
 // scaled rows of G in LDS, so there is no workspace.
-#include "batch_host.hpp"
+#include "batch_cone_host.hpp"
 #include "conelp_batch.hpp"
 
 using namespace kvx;
@@ -10,45 +10,12 @@ using namespace kvx::batchhost;
 
 namespace {
 
-// the cone into the kernel's arguments; the orders are in range (check)
-void place(ConelpBatchArgs &a, int64_t nq, const int64_t *q, int64_t ns, const int64_t *m)
-{
-    a.nq = (int)nq;
-    a.ns = (int)ns;
-    a.Ms = a.ml;
-    for (int64_t k = 0; k < CONEB_MAX_NQ; k++) a.q[k] = k < nq ? (unsigned short)q[k] : 0;
-    for (int64_t k = 0; k < CONEB_MAX_NS; k++) a.m[k] = k < ns ? (unsigned char)m[k] : 0;
-    for (int64_t k = 0; k < nq; k++) a.Ms += (int)q[k];
-    a.N = a.Nd = a.Np = a.Ms;
-    for (int64_t k = 0; k < ns; k++) {
-        a.N += (int)(m[k] * m[k]);
-        a.Nd += (int)m[k];
-        a.Np += (int)((m[k] * (m[k] + 1)) / 2);
-    }
-}
-
 // What both entries check before a device is asked for; on success the cone is placed in `a`
 int check(const char *who, ConelpBatchArgs &a, int64_t nq, const int64_t *q, int64_t ns, const int64_t *m)
 {
-    if (a.B < 1 || a.B > 2147483647) return refuse(who, "1 <= B <= 2147483647 is required");
-    if (a.n < 1 || a.n > CONEB_MAX_N) return refuse(who, "1 <= n <= 64 is required");
-    if (a.ml < 0 || a.ml > CONEB_MAX_ROWS) return refuse(who, "0 <= ml <= 384 is required");
-    if (nq < 0 || nq > CONEB_MAX_NQ) return refuse(who, "0 <= nq <= 128 is required");
-    if (nq > 0 && !q) return refuse(who, "the cone orders q are NULL");
-    if (ns < 0 || ns > CONEB_MAX_NS) return refuse(who, "0 <= ns <= 32 is required");
-    if (ns > 0 && !m) return refuse(who, "the block orders m are NULL");
-    int64_t N = a.ml;
-    for (int64_t k = 0; k < nq; k++) {
-        if (q[k] < 1 || q[k] > CONEB_MAX_ROWS) return refuse(who, "every cone order is at least 1 and at most 384");
-        N += q[k];
-    }
-    for (int64_t k = 0; k < ns; k++) {
-        if (m[k] < 1 || m[k] > CONEB_MAX_M) return refuse(who, "every block order is at least 1 and at most 16");
-        N += m[k] * m[k];
-    }
-    if (N < 1 || N > CONEB_MAX_ROWS) return refuse(who, "1 <= N = ml + sum(q) + sum(m^2) <= 384 is required");
-    if (a.p < 0 || a.p > a.n) return refuse(who, "0 <= p <= n is required");
-    place(a, nq, q, ns, m);
+    int64_t N = 0;
+    if (const char *why = cone_limits(a.B, a.n, a.ml, nq, q, ns, m, a.p, &N)) return refuse(who, why);
+    place_cone(a, nq, q, ns, m);
     if (a.p + a.Np < a.n) return refuse(who, "p + ml + sum(q) + sum(m (m + 1) / 2) >= n is required");
     if (conelp_batch_lds_bytes(a.n, a.ml, a.nq, a.q, a.ns, a.m, a.p) > 160 * 1024)
         return refuse(who, "the member needs more than 160 KiB of LDS");

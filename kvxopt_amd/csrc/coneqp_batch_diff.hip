@@ -20,6 +20,7 @@
 // test, or makes the comparison with centol false until the cap: exit 3.
 #include "coneqp_batch_diff.hpp"
 #include "batch_coneqp.hpp"
+#include "batch_diff_device.hpp"
 
 #include <cmath>
 
@@ -46,14 +47,6 @@ __host__ __device__ inline DiffLayout diff_layout(int n, int ml, int Ms, int N, 
     L.by = o; o += even(p);
     L.total = o;
     return L;
-}
-
-// row i of the symmetric matrix whose lower triangle is in HBM, times the LDS vector v
-__device__ __forceinline__ double sym_row_dot(const double *__restrict__ Q, int n, int i, const double *v)
-{
-    double t = 0.0;
-    for (int j = 0; j < n; j++) t += (j <= i ? Q[i + j * n] : Q[j + i * n]) * v[j];
-    return t;
 }
 
 // v[c] += sign * sum over the packed rows j of D(row_j, c) weight_j u[row_j] for a matrix D (N x n in HBM) that is not the

@@ -20,6 +20,7 @@
 // k_batch_outer_sum: the gradient of a matrix all members share, the sum over the members of their outer products, eight
 // threads per entry in an order fixed at compile time.
 #include "qp_batch_diff.hpp"
+#include "batch_diff_device.hpp"
 #include "batch_kkt.hpp"
 
 #include <cmath>
@@ -65,14 +66,6 @@ __device__ __forceinline__ void kkt_solve(const Member &M, double *vx, double *v
     orth_kkt_after(M.G, M.ml, M.n, M.di, vx, vz);
     for (int k = threadIdx.x; k < M.ml; k += NT) vz[k] *= M.di[k];       // each thread scales the entries it wrote itself
     __syncthreads();
-}
-
-// row i of the symmetric matrix whose lower triangle is in HBM, times the LDS vector v
-__device__ __forceinline__ double sym_row_dot(const double *__restrict__ Q, int n, int i, const double *v)
-{
-    double t = 0.0;
-    for (int j = 0; j < n; j++) t += (j <= i ? Q[i + j * n] : Q[j + i * n]) * v[j];
-    return t;
 }
 
 __global__ void __launch_bounds__(QPB_THREADS) k_qp_batch_diff(QpDiffArgs a)

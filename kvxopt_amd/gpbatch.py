@@ -33,17 +33,15 @@ accepted iterate is returned.  A member does not disturb the others: its bytes d
 members."""
 import numpy as np
 
-from . import _ipm, _lib, base
-from .qpbatch import _STATS, EXIT_OPTIMAL, _columns, _matrix, _shared_or_batch
+from . import _batch, base
+from ._batch import EXIT_OPTIMAL  # noqa: F401
+from ._batch import QP_STATS as _STATS
 
 MAX_N, MAX_ROWS, MAX_L = 63, 192, 768
 EXIT_MAXITERS, EXIT_SINGULAR, EXIT_RANK, EXIT_LINESEARCH = 1, 2, 3, 4
 
-
-def _limit(name, value, lo, hi):
-    if not lo <= value <= hi:
-        raise ValueError("gp_batch: %s = %d is outside its limit %d <= %s <= %s; solvers.gp solves one problem of any size"
-                         % (name, value, lo, name, "n" if name == "p" else "%d" % hi))
+_limit = _batch.limiter("gp_batch", "gp")
+_columns, _matrix, _shared_or_batch = _batch.columns, _batch.matrix, _batch.shared_or_batch
 
 
 def _shape(M):
@@ -60,13 +58,7 @@ def _is_d(M):
 
 def _prepare(K, F, g, G, h, A, b, options):
     """Every argument check, on the host; returns what kvx_gp_batch_solve takes."""
-    user = dict(options or {})
-    if user.get("refinement") is None:
-        user["refinement"] = 0
-    opt = _ipm.options(user, {"l": 0, "q": [], "s": []})
-    if opt.refinement != 0:
-        raise NotImplementedError("gp_batch: options['refinement'] = %d is not carried, only 0 (the default here); "
-                                  "solvers.gp refines, once by default" % opt.refinement)
+    opt, _ = _batch.options("gp_batch", "gp", options, {"l": 0, "q": [], "s": []})
     if type(K) is not list or not K or [k for k in K if type(k) is not int or k <= 0]:       # cvx.gp_problem's texts
         raise TypeError("'K' must be a list of positive integers")
     l, mnl = sum(K), len(K) - 1
@@ -98,39 +90,19 @@ def _prepare(K, F, g, G, h, A, b, options):
         if h is None:
             raise TypeError("'h' must be a dense 'd' matrix of size (%d,1)" % ml)
         hv, sh = _shared_or_batch(h, "h", ml, B, "'h' must be a dense 'd' matrix of size (%d,1)" % ml)
-    p = 0 if A is None else _shape(A)[0]
-    _limit("p", p, 0, n)
-    if p == 0:
-        Av, sA, bv, sb = None, 0, None, 0
-        if b is not None and _columns(b, "b", "0 rows").shape[0] != 0:
-            raise TypeError("'b' must be a dense 'd' matrix of size (0,1)")
-    else:
-        Av, sA, _ = _matrix(A, "A", n, B)
-        if b is None:
-            raise TypeError("'b' must be a dense 'd' matrix of size (%d,1)" % p)
-        bv, sb = _shared_or_batch(b, "b", p, B, "'b' must be a dense 'd' matrix of size (%d,1)" % p)
-    gv = np.ascontiguousarray(g.T).reshape(-1)
-    return opt, (B, n, list(K), ml, p), ((Fv, sF), (gv, l if B > 1 else 0), (Gv, sG), (hv, sh), (Av, sA), (bv, sb))
+    # an A without rows is an absent one, so b is looked at; every text of A's own has been raised above
+    p, eqA, eqb = _batch.equalities(A if A is not None and _shape(A)[0] else None, b, n, B, "g", _limit,
+                                    "'b' must be a dense 'd' matrix of size (0,1)", "'b' must be a dense 'd' matrix of size (%d,1)")
+    return opt, (B, n, list(K), ml, p), ((Fv, sF), _batch.flat(g, B), (Gv, sG), (hv, sh), eqA, eqb)
 
 
 def gp_batch(K, F, g, G=None, h=None, A=None, b=None, options=None):
     opt, (B, n, K, ml, p), data = _prepare(K, F, g, G, h, A, b, options)
-    L = _lib.lib()
     m = len(K)
-    N = m + ml
-    x, y, s, z = (np.zeros((rows, B), order="F") for rows in (n, p, N, N))
-    stats = np.zeros((len(_STATS), B), order="F")
-    iters, code = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
-    Kv = np.asarray(K, dtype=np.int64)
-    args = [B, n, m - 1, _lib.pi(Kv), ml, p]
-    for v, stride in data:
-        args += [None if v is None else _lib.pd(v), stride]
-    args += [int(opt.maxiters), float(opt.abstol), float(opt.reltol), float(opt.feastol)]
-    args += [_lib.pd(x), _lib.pd(y) if p else None, _lib.pd(s), _lib.pd(z), _lib.pd(stats), _lib.pi(iters), _lib.pi(code)]
-    _lib.raise_for(L.kvx_gp_batch_solve(*args), "kvx_gp_batch_solve")
-    sol = {"status": ["optimal" if c == EXIT_OPTIMAL else "unknown" for c in code], "x": x, "y": y,
-           "znl": np.asfortranarray(z[1:m]), "snl": np.asfortranarray(s[1:m]), "zl": np.asfortranarray(z[m:]),
-           "sl": np.asfortranarray(s[m:])}
-    sol.update((k, stats[i].copy()) for i, k in enumerate(_STATS))
-    sol.update({"iterations": iters, "exit": code})
-    return sol
+    sol = _batch.solve("kvx_gp_batch_solve", [B, n, m - 1, _batch.orders(K)[1], ml, p], data, opt, B, n, p, m + ml, _STATS, _batch.QP_STATUS)
+    s, z = sol.pop("s"), sol.pop("z")
+    out = {k: sol.pop(k) for k in ("status", "x", "y")}
+    out.update({"znl": np.asfortranarray(z[1:m]), "snl": np.asfortranarray(s[1:m]), "zl": np.asfortranarray(z[m:]),
+                "sl": np.asfortranarray(s[m:])})
+    out.update(sol)
+    return out

@@ -39,79 +39,29 @@ arrays 'iterations' and 'exit':
     or Rank([G; A]) < n")): that member has zeros in x, y, s, z, 0 iterations and nan statistics, and does not disturb the others;
   4 primal infeasible: y, z are the certificate with h'z + b'y = -1, the member's columns of x and s are nan;
   5 dual infeasible: x, s are the certificate with c'x = -1, the member's columns of y and z are nan."""
-import numpy as np
+from . import _batch
+from ._batch import (EXIT_DUAL_INFEASIBLE, EXIT_MAXITERS, EXIT_OPTIMAL, EXIT_PRIMAL_INFEASIBLE, EXIT_RANK,  # noqa: F401
+                     EXIT_SINGULAR, MAX_ML, MAX_N, STATUS)
+from ._batch import LP_STATS as _STATS
 
-from . import _ipm, _lib
-from .qpbatch import MAX_ML, MAX_N, _columns, _matrix, _shared_or_batch
-
-EXIT_OPTIMAL, EXIT_MAXITERS, EXIT_SINGULAR, EXIT_RANK, EXIT_PRIMAL_INFEASIBLE, EXIT_DUAL_INFEASIBLE = range(6)
-STATUS = {EXIT_OPTIMAL: "optimal", EXIT_PRIMAL_INFEASIBLE: "primal infeasible", EXIT_DUAL_INFEASIBLE: "dual infeasible"}
-_STATS = ("gap", "relative gap", "primal objective", "dual objective", "primal infeasibility", "dual infeasibility",
-          "primal slack", "dual slack", "residual as primal infeasibility certificate", "residual as dual infeasibility certificate")
-
-
-def _limit(name, value, lo, hi):
-    if not lo <= value <= hi:
-        raise ValueError("lp_batch: %s = %d is outside its limit %d <= %s <= %s; solvers.lp solves one problem of any size"
-                         % (name, value, lo, name, "n" if name == "p" else "%d" % hi))
-
-
-def _lp_matrix(M, name, n, B):
-    """qpbatch._matrix, whose texts name the member count by qp_batch's 'q': here it is 'c' that defines B."""
-    try:
-        return _matrix(M, name, n, B)
-    except TypeError as e:
-        raise TypeError(str(e).replace("'q' has", "'c' has")) from None
+_limit = _batch.limiter("lp_batch", "lp")
 
 
 def _prepare(c, G, h, A, b, options):
     """Every argument check, on the host; returns what kvx_lp_batch_solve takes."""
-    opt = _ipm.options(options, {}, qp=False)
-    if opt.refinement != 0:
-        raise NotImplementedError("lp_batch: options['refinement'] = %d is not carried, only 0 (the orthant's default); "
-                                  "solvers.lp refines" % opt.refinement)
-    c = _columns(c, "c", "one column per member")
-    n, B = c.shape
-    if B < 1:
-        raise TypeError("'c' must have at least one column")
+    opt = _batch.options("lp_batch", "lp", options, qp=False)
+    c, n, B = _batch.members(c, "c")
     _limit("n", n, 1, MAX_N)
-    Gv, sG, ml = _lp_matrix(G, "G", n, B)
+    Gv, sG, ml = _batch.matrix(G, "G", n, B, defines="c")
     _limit("ml", ml, 1, MAX_ML)
-    hv, sh = _shared_or_batch(h, "h", ml, B, "'h' must be a 'd' matrix of size (%d,1)" % ml)
-    if A is None:
-        p, Av, sA = 0, None, 0
-        if b is not None and _columns(b, "b", "0 rows").shape[0] != 0:
-            raise TypeError("'b' must have length 0")
-        bv, sb = None, 0
-    else:
-        Av, sA, p = _lp_matrix(A, "A", n, B)
-        _limit("p", p, 0, n)
-        if p == 0:
-            Av, bv, sA, sb = None, None, 0, 0
-        else:
-            if b is None:
-                raise TypeError("'b' must have length %d" % p)
-            bv, sb = _shared_or_batch(b, "b", p, B, "'b' must have length %d" % p)
+    hv, sh = _batch.shared_or_batch(h, "h", ml, B, "'h' must be a 'd' matrix of size (%d,1)" % ml)
+    p, eqA, eqb = _batch.equalities(A, b, n, B, "c", _limit)
     if p + ml < n:
         raise ValueError("lp_batch: p + ml = %d is outside its limit p + ml >= n = %d (conelp's Rank([G; A]) < n); solvers.lp "
                          "raises the same for one problem" % (p + ml, n))
-    cv = np.ascontiguousarray(c.T).reshape(-1)
-    return opt, (B, n, ml, p), ((cv, n if B > 1 else 0), (Gv, sG), (hv, sh), (Av, sA), (bv, sb))
+    return opt, (B, n, ml, p), (_batch.flat(c, B), (Gv, sG), (hv, sh), eqA, eqb)
 
 
 def lp_batch(c, G, h, A=None, b=None, options=None):
     opt, (B, n, ml, p), data = _prepare(c, G, h, A, b, options)
-    L = _lib.lib()
-    x, y, s, z = (np.zeros((rows, B), order="F") for rows in (n, p, ml, ml))
-    stats = np.zeros((len(_STATS), B), order="F")
-    iters, code = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
-    args = [B, n, ml, p]
-    for v, stride in data:
-        args += [None if v is None else _lib.pd(v), stride]
-    args += [int(opt.maxiters), float(opt.abstol), float(opt.reltol), float(opt.feastol)]
-    args += [_lib.pd(x), _lib.pd(y) if p else None, _lib.pd(s), _lib.pd(z), _lib.pd(stats), _lib.pi(iters), _lib.pi(code)]
-    _lib.raise_for(L.kvx_lp_batch_solve(*args), "kvx_lp_batch_solve")
-    sol = {"status": [STATUS.get(int(k), "unknown") for k in code], "x": x, "y": y, "s": s, "z": z}
-    sol.update((k, stats[i].copy()) for i, k in enumerate(_STATS))
-    sol.update({"iterations": iters, "exit": code})
-    return sol
+    return _batch.solve("kvx_lp_batch_solve", [B, n, ml, p], data, opt, B, n, p, ml, _STATS, STATUS)

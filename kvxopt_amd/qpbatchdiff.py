@@ -40,13 +40,8 @@ with exit 2 at the limit of their precision, and are skipped here.
 The limits and the texts of the argument checks are those of qp_batch.  Every check runs before a device is asked for; there is
 no CPU fallback.  Not carried: several cotangents per call, derivatives of lp_batch / gp_batch (coneqp_batch: coneqpbatchdiff), gradients with
 respect to y and z, the derivative fused into the forward launch, a torch.autograd.Function."""
-import numpy as np
-
-from . import _lib, qpbatch
-
-EXIT_DONE, EXIT_SKIPPED, EXIT_FAILED = range(3)
-MAX_REFINEMENT = 3
-WRT = ("P", "q", "G", "h", "A", "b")
+from . import _batchdiff, _lib, qpbatch
+from ._batchdiff import EXIT_DONE, EXIT_FAILED, EXIT_SKIPPED, MAX_REFINEMENT, WRT  # noqa: F401
 
 
 def _refinement(who, options):
@@ -54,58 +49,19 @@ def _refinement(who, options):
     ref = o.pop("refinement", 1)
     if o:
         raise ValueError("%s: options accepts only 'refinement', not %s" % (who, ", ".join(repr(k) for k in sorted(o, key=str))))
-    if isinstance(ref, bool) or not isinstance(ref, (int, np.integer)) or ref < 0:
-        raise ValueError("options['refinement'] must be a nonnegative integer")
-    if ref > MAX_REFINEMENT:
-        raise ValueError("%s: options['refinement'] = %d is outside its limit 0 <= refinement <= %d" % (who, ref, MAX_REFINEMENT))
-    return int(ref)
+    return _batchdiff.count(who, "refinement", ref, MAX_REFINEMENT)
 
 
 def _problem(who, P, q, G, h, A, b):
     """qp_batch's own checks of the problem arguments, under the entry's name."""
-    try:
-        _, dims, data = qpbatch._prepare(P, q, G, h, A, b, None)
-    except ValueError as e:
-        raise ValueError(str(e).replace("qp_batch:", who + ":", 1)) from None
-    return dims, data
-
-
-def _solution(sol, B, n, ml, p):
-    """x, y, s, z and exit of `sol` as contiguous arrays, one member after the other."""
-    if not isinstance(sol, dict) or any(k not in sol for k in ("x", "y", "s", "z", "exit")):
-        raise TypeError("'sol' must be the dictionary qp_batch returned, with 'x', 'y', 's', 'z' and 'exit'")
-    out = []
-    for k, rows in (("x", n), ("y", p), ("s", ml), ("z", ml)):
-        v = np.asarray(sol[k], dtype=np.float64)
-        if v.shape != (rows, B):
-            raise TypeError("sol['%s'] must be a 'd' matrix of size (%d, %d)" % (k, rows, B))
-        out.append(np.ascontiguousarray(v.T).reshape(-1))
-    code = np.asarray(sol["exit"])
-    if code.shape != (B,) or code.dtype.kind not in "iu":
-        raise TypeError("sol['exit'] must be an integer array of length %d" % B)
-    return out, np.ascontiguousarray(code, dtype=np.int64)
+    return _batchdiff.problem(who, "qp_batch", qpbatch._prepare, P, q, G, h, A, b)
 
 
 def _common(dims, data, vecs, code, ref):
     """The leading arguments of all four C entries: sizes, P, G, A with strides, the solution, the refinement."""
     (Pv, sP), _, (Gv, sG), _, (Av, sA), _ = data
-    x, y, s, z = vecs
     p = dims[3]
-    return list(dims) + [_lib.pd(Pv), sP, _lib.pd(Gv), sG, _lib.pd(Av) if p else None, sA,
-                         _lib.pd(x), _lib.pd(y) if p else None, _lib.pd(s), _lib.pd(z), _lib.pi(code), ref]
-
-
-def _from_members(v, shared, rows, n, B):
-    """A matrix gradient as the C entry wrote it -- column-major, one member after the other -- in the argument's shape."""
-    return np.ascontiguousarray(v.reshape(n, rows).T) if shared else np.ascontiguousarray(v.reshape(B, n, rows).transpose(0, 2, 1))
-
-
-def _column_gradient(g, given, shared, done):
-    """The gradient of h or b: per member, or the sum over the done members in the shape the shared column was given."""
-    if not shared:
-        return g
-    t = g[:, done].sum(axis=1)
-    return t.reshape(-1, 1) if isinstance(given, np.ndarray) and given.ndim == 2 else t
+    return list(dims) + [_lib.pd(Pv), sP, _lib.pd(Gv), sG, _lib.pd(Av) if p else None, sA] + _batchdiff.solution_pointers(vecs, code, p) + [ref]
 
 
 def qp_batch_vjp(P, q, G, h, A=None, b=None, *, sol, gx, wrt=WRT, options=None):
@@ -113,48 +69,8 @@ def qp_batch_vjp(P, q, G, h, A=None, b=None, *, sol, gx, wrt=WRT, options=None):
     ref = _refinement(who, options)
     dims, data = _problem(who, P, q, G, h, A, b)
     B, n, ml, p = dims
-    vecs, code = _solution(sol, B, n, ml, p)
-    g = qpbatch._columns(gx, "gx", "one column per member")
-    if g.shape != (n, B):
-        raise TypeError("'gx' must be a 'd' matrix of size (%d, %d)" % (n, B))
-    wrt = (wrt,) if isinstance(wrt, str) else tuple(wrt)
-    if any(k not in WRT for k in wrt):
-        raise ValueError("%s: wrt names %s; it takes 'P', 'q', 'G', 'h', 'A', 'b'" % (who, ", ".join(repr(k) for k in wrt if k not in WRT)))
-    gv = np.ascontiguousarray(g.T).reshape(-1)
-    sP, sG, sA = data[0][1], data[2][1], data[4][1]
-    L = _lib.lib()
-    ux, uy, uz = (np.zeros((rows, B), order="F") for rows in (n, p, ml))
-    gexit = np.zeros(B, dtype=np.int64)
-    mats = {}
-    for k, rows, stride in (("P", n, sP), ("G", ml, sG), ("A", p, sA)):
-        mats[k] = np.zeros((B if stride else 1) * rows * n) if k in wrt and rows else None
-    args = _common(dims, data, vecs, code, ref)
-    args += [_lib.pd(gv), _lib.pd(ux), _lib.pd(uy) if p else None, _lib.pd(uz)]
-    args += [None if mats[k] is None else _lib.pd(mats[k]) for k in ("P", "G", "A")] + [_lib.pi(gexit)]
-    _lib.raise_for(L.kvx_qp_batch_vjp(*args), "kvx_qp_batch_vjp")
-    out = {"ux": ux, "uy": uy, "uz": uz, "exit": gexit}
-    done = gexit == EXIT_DONE
-    for k in wrt:
-        if k == "q":
-            out[k] = ux.copy()
-        elif k == "h":
-            out[k] = _column_gradient(0.0 - uz, h, data[3][1] == 0, done)            # 0 - u: no negative zeros
-        elif k == "b":
-            out[k] = _column_gradient(0.0 - uy, b, data[5][1] == 0, done) if p else None
-        else:
-            rows, stride = {"P": (n, sP), "G": (ml, sG), "A": (p, sA)}[k]
-            out[k] = None if mats[k] is None else _from_members(mats[k], stride == 0, rows, n, B)
-    return out
-
-
-def _perturbation(name, v, like, n, B, rows):
-    """(values or None, member stride) of one perturbation, checked as qp_batch checks the datum it perturbs."""
-    if v is None:
-        return None, 0
-    if like in ("P", "G", "A"):
-        vals, stride, _ = qpbatch._matrix(v, name, n, B, rows=rows)
-        return vals, stride
-    return qpbatch._shared_or_batch(v, name, rows, B, "'%s' must be a 'd' matrix of size (%d,1)" % (name, rows))
+    vecs, code = _batchdiff.solution(sol, "qp_batch", B, n, ml, p)
+    return _batchdiff.vjp("kvx_qp_batch_vjp", who, lambda: _common(dims, data, vecs, code, ref), _batchdiff.strides(data), B, n, ml, p, gx, wrt, h, b)
 
 
 def qp_batch_jvp(P, q, G, h, A=None, b=None, *, sol, dP=None, dq=None, dG=None, dh=None, dA=None, db=None, options=None):
@@ -162,15 +78,6 @@ def qp_batch_jvp(P, q, G, h, A=None, b=None, *, sol, dP=None, dq=None, dG=None, 
     ref = _refinement(who, options)
     dims, data = _problem(who, P, q, G, h, A, b)
     B, n, ml, p = dims
-    vecs, code = _solution(sol, B, n, ml, p)
-    pert = [_perturbation("d" + k, v, k, n, B, rows)
-            for k, v, rows in (("P", dP, n), ("q", dq, n), ("G", dG, ml), ("h", dh, ml), ("A", dA, p), ("b", db, p))]
-    L = _lib.lib()
-    dx, dy, dz, ds = (np.zeros((rows, B), order="F") for rows in (n, p, ml, ml))
-    gexit = np.zeros(B, dtype=np.int64)
-    args = _common(dims, data, vecs, code, ref)
-    for k, (vals, stride) in zip(WRT, pert):
-        args += [None if vals is None or (k in "Ab" and not p) else _lib.pd(vals), stride]
-    args += [_lib.pd(dx), _lib.pd(dy) if p else None, _lib.pd(dz), _lib.pd(ds), _lib.pi(gexit)]
-    _lib.raise_for(L.kvx_qp_batch_jvp(*args), "kvx_qp_batch_jvp")
-    return {"x": dx, "y": dy, "z": dz, "s": ds, "exit": gexit}
+    vecs, code = _batchdiff.solution(sol, "qp_batch", B, n, ml, p)
+    pert = _batchdiff.perturbations((dP, dq, dG, dh, dA, db), B, n, ml, p)
+    return _batchdiff.jvp("kvx_qp_batch_jvp", lambda: _common(dims, data, vecs, code, ref), pert, B, n, ml, p)

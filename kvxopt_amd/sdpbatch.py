@@ -36,89 +36,40 @@ Fixed summation order, no atomics; a member's bytes do not depend on B, on its p
 
 The result has the keys, NaN conventions and `exit` codes 0-5 of lp_batch; 's' and 'z' are N x B with every 's' block a full
 symmetric matrix, as cone.conelp returns them; 'primal slack' and 'dual slack' are the reference's -max_step over the whole cone."""
-import numpy as np
+from . import _batch
+from ._batch import LP_STATS as _STATS
+from ._batch import MAX_CONE_ROWS as MAX_ROWS
+from ._batch import MAX_M, MAX_N, MAX_NS, STATUS
 
-from . import _ipm, _lib
-from .lpbatch import _STATS, _lp_matrix, STATUS
-from .qpbatch import MAX_N, _columns, _shared_or_batch
-
-MAX_ROWS = 384
-MAX_NS = 32
-MAX_M = 16
-
-
-def _limit(name, value, lo, hi):
-    if not lo <= value <= hi:
-        raise ValueError("sdp_batch: %s = %d is outside its limit %d <= %s <= %s; solvers.sdp solves one problem of any size"
-                         % (name, value, lo, name, "n" if name == "p" else "%d" % hi))
+_limit = _batch.limiter("sdp_batch", "sdp")
 
 
 def _prepare(c, G, h, dims, A, b, options):
     """Every argument check, on the host; returns what kvx_sdp_batch_solve takes."""
-    user = dict(options or {})
-    if user.get("refinement") is None:
-        user["refinement"] = 0
-    if not isinstance(dims, dict):
-        raise TypeError("'dims' must be a dictionary with the keys 'l' and 's'")
-    dims = _ipm.check_dims(dims)
-    opt = _ipm.options(user, dims, qp=False)
-    if opt.refinement != 0:
-        raise NotImplementedError("sdp_batch: options['refinement'] = %d is not carried, only 0 (the default here); "
-                                  "solvers.sdp refines, once by default" % opt.refinement)
+    opt, dims = _batch.options("sdp_batch", "sdp", options, dims, "'l' and 's'", qp=False)
     if dims["q"]:
         raise ValueError("sdp_batch: dims['q'] = %r is outside its limit, absent or empty; solvers.socp_batch solves batches with "
                          "second-order cones and solvers.conelp problems with both kinds" % (dims["q"],))
     ml, s = int(dims["l"]), [int(k) for k in dims["s"]]
-    c = _columns(c, "c", "one column per member")
-    n, B = c.shape
-    if B < 1:
-        raise TypeError("'c' must have at least one column")
+    c, n, B = _batch.members(c, "c")
     _limit("n", n, 1, MAX_N)
     _limit("ns", len(s), 0, MAX_NS)
     for m in s:
         _limit("m_k", m, 1, MAX_M)
     N = ml + sum(m * m for m in s)
     _limit("N", N, 1, MAX_ROWS)
-    Gv, sG, rows = _lp_matrix(G, "G", n, B)
+    Gv, sG, rows = _batch.matrix(G, "G", n, B, defines="c")
     if rows != N:
         raise TypeError("'G' must be a 'd' matrix of size (%d, %d)" % (N, n))
-    hv, sh = _shared_or_batch(h, "h", N, B, "'h' must be a 'd' matrix of size (%d,1)" % N)
-    if A is None:
-        p, Av, sA = 0, None, 0
-        if b is not None and _columns(b, "b", "0 rows").shape[0] != 0:
-            raise TypeError("'b' must have length 0")
-        bv, sb = None, 0
-    else:
-        Av, sA, p = _lp_matrix(A, "A", n, B)
-        _limit("p", p, 0, n)
-        if p == 0:
-            Av, bv, sA, sb = None, None, 0, 0
-        else:
-            if b is None:
-                raise TypeError("'b' must have length %d" % p)
-            bv, sb = _shared_or_batch(b, "b", p, B, "'b' must have length %d" % p)
+    hv, sh = _batch.shared_or_batch(h, "h", N, B, "'h' must be a 'd' matrix of size (%d,1)" % N)
+    p, eqA, eqb = _batch.equalities(A, b, n, B, "c", _limit)
     packed = ml + sum(m * (m + 1) // 2 for m in s)
     if p + packed < n:
         raise ValueError("sdp_batch: p + ml + sum(m_k (m_k + 1) / 2) = %d is outside its limit, at least n = %d (conelp's "
                          "Rank([G; A]) < n); solvers.sdp raises the same for one problem" % (p + packed, n))
-    cv = np.ascontiguousarray(c.T).reshape(-1)
-    return opt, (B, n, ml, s, N, p), ((cv, n if B > 1 else 0), (Gv, sG), (hv, sh), (Av, sA), (bv, sb))
+    return opt, (B, n, ml, s, N, p), (_batch.flat(c, B), (Gv, sG), (hv, sh), eqA, eqb)
 
 
 def sdp_batch(c, G, h, dims, A=None, b=None, options=None):
     opt, (B, n, ml, s, N, p), data = _prepare(c, G, h, dims, A, b, options)
-    L = _lib.lib()
-    x, y, sv, z = (np.zeros((rows, B), order="F") for rows in (n, p, N, N))
-    stats = np.zeros((len(_STATS), B), order="F")
-    iters, code = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
-    mv = np.asarray(s, dtype=np.int64)
-    args = [B, n, ml, len(s), _lib.pi(mv) if s else None, p]
-    for v, stride in data:
-        args += [None if v is None else _lib.pd(v), stride]
-    args += [int(opt.maxiters), float(opt.abstol), float(opt.reltol), float(opt.feastol)]
-    args += [_lib.pd(x), _lib.pd(y) if p else None, _lib.pd(sv), _lib.pd(z), _lib.pd(stats), _lib.pi(iters), _lib.pi(code)]
-    _lib.raise_for(L.kvx_sdp_batch_solve(*args), "kvx_sdp_batch_solve")
-    sol = {"status": [STATUS.get(int(k), "unknown") for k in code], "x": x, "y": y, "s": sv, "z": z}
-    sol.update((k, stats[i].copy()) for i, k in enumerate(_STATS))
-    sol.update({"iterations": iters, "exit": code})
-    return sol
+    return _batch.solve("kvx_sdp_batch_solve", [B, n, ml] + _batch.orders(s) + [p], data, opt, B, n, p, N, _STATS, STATUS)

@@ -1,6 +1,7 @@
-"""One SHA-256 per named batch of the six batch solvers: what a change that must not move a bit is held to.
+"""One SHA-256 per named batch of the batch solvers and of their derivatives: what a change that must not move a
+bit is held to.
 
-    python tools/batch_bytes.py [--only qp,lp,socp,sdp,conelp,coneqp]
+    python tools/batch_bytes.py [--only qp,lp,socp,sdp,conelp,coneqp,gp,qpdiff,coneqpdiff]
     KVX_LIB_PATH=/path/to/other/libkvxhip.so python tools/batch_bytes.py
 
 For solvers.qp_batch, lp_batch, socp_batch, sdp_batch, conelp_batch and coneqp_batch it runs every named batch of
@@ -9,7 +10,12 @@ all of SHAPES, every key of BATCHES (qp: INDEPENDENCE and MIXED; coneqp: each wi
 tests/test_*_batch_gpu.py spoil them, and the golden cases as those tests batch them (member 0 of a batch of three with shared
 matrices and perturbed linear terms; the tiny LPs in batches of their own; coneqp's with the options recorded with the case) --
 and prints, for each (solver, batch), the SHA-256 over the bytes of x, y, s, z,
-every stat, `iterations`, `exit` and the statuses.  The last line is the whole as JSON.  The library is loaded through
+every stat, `iterations`, `exit` and the statuses.  `gp`: every named batch of tests/gp_batch_numpy.py (the edges with their
+options, "spread700", "independence", "mixed", "branches", "restore", "restore2"), the vectors being x, y, znl, snl, zl, sl.  `qpdiff`
+and `coneqpdiff`: every shape of qp_batch_diff_numpy.SHAPES and every batch of coneqp_batch_diff_numpy.SMALL_BATCHES, solved and
+differentiated as tests/test_{qp,coneqp}_batch_diff_gpu.py do it, once with matrices per member and once with member 0's P, G, A
+shared by all; the digest covers ux, uy, uz, exit and every `wrt` gradient of the vjp and x, y, z, s, exit of the jvp, for coneqp also
+'centrality' and 'centering steps' of both.  The last line is the whole as JSON.  The library is loaded through
 kvxopt_amd._lib, so KVX_LIB_PATH selects the build; run two builds in two processes and compare the two last lines.  The digests
 belong to one compiler and one device: none is kept in the repository.
 
@@ -28,8 +34,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import conelp_batch_numpy as CONE  # noqa: E402
+import coneqp_batch_diff_numpy as CONEQPDIFF  # noqa: E402
 import coneqp_batch_numpy as CONEQP  # noqa: E402
+import gp_batch_numpy as GP  # noqa: E402
 import lp_batch_numpy as LP  # noqa: E402
+import qp_batch_diff_numpy as QPDIFF  # noqa: E402
 import qp_batch_numpy as QP  # noqa: E402
 import sdp_batch_numpy as SDP  # noqa: E402
 import socp_batch_numpy as SOCP  # noqa: E402
@@ -42,9 +51,9 @@ QP_STATS = ("gap", "relative gap", "primal objective", "dual objective", "primal
 LP_STATS = QP_STATS + ("residual as primal infeasibility certificate", "residual as dual infeasibility certificate")
 
 
-def digest(sol, stats):
+def digest(sol, stats, vectors=VECTORS):
     h = hashlib.sha256()
-    for v in VECTORS:
+    for v in vectors:
         h.update(np.ascontiguousarray(sol[v], dtype=np.float64).tobytes())
     for f in stats:
         h.update(np.ascontiguousarray(sol[f], dtype=np.float64).tobytes())
@@ -173,6 +182,60 @@ def coneqp_batches():
                                                      get("b"), options=meta[name]["options"])
 
 
+def gp_batches():
+    for name in list(GP.EDGES) + ["spread700", "independence", "mixed", "branches", "restore", "restore2"]:
+        sol = solvers.gp_batch(*GP.batch_args(GP.named(name)), options=GP.EDGE_OPTIONS.get(name))
+        yield name, digest(sol, QP_STATS, ("x", "y", "znl", "snl", "zl", "sl"))
+
+
+def derivative_digest(V, J, extra=()):
+    h = hashlib.sha256()
+    for r, vectors in ((V, ("ux", "uy", "uz")), (J, ("x", "y", "z", "s"))):
+        for v in vectors:
+            h.update(np.ascontiguousarray(r[v], dtype=np.float64).tobytes())
+        h.update(np.ascontiguousarray(r["exit"], dtype=np.int64).tobytes())
+        for k in extra:
+            h.update(np.ascontiguousarray(r[k]).tobytes())
+    for name in QPDIFF.NAMES:
+        h.update(b"none" if V[name] is None else np.ascontiguousarray(V[name], dtype=np.float64).tobytes())
+    return h.hexdigest()
+
+
+def derivative_batches(batches, solve, vjp, jvp, extra=()):
+    """batches: (name, M, gx, d); solve / vjp / jvp(P, G, A) take the three matrices, per member or shared."""
+    for name, M, gx, d in batches:
+        pert = {"d" + k: v for k, v in d.items()}
+        for kind, (P, G, A) in (("members", (M.P, M.G, M.A)), ("shared", (M.P[0], M.G[0], None if M.A is None else M.A[0]))):
+            sol = solve(M, P, G, A)
+            yield "%s-%s" % (name, kind), derivative_digest(vjp(M, P, G, A, sol, gx), jvp(M, P, G, A, sol, pert), extra)
+
+
+def qpdiff_batches():
+    def batches():
+        for shape in QPDIFF.SHAPES:                        # tests/test_qp_batch_diff_gpu.py::case
+            seed = QPDIFF.SEEDS[shape]
+            M = QP.batch(shape, QP.SHAPE_B, seed)
+            gx = np.asfortranarray(np.random.default_rng(seed + 1).standard_normal((M.n, QP.SHAPE_B)))
+            yield "shape-%d-%d-%d" % shape, M, gx, QPDIFF.direction(M, seed + 2)
+
+    return derivative_batches(batches(), lambda M, P, G, A: solvers.qp_batch(P, M.q, G, M.h, A, M.b),
+                              lambda M, P, G, A, sol, gx: solvers.qp_batch_vjp(P, M.q, G, M.h, A, M.b, sol=sol, gx=gx),
+                              lambda M, P, G, A, sol, pert: solvers.qp_batch_jvp(P, M.q, G, M.h, A, M.b, sol=sol, **pert))
+
+
+def coneqpdiff_batches():
+    def batches():
+        for name in CONEQPDIFF.SMALL_BATCHES:              # tests/test_coneqp_batch_diff_gpu.py::case
+            M = CONEQPDIFF.batch(name)
+            yield name, M, CONEQPDIFF.cotangent(M, 5), CONEQPDIFF.direction(M, 6)
+
+    return derivative_batches(batches(),
+                              lambda M, P, G, A: solvers.coneqp_batch(P, M.q, G, M.h, M.dims, A, M.b, options=CONEQPDIFF.SOLVE_TOL),
+                              lambda M, P, G, A, sol, gx: solvers.coneqp_batch_vjp(P, M.q, G, M.h, M.dims, A, M.b, sol=sol, gx=gx),
+                              lambda M, P, G, A, sol, pert: solvers.coneqp_batch_jvp(P, M.q, G, M.h, M.dims, A, M.b, sol=sol, **pert),
+                              ("centrality", "centering steps"))
+
+
 SOLVERS = {
     "qp": (qp_batches, QP_STATS),
     "lp": (lp_batches, LP_STATS),
@@ -183,12 +246,15 @@ SOLVERS = {
     "conelp": (lambda: dims_batches(CONE, solvers.conelp_batch, spoil_conelp, "g28_conelp_batch",
                                     ("doc_conelp", "doc_conelp_lower", "mixed_eq", "conelp_pinf", "conelp_dinf")), LP_STATS),
     "coneqp": (coneqp_batches, QP_STATS),
+    "gp": (gp_batches, None),                              # these three yield digests
+    "qpdiff": (qpdiff_batches, None),
+    "coneqpdiff": (coneqpdiff_batches, None),
 }
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="qp,lp,socp,sdp,conelp,coneqp")
+    ap.add_argument("--only", default=",".join(SOLVERS))
     a = ap.parse_args()
     _lib.require_device()
     print("library: %s" % _lib.LIB_PATH)
@@ -197,8 +263,8 @@ def main():
         batches, stats = SOLVERS[solver]
         out[solver] = {}
         for name, sol in batches():
-            out[solver][name] = digest(sol, stats)
-            print("%-6s %-28s %s" % (solver, name, out[solver][name]), flush=True)
+            out[solver][name] = sol if stats is None else digest(sol, stats)
+            print("%-10s %-36s %s" % (solver, name, out[solver][name]), flush=True)
     print(json.dumps(out, sort_keys=True))
 
 
