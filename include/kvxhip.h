@@ -953,6 +953,57 @@ int kvx_gp_batch_solve_dev(int64_t B, int64_t n, int64_t mnl, const int64_t *K, 
                            double *x, double *y, double *s, double *z, double *stats, int64_t *iterations, int64_t *exitcode,
                            double *scratch);
 
+/* ---- derivatives of a solved batch of geometric programs (csrc/gp_batch_diff.hip).  With zeta_0 = 1,
+ * zeta_i = z_i (i = 1..mnl), y_i = softmax(F_i x + g_i) and Df_i = y_i'F_i per block, the optimality conditions of member b
+ * differentiated at its returned x, y, s, z are a linear system in x-space (order n; the epigraph row is gone) with the matrix
+ *     K = [ H  A'  J' ;  A  0  0 ;  J  0  -diag(s / z) ],   H = sum_i zeta_i F_i'(diag y_i - y_i y_i')F_i,   J = [Df_1..Df_mnl; G],
+ * whose reduced matrix H + J' diag(z / s) J is assembled from the staged rows of k_gp_batch and factored once per member, one
+ * workgroup each, in ONE launch, with `refinement` (0..3) steps of iterative refinement on the full system.
+ * The problem arguments B .. sA are those of kvx_gp_batch_solve (K a HOST array for all entries); g enters (for y), h and b
+ * do not.  x (n x B), y (p x B), exitcode (B) and s, z (N x B, N = mnl + 1 + ml, the objective row first) are what
+ * kvx_gp_batch_solve[_dev] wrote; row 0 of s and z is not read.  uz, dz, ds have N rows too and row 0 is written as 0.
+ * kvx_gp_batch_vjp (reverse mode): the cotangent gx (n x B); K [ux; uy; uz] = [-gx; 0; 0].  Results ux, uy (p x B), uz,
+ *   gg (l x B) = dl/dg with gg_k = y_k (zeta_i (F_k - Df_i) ux + uz_i) (uz_0 = 0), and where the pointer is not NULL
+ *   gF = a ux' + gg x' (l x n; a_k = zeta_i y_k), gG = uzl x' + zl ux' (ml x n), gA = uy x' + y ux' (p x n), column-major:
+ *   one per member after the other for a matrix with a member stride, ONE matrix, the sum over the done members in an order
+ *   fixed at compile time, for a shared one (stride 0).  dl/dh = -uzl and dl/db = -uy are left to the caller.
+ *   The _dev entry takes `work`: l x B doubles of device memory that receive a, needed (not NULL) when gF is asked for and F
+ *   is shared -- a workspace and not a result, since a is no derivative and a host caller has no use for l x B more doubles
+ *   coming down; the host entry takes it from the pool.
+ * kvx_gp_batch_jvp (forward mode): perturbations dF (l x n), dg (l), dG (ml x n), dh (ml), dA (p x n), db (p), each NULL (zero),
+ *   shared (stride 0) or per member; with v = dF x + dg,
+ *   K [dx; dy; dz] = [-(sum_i zeta_i (dF_i'y_i + F_i'(y_i o v_i - y_i (y_i'v_i))) + dG'zl + dA'y); db - dA x; (-y_i'v_i; dh - dG x)]
+ *   and ds = -(s / z) dz.  Results dx, dy, dz, ds.
+ * gexit (B): 0 done; 1 skipped since exitcode[b] != 0; 2 a failed pivot or an s_k, z_k (k >= 1) that is not positive and
+ * finite.  1 and 2 leave zeros in every per-member output and add nothing to a shared sum.  A member's bytes do not depend on
+ * B, on its place or on the other members.
+ * Host entries: host pointers; upload, launch, download.  The _dev entries: device pointers (K excepted), results complete on
+ * return.  KVX_EINVAL for bad sizes, limits, strides, refinement, NULL pointers or a non-positive K[i] on any box, before a
+ * device is asked for; KVX_EDEVICE without a GPU (never a CPU fallback).  kvx_gp_batch_diff_lds_bytes: the LDS of one
+ * workgroup of the derivative in bytes, -1 outside the limits; forward (may be NULL) receives that of k_gp_batch. */
+int kvx_gp_batch_vjp(int64_t B, int64_t n, int64_t mnl, const int64_t *K, int64_t ml, int64_t p, const double *F, int64_t sF,
+                     const double *g, int64_t sg, const double *G, int64_t sG, const double *A, int64_t sA, const double *x,
+                     const double *y, const double *s, const double *z, const int64_t *exitcode, int64_t refinement, const double *gx,
+                     double *ux, double *uy, double *uz, double *gg, double *gF, double *gG, double *gA, int64_t *gexit);
+int kvx_gp_batch_vjp_dev(int64_t B, int64_t n, int64_t mnl, const int64_t *K, int64_t ml, int64_t p, const double *F, int64_t sF,
+                         const double *g, int64_t sg, const double *G, int64_t sG, const double *A, int64_t sA, const double *x,
+                         const double *y, const double *s, const double *z, const int64_t *exitcode, int64_t refinement,
+                         const double *gx, double *ux, double *uy, double *uz, double *gg, double *gF, double *gG, double *gA,
+                         double *work, int64_t *gexit);
+int kvx_gp_batch_jvp(int64_t B, int64_t n, int64_t mnl, const int64_t *K, int64_t ml, int64_t p, const double *F, int64_t sF,
+                     const double *g, int64_t sg, const double *G, int64_t sG, const double *A, int64_t sA, const double *x,
+                     const double *y, const double *s, const double *z, const int64_t *exitcode, int64_t refinement, const double *dF,
+                     int64_t sdF, const double *dg, int64_t sdg, const double *dG, int64_t sdG, const double *dh, int64_t sdh,
+                     const double *dA, int64_t sdA, const double *db, int64_t sdb, double *dx, double *dy, double *dz, double *ds,
+                     int64_t *gexit);
+int kvx_gp_batch_jvp_dev(int64_t B, int64_t n, int64_t mnl, const int64_t *K, int64_t ml, int64_t p, const double *F, int64_t sF,
+                         const double *g, int64_t sg, const double *G, int64_t sG, const double *A, int64_t sA, const double *x,
+                         const double *y, const double *s, const double *z, const int64_t *exitcode, int64_t refinement,
+                         const double *dF, int64_t sdF, const double *dg, int64_t sdg, const double *dG, int64_t sdG, const double *dh,
+                         int64_t sdh, const double *dA, int64_t sdA, const double *db, int64_t sdb, double *dx, double *dy, double *dz,
+                         double *ds, int64_t *gexit);
+int64_t kvx_gp_batch_diff_lds_bytes(int64_t n, int64_t mnl, const int64_t *K, int64_t ml, int64_t p, int64_t *forward);
+
 /* ---- dense helpers of the equality-constrained KKT solve with a general S (misc.py:1476-1487, 1545): K = A S^-1 A' formed
  * as a dense p x p matrix from X = S^-1 A' (kvx_chol_solve_dev with nrhs = p) when p is moderate ------------------------- */
 /* Y(j, c) = sum_i A(i, j) X(i, c) for the CCS matrix A with n columns and every column c < ncols of the dense X */

@@ -272,6 +272,12 @@ _SIGS = {
     "kvx_gp_batch_scratch_doubles": (i64, [i64] * 4),
     "kvx_gp_batch_solve": (ctypes.c_int, [i64] * 3 + [i64p, i64, i64] + [f64p, i64] * 6 + [i64, f64, f64, f64] + [f64p] * 5 + [i64p] * 2),
     "kvx_gp_batch_solve_dev": (ctypes.c_int, [i64] * 3 + [i64p, i64, i64] + [vp, i64] * 6 + [i64, f64, f64, f64] + [vp] * 8),
+    "kvx_gp_batch_vjp": (ctypes.c_int, [i64] * 3 + [i64p, i64, i64] + [f64p, i64] * 4 + [f64p] * 4 + [i64p, i64] + [f64p] * 8 + [i64p]),
+    "kvx_gp_batch_vjp_dev": (ctypes.c_int, [i64] * 3 + [i64p, i64, i64] + [vp, i64] * 4 + [vp] * 5 + [i64] + [vp] * 10),
+    "kvx_gp_batch_jvp": (ctypes.c_int, [i64] * 3 + [i64p, i64, i64] + [f64p, i64] * 4 + [f64p] * 4 + [i64p, i64] + [f64p, i64] * 6
+                         + [f64p] * 4 + [i64p]),
+    "kvx_gp_batch_jvp_dev": (ctypes.c_int, [i64] * 3 + [i64p, i64, i64] + [vp, i64] * 4 + [vp] * 5 + [i64] + [vp, i64] * 6 + [vp] * 5),
+    "kvx_gp_batch_diff_lds_bytes": (i64, [i64] * 2 + [i64p, i64, i64, i64p]),
     "kvx_vec_scatter_dev": (ctypes.c_int, [i64, vp, vp, vp]),
     "kvx_nts_colscale_dev": (ctypes.c_int, [i64, vp, vp, vp, vp]),
     "kvx_spmm_t_dev": (ctypes.c_int, [i64, i64, vp, vp, vp, vp, i64, vp, i64]),

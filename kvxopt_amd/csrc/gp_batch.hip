@@ -23,14 +23,14 @@
 // so it is workgroup-uniform.  A NaN or Inf never passes a pivot test (!(pivot > 0 && pivot < inf) fails).
 #include "gp_batch.hpp"
 #include "batch_kkt.hpp"
+#include "gp_batch_device.hpp"
 
 #include <cmath>
 
 namespace kvx {
 namespace {
 
-using namespace batchdev;
-static_assert(NT == GPB_THREADS, "the shared helpers are written for the workgroup of k_gp_batch");
+using namespace gpdev;
 constexpr double BETA = 0.5, ALPHA = 0.01, STEP = 0.99;     // cvxprog.py:384-388, 424
 constexpr int MAX_RELAXED_ITERS = 8, EXPON = 3;
 
@@ -85,12 +85,10 @@ __host__ __device__ inline Saved saved(int n, int m, int ml, int p)
     return V;
 }
 
-struct Member : KktMem {                      // KktMem::n is the order n + 1 of the system; A is the padded copy in the scratch
-    int nx, m, ml, N, l;                      // nx: the variables of the program, the column of t
-    const double *F, *g, *G, *h, *b;
-    const int *off, *blk;
-    double *Gs;                               // the block gradients beside the staged rows
-    double *x, *dx, *rx, *y, *dy, *ry, *s, *z, *d, *di, *lm, *lmsq, *ds, *dz, *ds2, *dz2, *rz, *ws, *f, *yv, *w, *red;
+struct Member : GpMem {                       // KktMem::n is the order n + 1 of the system; A is the padded copy in the scratch
+    int N;
+    const double *h, *b;
+    double *x, *dx, *rx, *y, *dy, *ry, *s, *z, *d, *di, *lm, *lmsq, *ds, *dz, *ds2, *dz2, *rz, *ws, *f, *red;
 };
 
 // dst[k] := src[k], k < count, every thread its own indices: the way to and from the HBM scratch.  No barrier.
@@ -99,121 +97,13 @@ __device__ __forceinline__ void copy_own(double *dst, const double *src, int cou
     for (int k = threadIdx.x; k < count; k += NT) dst[k] = src[k];
 }
 
-// The evaluator at the point xe = (x, t) (cvxprog.py:2109-2126): f (m values, -t on row 0) and yv = exp(u) / sum exp(u) per
-// block, u = F x + g, the maximum of a block taken before exp.  A wavefront per block, lanes along its terms.  Barriers before
-// (the caller's) and after.
-__device__ __forceinline__ void lse_eval(const Member &M, const double *xe, double *f, double *yv)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int k = threadIdx.x; k < M.l; k += NT) yv[k] = row_dot(M.F, M.l, M.nx, k, xe) + M.g[k];
-    __syncthreads();
-    for (int i = w; i < M.m; i += NW) {
-        const int a = M.off[i], b = M.off[i + 1];
-        double mx = -INFINITY;
-        for (int k = a + lane; k < b; k += 64) mx = fmax(mx, yv[k]);
-        mx = wave_max(mx);
-        double sm = 0.0;
-        for (int k = a + lane; k < b; k += 64) {
-            const double e = exp(yv[k] - mx);
-            yv[k] = e;
-            sm += e;
-        }
-        sm = wave_sum(sm);
-        for (int k = a + lane; k < b; k += 64) yv[k] /= sm;
-        if (lane == 0) f[i] = mx + log(sm) - (i == 0 ? xe[M.nx] : 0.0);
-    }
-    __syncthreads();
-}
-
-// out += sign * J'(sc o v) (sc null: ones) for the N-vector v, J = [Df; G] at the point whose weights are yv.  Barriers before
-// (the caller's) and after.
-__device__ __forceinline__ void jt_add(const Member &M, const double *yv, const double *v, const double *sc, double sign, double *out)
-{
-    for (int k = threadIdx.x; k < M.l; k += NT) {
-        const int i = M.blk[k];
-        M.w[k] = yv[k] * (sc ? sc[i] * v[i] : v[i]);
-    }
-    __syncthreads();
-    gemv_t_add(M.F, M.l, M.nx, M.w, nullptr, sign, out);
-    if (threadIdx.x == NT - 1) out[M.nx] -= sign * (sc ? sc[0] * v[0] : v[0]);     // column n holds -1 in row 0 and nothing else
-    __syncthreads();
-    if (M.ml > 0) gemv_t_add(M.G, M.ml, M.nx, v + M.m, sc ? sc + M.m : nullptr, sign, out);
-    __syncthreads();
-}
-
-// out := J u for the (n + 1)-vector u.  Barriers before (the caller's) and after.
-__device__ __forceinline__ void j_mul(const Member &M, const double *yv, const double *u, double *out)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int k = threadIdx.x; k < M.l; k += NT) M.w[k] = yv[k] * row_dot(M.F, M.l, M.nx, k, u);
-    for (int k = threadIdx.x; k < M.ml; k += NT) out[M.m + k] = row_dot(M.G, M.ml, M.nx, k, u);
-    __syncthreads();
-    for (int i = w; i < M.m; i += NW) {
-        double acc = 0.0;
-        for (int k = M.off[i] + lane; k < M.off[i + 1]; k += 64) acc += M.w[k];
-        acc = wave_sum(acc);
-        if (lane == 0) out[i] = acc - (i == 0 ? u[M.nx] : 0.0);
-    }
-    __syncthreads();
-}
-
-// dst[j * ldn + c] := sc_i Df_i[c] (sc null: 1) for the blocks i = i0 + j, j < nb, c < n: a wavefront per entry, lanes along the
-// terms of the block.  With sc, column n of the row as well: -sc_0 on block 0, else 0.  No barrier.
-__device__ __forceinline__ void block_grads(const Member &M, int i0, int nb, const double *sc, double *dst)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int t = w; t < nb * M.nx; t += NW) {
-        const int j = t / M.nx, c = t - j * M.nx, i = i0 + j;
-        double acc = 0.0;
-        for (int k = M.off[i] + lane; k < M.off[i + 1]; k += 64) acc += M.yv[k] * M.F[k + (int64_t)c * M.l];
-        acc = wave_sum(acc);
-        if (lane == 0) dst[j * M.ldn + c] = sc ? sc[i] * acc : acc;
-    }
-    if (sc)
-        for (int j = threadIdx.x; j < nb; j += NT) dst[j * M.ldn + M.nx] = i0 + j == 0 ? -sc[0] : 0.0;
-}
-
-// The KKT factorisation at (x, z) in the scaling di (misc.py:1436-1487): S = H + J' diag(di^2) J from staged rows, its factor
-// L in place, and for p > 0 X, K and its factor (batch_kkt.hpp).  false on a failed pivot.  Barriers before (the caller's) and
-// after.
+// The KKT factorisation at (x, z) in the scaling di (misc.py:1436-1487): S = H + J' diag(di^2) J from staged rows
+// (gp_batch_device.hpp), its factor L in place, and for p > 0 X, K and its factor (batch_kkt.hpp).  false on a failed pivot.
+// Barriers before (the caller's) and after.
 __device__ __forceinline__ bool factor(const Member &M)
 {
-    const int ne = M.n, nx = M.nx, l = M.l, ml = M.ml, m = M.m, ldn = M.ldn;
-    kkt_s_init(M, false);
-    for (int k0 = 0; k0 < l; k0 += GPB_TILE) {                       // sqrt(z_i y_k) (F_k - Df_i)
-        const int kt = min((int)GPB_TILE, l - k0), i0 = M.blk[k0], nb = M.blk[k0 + kt - 1] - i0 + 1;
-        __syncthreads();                                   // the staged rows of the previous step have been read
-        block_grads(M, i0, nb, nullptr, M.Gs);
-        __syncthreads();
-        for (int e = threadIdx.x; e < GPB_TILE * ne; e += NT) {
-            const int kk = e & (GPB_TILE - 1), c = e / GPB_TILE;
-            if (kk < kt) {
-                const int k = k0 + kk, i = M.blk[k];
-                M.T[kk * ldn + c] = c < nx ? sqrt(M.z[i] * M.yv[k]) * (M.F[k + (int64_t)c * l] - M.Gs[(i - i0) * ldn + c]) : 0.0;
-            }
-        }
-        __syncthreads();
-        kkt_s_add_rows(M, kt);
-    }
-    for (int i0 = 0; i0 < m; i0 += GPB_TILE) {                       // dnli_i Df_i
-        const int it = min((int)GPB_TILE, m - i0);
-        __syncthreads();
-        block_grads(M, i0, it, M.di, M.T);
-        __syncthreads();
-        kkt_s_add_rows(M, it);
-    }
-    for (int k0 = 0; k0 < ml; k0 += GPB_TILE) {                      // di_k G_k
-        const int kt = min((int)GPB_TILE, ml - k0);
-        __syncthreads();
-        for (int e = threadIdx.x; e < GPB_TILE * ne; e += NT) {
-            const int kk = e & (GPB_TILE - 1), c = e / GPB_TILE;
-            if (kk < kt) M.T[kk * ldn + c] = c < nx ? M.di[m + k0 + kk] * M.G[k0 + kk + (int64_t)c * ml] : 0.0;
-        }
-        __syncthreads();
-        kkt_s_add_rows(M, kt);
-    }
-    __syncthreads();
-    return chol_lds(M.S, ldn, ne) && kkt_equalities(M);
+    gp_assemble<true>(M, M.z, M.di, false);
+    return chol_lds(M.S, M.ldn, M.n) && kkt_equalities(M);
 }
 
 // misc.py:1489-1563 on the LDS vectors (vx, vy, vz) = (bx, by, bz): on return ux, uy, W uz.  Barriers before (the caller's)
@@ -222,9 +112,9 @@ __device__ __forceinline__ void kkt_solve(const Member &M, double *vx, double *v
 {
     for (int k = threadIdx.x; k < M.N; k += NT) vz[k] *= M.di[k];
     __syncthreads();
-    jt_add(M, M.yv, vz, M.di, 1.0, vx);
+    jt_add<true>(M, M.yv, vz, M.di, 1.0, vx);
     kkt_reduced_solve(M, false, vx, vy);
-    j_mul(M, M.yv, vx, M.ws);
+    j_mul<true>(M, M.yv, vx, M.ws);
     for (int k = threadIdx.x; k < M.N; k += NT) vz[k] = M.di[k] * M.ws[k] - vz[k];
     __syncthreads();
 }
@@ -255,14 +145,7 @@ __global__ void __launch_bounds__(GPB_THREADS) k_gp_batch(GpBatchArgs a)
     double *xo = a.x + bm * nx, *yo = p ? a.y + bm * p : nullptr, *so = a.s + bm * N, *zo = a.z + bm * N, *st = a.stats + bm * GPB_NSTAT;
 
     // ---- the blocks, A with its zero column, the starting point x = 0, t = 0, y = 0, s = z = 1 (cvxprog.py:557-570)
-    if (tid == 0) {
-        int o = 0;
-        for (int i = 0; i < m; i++) { off[i] = o; o += a.K[i]; }
-        off[m] = o;
-    }
-    __syncthreads();
-    for (int i = tid; i < m; i += NT)
-        for (int k = off[i]; k < off[i + 1]; k++) blk[k] = i;
+    gp_blocks(a, off, blk);
     if (p > 0) {
         const double *A = a.A + bm * a.sA;
         for (int e = tid; e < p * ne; e += NT) sv[V.A + e] = e < p * nx ? A[e] : 0.0;
@@ -278,7 +161,7 @@ __global__ void __launch_bounds__(GPB_THREADS) k_gp_batch(GpBatchArgs a)
     double phi0 = 0.0, dphi0 = 0.0, gap0 = 0.0, step0 = 0.0, dsdz0 = 0.0, sigma0 = 0.0, eta0 = 0.0;
     for (;; iters++) {
         // ---- f, the weights of Df and H at x; residuals and objectives (cvxprog.py:625-727)
-        lse_eval(M, M.x, M.f, M.yv);
+        lse_eval<true>(M, M.x, M.f, M.yv);
         double v[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};               // |rx|^2, |ry|^2, |rznl|^2, |rzl|^2, y'ry, z'rz, s'z
         if (tid < ne) M.rx[tid] = tid == nx ? 1.0 : 0.0;                 // c = e_n
         if (tid < p) {
@@ -298,7 +181,7 @@ __global__ void __launch_bounds__(GPB_THREADS) k_gp_batch(GpBatchArgs a)
         __syncthreads();
         if (p > 0) gemv_t_add(M.A, p, ne, M.y, nullptr, 1.0, M.rx);
         __syncthreads();
-        jt_add(M, M.yv, M.z, nullptr, 1.0, M.rx);
+        jt_add<true>(M, M.yv, M.z, nullptr, 1.0, M.rx);
         if (tid < ne) v[0] = M.rx[tid] * M.rx[tid];
         blk_reduce<7, false>(v, M.red);
         gap = v[6];
@@ -341,7 +224,7 @@ __global__ void __launch_bounds__(GPB_THREADS) k_gp_batch(GpBatchArgs a)
             blk_reduce<2, false>(r, M.red);                // its barriers also publish the restored state
             resx = sqrt(r[0]); resznl = sqrt(r[1]);
             relaxed_iters = -1;
-            lse_eval(M, M.x, M.f, M.yv);
+            lse_eval<true>(M, M.x, M.f, M.yv);
         }
         if (failed) break;
 
@@ -386,10 +269,10 @@ __global__ void __launch_bounds__(GPB_THREADS) k_gp_batch(GpBatchArgs a)
                 }
                 if (tid < ne) newrx[tid] = tid == nx ? 1.0 : 0.0;
                 __syncthreads();
-                lse_eval(M, newx, newf, yn);
+                lse_eval<true>(M, newx, newf, yn);
                 if (p > 0) gemv_t_add(M.A, p, ne, newy, nullptr, 1.0, newrx);
                 __syncthreads();
-                jt_add(M, yn, newz, nullptr, 1.0, newrx);
+                jt_add<true>(M, yn, newz, nullptr, 1.0, newrx);
                 double r[2] = {0.0, 0.0};
                 if (tid < ne) r[0] = newrx[tid] * newrx[tid];
                 for (int k = tid; k < m; k += NT) { const double u = news[k] + newf[k]; r[1] += u * u; }

@@ -33,4 +33,31 @@ struct GpBatchArgs : BatchArgs {
 size_t gp_batch_lds_bytes(int n, int m, int l, int ml, int p);
 int64_t gp_batch_scratch_doubles(int n, int m, int ml, int p);
 hipError_t launch_gp_batch(hipStream_t st, const GpBatchArgs &a);
+
+namespace gphost {
+// The limits of a member, as the solver's and the derivative's entries refuse them before anything else; on success the blocks
+// are placed in `a`.
+inline int place_blocks(const char *who, GpBatchArgs &a, int64_t mnl, const int64_t *K)
+{
+    using batchhost::refuse;
+    if (a.B < 1 || a.B > 2147483647) return refuse(who, "1 <= B <= 2147483647 is required");
+    if (a.n < 1 || a.n > GPB_MAX_N) return refuse(who, "1 <= n <= 63 is required");
+    if (mnl < 0 || mnl + 1 > GPB_MAX_ROWS) return refuse(who, "0 <= mnl and N = mnl + 1 + ml <= 192 are required");
+    if (!K) return refuse(who, "the block sizes K are NULL");
+    int64_t l = 0;
+    for (int64_t i = 0; i <= mnl; i++) {
+        if (K[i] < 1) return refuse(who, "every block size K[i] is a positive integer");
+        if (K[i] > GPB_MAX_L) return refuse(who, "l = sum(K) <= 768 is required");
+        l += K[i];
+    }
+    if (l > GPB_MAX_L) return refuse(who, "l = sum(K) <= 768 is required");
+    if (a.ml < 0) return refuse(who, "ml >= 0 is required");
+    if (mnl + 1 + a.ml > GPB_MAX_ROWS) return refuse(who, "0 <= mnl and N = mnl + 1 + ml <= 192 are required");
+    if (a.p < 0 || a.p > a.n) return refuse(who, "0 <= p <= n is required");
+    a.m = (int)mnl + 1;
+    a.l = (int)l;
+    for (int i = 0; i < GPB_MAX_ROWS; i++) a.K[i] = i < a.m ? (unsigned short)K[i] : 0;
+    return KVX_OK;
+}
+}  // namespace gphost
 }  // namespace kvx

@@ -1,7 +1,8 @@
 // kvx_gp_batch_solve / kvx_gp_batch_solve_dev (include/kvxhip.h): the limits of k_gp_batch (gp_batch.hip) and its launch on the
 // pieces the batch solvers share (batch_host.hpp: the refusal, the question for a device, the packed arguments, the pooled
 // copies).  g travels as the c of BatchArgs; F is the program's own.  The block sizes K are a host array for both entries: they
-// travel to the kernel with its arguments.  check_common and solve_host are not used: here g has l entries and not n, G and h
+// travel to the kernel with its arguments; the limits of a member and their placement are gphost::place_blocks of gp_batch.hpp,
+// which the derivative's entries (gp_batch_diff_api.cpp) call too.  check_common and solve_host are not used: here g has l entries and not n, G and h
 // have ml >= 0 rows where s and z have N = mnl + 1 + ml, and a member has a workspace in HBM, which the host entry allocates
 // and the _dev entry is given.
 #include "batch_host.hpp"
@@ -15,28 +16,12 @@ namespace {
 // What both entries check before a device is asked for; on success the blocks are placed in `a`
 int check(const char *who, GpBatchArgs &a, int64_t mnl, const int64_t *K, bool resident)
 {
-    if (a.B < 1 || a.B > 2147483647) return refuse(who, "1 <= B <= 2147483647 is required");
-    if (a.n < 1 || a.n > GPB_MAX_N) return refuse(who, "1 <= n <= 63 is required");
-    if (mnl < 0 || mnl + 1 > GPB_MAX_ROWS) return refuse(who, "0 <= mnl and N = mnl + 1 + ml <= 192 are required");
-    if (!K) return refuse(who, "the block sizes K are NULL");
-    int64_t l = 0;
-    for (int64_t i = 0; i <= mnl; i++) {
-        if (K[i] < 1) return refuse(who, "every block size K[i] is a positive integer");
-        if (K[i] > GPB_MAX_L) return refuse(who, "l = sum(K) <= 768 is required");
-        l += K[i];
-    }
-    if (l > GPB_MAX_L) return refuse(who, "l = sum(K) <= 768 is required");
-    if (a.ml < 0) return refuse(who, "ml >= 0 is required");
-    if (mnl + 1 + a.ml > GPB_MAX_ROWS) return refuse(who, "0 <= mnl and N = mnl + 1 + ml <= 192 are required");
-    if (a.p < 0 || a.p > a.n) return refuse(who, "0 <= p <= n is required");
-    a.m = (int)mnl + 1;
-    a.l = (int)l;
-    for (int i = 0; i < GPB_MAX_ROWS; i++) a.K[i] = i < a.m ? (unsigned short)K[i] : 0;
+    if (int rc = gphost::place_blocks(who, a, mnl, K)) return rc;
     if (gp_batch_lds_bytes(a.n, a.m, a.l, a.ml, a.p) > 160 * 1024) return refuse(who, "the member needs more than 160 KiB of LDS");
     if (!a.F || !a.c || (a.ml > 0 && (!a.G || !a.h)) || (a.p > 0 && (!a.A || !a.b))) return refuse(who, "a data pointer is NULL");
     if (!a.x || !a.s || !a.z || !a.stats || !a.iters || !a.exitc || (a.p > 0 && !a.y)) return refuse(who, "a result pointer is NULL");
     if (resident && !a.scratch) return refuse(who, "the scratch pointer is NULL");
-    const int64_t n = a.n, ml = a.ml, p = a.p;
+    const int64_t n = a.n, ml = a.ml, p = a.p, l = a.l;
     const Part parts[] = {{"F", a.sF, l * n}, {"g", a.sc, l}, {"G", a.sG, ml * n}, {"h", a.sh, ml}, {"A", a.sA, p * n}, {"b", a.sb, p}};
     for (const auto &t : parts)
         if (t.stride != 0 && t.stride < t.size)

@@ -186,11 +186,12 @@ __global__ void __launch_bounds__(QPB_THREADS) k_qp_batch_diff(QpDiffArgs a)
 // A workgroup holds OUTER_TILE entries of C.  Part q of OUTER_SPLIT adds the members q, q + OUTER_SPLIT, ... of an entry in
 // that order, the parts are added 0 .. OUTER_SPLIT - 1: an order that depends on these two constants alone, not on B, the
 // grid or the entry.  A member that is not done adds +0.  sym (the sum for P, rows = n): entries (r, c) and (c, r) evaluate one
-// expression, so the sum is symmetric to the last bit.
+// expression, so the sum is symmetric to the last bit.  ldu: two members of u1, u2 are that far apart (gp_batch_diff: the rows
+// of G inside columns of N rows).
 enum { OUTER_TILE = 32, OUTER_SPLIT = 8, OUTER_THREADS = OUTER_TILE * OUTER_SPLIT };
 
 __global__ void __launch_bounds__(OUTER_THREADS)
-k_batch_outer_sum(int64_t B, int rows, int n, const double *__restrict__ u1, const double *__restrict__ v1, const double *__restrict__ u2,
+k_batch_outer_sum(int64_t B, int rows, int ldu, int n, const double *__restrict__ u1, const double *__restrict__ v1, const double *__restrict__ u2,
                   const double *__restrict__ v2, double scale, int sym, const int64_t *__restrict__ gexit, double *__restrict__ C)
 {
     __shared__ double part[OUTER_SPLIT][OUTER_TILE];
@@ -201,7 +202,7 @@ k_batch_outer_sum(int64_t B, int rows, int n, const double *__restrict__ u1, con
     double acc = 0.0;
 #pragma unroll 4
     for (int64_t b = q; b < B; b += OUTER_SPLIT) {
-        const double t = u1[r + b * rows] * v1[c + b * n] + u2[r + b * rows] * v2[c + b * n];
+        const double t = u1[r + b * ldu] * v1[c + b * n] + u2[r + b * ldu] * v2[c + b * n];
         acc += gexit[b] == 0 ? t : 0.0;
     }
     part[q][le] = acc;
@@ -226,11 +227,11 @@ hipError_t launch_qp_batch_diff(hipStream_t st, const QpDiffArgs &a)
 }
 
 hipError_t launch_batch_outer_sum(hipStream_t st, int64_t B, int rows, int n, const double *u1, const double *v1, const double *u2,
-                                  const double *v2, double scale, bool sym, const int64_t *gexit, double *C)
+                                  const double *v2, double scale, bool sym, const int64_t *gexit, double *C, int ldu)
 {
     if (rows * n == 0) return hipSuccess;
     k_batch_outer_sum<<<dim3((unsigned)((rows * n + OUTER_TILE - 1) / OUTER_TILE)), dim3(OUTER_THREADS), 0, st>>>(
-        B, rows, n, u1, v1, u2, v2, scale, sym ? 1 : 0, gexit, C);
+        B, rows, ldu ? ldu : rows, n, u1, v1, u2, v2, scale, sym ? 1 : 0, gexit, C);
     return hipGetLastError();
 }
 

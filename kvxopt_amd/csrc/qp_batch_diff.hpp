@@ -79,6 +79,7 @@ hipError_t launch_qp_batch_diff(hipStream_t st, const QpDiffArgs &a);
 
 // C (rows x n, column-major) = scale * sum over the members b with gexit[b] == 0, in an order fixed at compile time, of
 // u1_b v1_b' + u2_b v2_b'; u1, u2 are rows x B and v1, v2 n x B.  sym (rows = n, u1 = v2, v1 = u2): C is symmetric to the last bit.
+// ldu: the distance between two members in u1 and u2 where they are `rows` rows of longer columns; 0: rows.
 hipError_t launch_batch_outer_sum(hipStream_t st, int64_t B, int rows, int n, const double *u1, const double *v1, const double *u2,
-                                  const double *v2, double scale, bool sym, const int64_t *gexit, double *C);
+                                  const double *v2, double scale, bool sym, const int64_t *gexit, double *C, int ldu = 0);
 }  // namespace kvx

@@ -38,7 +38,7 @@ they agree with central differences.  For derivatives solve with tolerances near
 with exit 2 at the limit of their precision, and are skipped here.
 
 The limits and the texts of the argument checks are those of qp_batch.  Every check runs before a device is asked for; there is
-no CPU fallback.  Not carried: several cotangents per call, derivatives of lp_batch / gp_batch (coneqp_batch: coneqpbatchdiff), gradients with
+no CPU fallback.  Not carried: several cotangents per call, derivatives of lp_batch (coneqp_batch: coneqpbatchdiff, gp_batch: gpbatchdiff), gradients with
 respect to y and z, the derivative fused into the forward launch, a torch.autograd.Function."""
 from . import _batchdiff, _lib, qpbatch
 from ._batchdiff import EXIT_DONE, EXIT_FAILED, EXIT_SKIPPED, MAX_REFINEMENT, WRT  # noqa: F401

@@ -45,6 +45,11 @@
     gp_batch(K, F, g, G=None, h=None, A=None, b=None, options=None)                  no counterpart: B small dense geometric programs
                                                                                      in one launch, K shared by the members
                                                                                      (-> gpbatch.gp_batch; reads its own `options` only)
+    gp_batch_vjp(K, F, g, G=None, h=None, A=None, b=None, *, sol, gx, wrt=...,       no counterpart: the gradients of a loss through a
+                 options=None)                                                       solved gp_batch, from its cotangent gx = dl/dx
+    gp_batch_jvp(K, F, g, G=None, h=None, A=None, b=None, *, sol, dF=None, ...,      no counterpart: the directional derivative of the
+                 db=None, options=None)                                              solution of a solved gp_batch
+                                                                                     (-> gpbatchdiff; options: 'refinement' 0..3 only)
     options                                                                        the module-level dict of the reference
 
 Like the reference, algorithm parameters come from `solvers.options` ('maxiters', 'abstol', 'reltol', 'feastol',
@@ -67,6 +72,7 @@ from .conelpbatch import conelp_batch  # noqa: F401
 from .coneqpbatch import coneqp_batch  # noqa: F401
 from .coneqpbatchdiff import coneqp_batch_jvp, coneqp_batch_vjp  # noqa: F401
 from .gpbatch import gp_batch  # noqa: F401
+from .gpbatchdiff import gp_batch_jvp, gp_batch_vjp  # noqa: F401
 from .lpbatch import lp_batch  # noqa: F401
 from .qpbatch import qp_batch  # noqa: F401
 from .qpbatchdiff import qp_batch_jvp, qp_batch_vjp  # noqa: F401
